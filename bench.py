@@ -10,12 +10,20 @@ default each rank evaluates a pod slice against the whole node snapshot, with no
 (dist.pod_partition); --shard nodes shards the nodes instead and merges the per-pod results
 with RCCL all-reduces (libyoda's yoda_comm_run, or yoda_amd/dist.py over torch).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries `roofline` (dominant
-kernel: algorithmic bytes / HIP-event-timed launch duration vs 8 TB/s) and `cpu_baseline`
-(the C oracle, reference-shaped, on a bounded pod sample, rank 0 at N=1 only).
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0): the
+contract fields (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`) and
+`roofline` (dominant kernel: algorithmic bytes / HIP-event-timed launch duration vs 8 TB/s,
+from the events of the timed steps themselves and the committed counter summary).
+--dump-outputs DIR also writes what the last timed step computed (the arrays yoda_download
+hands a caller) as DIR/<name>.npy in float64; the inputs are seeded, so two builds run with
+the same arguments can be compared output for output.  --full adds everything that takes
+runs of its own after the timed region: `e2e_ms`, `status_counts`, `extra` (work classes,
+the per-pair kernels, the variant workloads, plugin row latency, the config-5 greedy leg)
+and `cpu_baseline` (the C oracle, reference-shaped, on a bounded pod sample, rank 0 at N=1
+only); --no-extras, --no-greedy and --no-cpu-baseline trim a --full run.
 """
 from __future__ import annotations
 
@@ -404,6 +412,22 @@ def row_latency(dev_index: int, node_counts=(5000, 100000), cycles: int = 60) ->
     return out
 
 
+def dump_outputs(res, out_dir: str, rank: int, world: int) -> dict:
+    """--dump-outputs: the arrays of the last timed step (yoda_download's EvalResult: pick,
+    status, n_feasible, n_ties, top_score, maxima) as <out_dir>/<name>.npy, float64.  Every
+    pod is written (config 3: 100k pods, 8.8 MB in all).  pick / status / the counts are
+    exact in float64; top_score (i64) and maxima (u64) round above 2^53, the same way in
+    every run.  At N > 1 each rank writes its own part as <name>.rank<r>.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f".rank{rank}" if world > 1 else ""
+    written = {}
+    for name in ("pick", "status", "n_feasible", "n_ties", "top_score", "maxima"):
+        a = np.ascontiguousarray(getattr(res, name), dtype=np.float64)
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+        written[name] = list(a.shape)
+    return written
+
+
 def diskio_classes(pods) -> int:
     """Distinct Mode-B pod classes of a batch: (alpha, beta) bit pairs (algorithm.go:105-106,
     the grouping libyoda's Mode-B batch path evaluates once per class)."""
@@ -499,12 +523,22 @@ def main():
     ap.add_argument("--mode", choices=["scv", "diskio"], default="scv")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--cpu-threads", type=int, default=16)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="--workload eval: after the timed region also measure and check "
+                         "everything beside the headline (e2e_ms, status_counts, the "
+                         "disclosure runs of `extra`, cpu_baseline); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="--workload eval: write the outputs of the last timed step (pick, "
+                         "status, n_feasible, n_ties, top_score, maxima of every pod) as "
+                         "DIR/<name>.npy, float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full / --workload greedy: skip the C oracle baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the disclosure runs (work classes, per-pair path, mixed-model "
-                         "and F64 variants) after the timed region")
+                    help="--full: skip the disclosure runs (work classes, per-pair path, "
+                         "mixed-model and F64 variants) after the timed region")
     ap.add_argument("--no-greedy", action="store_true",
-                    help="skip the config-5 greedy leg of the disclosure runs (extra.greedy)")
+                    help="--full: skip the config-5 greedy leg of the disclosure runs "
+                         "(extra.greedy)")
     ap.add_argument("--check", action="store_true",
                     help="N>1: rank 0 re-evaluates the batch on one unsharded handle and "
                          "asserts identical picks / statuses / ties (rehearsal)")
@@ -530,6 +564,8 @@ def main():
                     help="eval: the headline batch (config 3); greedy: config 5 sequential "
                          "assume; row: the plugin's per-cycle row latency (P = 1)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.workload == "greedy":
         return bench_greedy(args)
     if args.workload == "row":
@@ -644,9 +680,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    # the outputs of the last timed step, for --dump-outputs and the checks of --full / --check
+    res = y.download() if args.full or args.dump_outputs or args.check else None
+    dumped = dump_outputs(res, args.dump_outputs, rank, world) if args.dump_outputs else None
+
     # End-to-end (pod H2D + kernels + picks D2H), single GPU only: reported, never `value`.
     e2e_ms = None
-    if world == 1:
+    if args.full and world == 1:
         # median of 9 after 2 untimed batches (the first upload of the loop wakes the host
         # pool and touches the staging pages): the host pod SoA -> yoda_upload_pods (pack +
         # one pinned H2D) -> yoda_run -> picks and statuses back to host memory
@@ -659,7 +699,6 @@ def main():
             if it >= 2:
                 ts.append((time.perf_counter() - t0) * 1e3)
         e2e_ms = float(np.median(ts))
-    res = y.download()
 
     ms_per_step = elapsed / args.steps * 1e3
     value = P * N / (elapsed / args.steps)
@@ -751,9 +790,13 @@ def main():
                      "step_unique_bytes": step_bytes,
                      "per_pair_model_bytes": bytes_per_pair(k_slots, mode),
                      "pmc_source": pmc_src},
-        "e2e_ms": e2e_ms,
-        "status_counts": {str(s): int((res.status == s).sum()) for s in np.unique(res.status)},
     }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
+    if args.full:
+        out["e2e_ms"] = e2e_ms
+        out["status_counts"] = {str(s): int((res.status == s).sum())
+                                for s in np.unique(res.status)}
     if world > 1 and args.check and rank == 0:
         full = Yoda(dev_index)
         full.upload_nodes(nodes)
@@ -765,9 +808,9 @@ def main():
                 raise SystemExit(f"--check: sharded {f} differs from the unsharded handle")
         out["check"] = ("rank 0's pod shard" if pod_shard else "merged") + \
             " picks/statuses/ties/feasible == unsharded"
-    if rank == 0 and world == 1 and not args.no_extras and mode == MODE_SCV:
+    if args.full and rank == 0 and world == 1 and not args.no_extras and mode == MODE_SCV:
         out["extra"] = disclosure(y, nodes, pods, step, barrier, args)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baselines(nodes, pods, mode, args.cpu_seconds,
                                             args.cpu_threads, res)
     if rank == 0:

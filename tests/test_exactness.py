@@ -60,8 +60,8 @@ def test_f64_lemma_random():
     assert np.array_equal(q, want)
 
 
-def test_c_checker_builds_and_passes_random():
-    exe = "/tmp/yoda_check_div_lemma"
+def test_c_checker_builds_and_passes_random(tmp_path):
+    exe = str(tmp_path / "check_div_lemma")
     subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-o", exe,
                     os.path.join(REPO, "tools", "check_div_lemma.c"), "-lm"], check=True)
     out = subprocess.run([exe, "r", "20000000"], capture_output=True, text=True)
