@@ -2874,6 +2874,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(K <= 8 ?
       return ok == 0u ? HUGE_VAL : ub;
     }
     const uint32_t* U = args.kbub;
+    // (the level bound alone, without the fm[] loads and the dependent U[2J] trip, was measured:
+    // it works 30 % more blocks on config 3 and K2 is 4 µs slower -- DESIGN.md §4)
     // the block's K largest frees and its level bound, all in flight together (the level
     // words do not depend on J); then the J-indexed bound: two round trips
     uint32_t fm[K];
@@ -3339,36 +3341,48 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(K <= 8 ?
     // only the blocks K1 found a feasible pod of this wave in (bit b of word b/64)
     const uint64_t* bw = blk + (size_t)uniform_u32(p >> 6) * blk_stride;
     const uint32_t b0 = n0 >> 6, b1 = (n1 + 63) >> 6;
-    // pruning: the chunk's high-bound blocks first (pass 0), then the rest (pass 1)
-    const int passes = prune && args.hot ? 2 : 1;
-    for (int pass = 0; pass < passes; ++pass)
-    for (uint32_t wi = b0 >> 6; b0 < b1 && wi <= (b1 - 1) >> 6; ++wi) {
-      uint64_t bits = bw[wi];
-      const uint32_t base = wi << 6;
-      if (b0 > base) bits &= ~0ull << (b0 - base);
-      if (b1 < base + 64) bits &= (1ull << (b1 - base)) - 1ull;
-      if (passes == 2) bits &= pass == 0 ? args.hot[wi] : ~args.hot[wi];
-      // the bounds of the word's 64 blocks, lane = block (one coalesced pass; a block is
+    // The chunk in chunk-relative windows of 64 blocks (as the block K1's lane = block pass): a
+    // chunk of at most 64 blocks is one window wherever it lies in the list words, so its
+    // bounds are evaluated once.  Pruning: the window's high-bound blocks first (hot), then
+    // the rest, against the same bounds.  (The hot mask has a row of blk_stride words too:
+    // a bit per block; without it every block is "hot": one pass in list order.)
+    const bool hot_first = prune && args.hot != nullptr;
+    // (without the hot mask the second row is the list's own again: two loads that hit the lines
+    // of the first and are ignored.  Guarding them with a branch on hot_first costs the config-3
+    // instantiation 2 more spilled VGPRs, 9 -> 11, and the mixed Q32 one 19 -> 21.)
+    const uint64_t* hw = hot_first ? args.hot : bw;
+    for (uint32_t wb = b0; wb < b1; wb += kWave) {
+      // the list words and the hot words of the window: up to four loads, issued together
+      const uint64_t bits_w = window_bits(bw, blk_stride, wb, b1);
+      const uint64_t hot_w = window_bits(hw, blk_stride, wb, b1);
+      // hot first, then the rest (bits, then rest: one list of blocks to visit)
+      uint64_t bits = hot_first ? bits_w & hot_w : bits_w;
+      uint64_t rest = hot_first ? bits_w & ~hot_w : 0ull;
+      // the bounds of the window's 64 blocks, lane = block (one coalesced pass; a block is
       // then skipped on a v_readlane and a compare against the current threshold)
       double ub_l = 0.0;
-      if (prune && bits != 0ull) {
-        ub_l = block_ub(min(base + lane, b1 - 1u));
+      if (prune && bits_w != 0ull) {
+        ub_l = block_ub(min(wb + lane, b1 - 1u));
         if (args.gbest != nullptr) {  // (the other chunks' progress)
           if constexpr (TOPK) refresh_thrk(); else refresh_thr();
         }
-        // every listed block of the word below the threshold: skipped at once
+        // every listed block of the window below the threshold: skipped at once
 #ifdef YODA_K2_WORDSKIP  // (A/B: off -- K2 0.218 vs 0.205 ms without, profiles/r05/g)
-        const double wmax = wave_max_f64(((bits >> lane) & 1ull) ? ub_l : -1.0);
+        const double wmax = wave_max_f64(((bits_w >> lane) & 1ull) ? ub_l : -1.0);
         if (pruned(wmax)) {
 #else
         if (false) {
 #endif
           if (STATS && !trace && lane == 0)
-            atomicAdd(stats + 13, (unsigned long long)__builtin_popcountll(bits));
-          bits = 0ull;
+            atomicAdd(stats + 13, (unsigned long long)__builtin_popcountll(bits_w));
+          bits = rest = 0ull;
         }
       }
-      while (bits) {
+      while ((bits | rest) != 0ull) {
+        if (bits == 0ull) {
+          bits = rest;
+          rest = 0ull;
+        }
         const uint32_t j = (uint32_t)__builtin_ctzll(bits);
         bits &= bits - 1;
         if (prune) {
@@ -3381,7 +3395,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(K <= 8 ?
             continue;
           }
         }
-        block((base + j) << 6);
+        block((wb + j) << 6);
         if (prune && worked && TOPK) {
           refresh_thrk();
         } else if (prune && worked) {

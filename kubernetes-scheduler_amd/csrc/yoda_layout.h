@@ -255,6 +255,25 @@ __host__ __device__ constexpr uint32_t bs_row(uint32_t n_nodes) { return (n_node
 __host__ __device__ constexpr uint32_t blk_row(uint32_t n_nodes) {
   return ((n_nodes + 63u) / 64u + 63u) / 64u;
 }
+// The 64-block window of one row of such bit words (a wave's block list, or the hot mask) that
+// starts at block wb: bit j = block wb + j, for the blocks below b1 (wb < b1, wb / 64 <
+// row_words).  A window that starts inside a word takes its upper part from the next word of the
+// row; the word after the row (another wave's, or the seeds) is never read -- the callers keep
+// b1 <= 64 * row_words; with a b1 beyond that the blocks past the row read as unlisted
+// (tools/check_k2_window.cpp covers both).  Both words are
+// loaded before either is used (the second index falls back to the first when it is not
+// needed), so a caller's loads of several rows go out together.
+__host__ __device__ inline uint64_t window_bits(const uint64_t* words, uint32_t row_words,
+                                                uint32_t wb, uint32_t b1) {
+  const uint32_t wi = wb >> 6, sh = wb & 63u;
+  const bool two = sh != 0u && wi + 1u < row_words && ((wi + 1u) << 6) < b1;
+  const uint64_t lo = words[wi], hi = words[two ? wi + 1u : wi];
+  uint64_t bits = lo >> sh;
+  if (two) bits |= hi << (64u - sh);
+  const uint32_t n = b1 - wb;
+  if (n < 64u) bits &= (1ull << n) - 1ull;
+  return bits;
+}
 
 // The block-grouped copies of the node summaries (private batch runs) that k_set_static keeps
 // current with the originals: inv[node] = its internal position.
