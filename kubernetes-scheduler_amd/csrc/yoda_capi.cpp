@@ -42,7 +42,7 @@ hipError_t launch_reduce1(const Partials& part, uint32_t C, uint32_t n_pods, uin
                           uint32_t* lpt_w = nullptr, uint32_t* lpt_order = nullptr,
                           const uint64_t* cmask = nullptr);
 hipError_t launch_k1_order(int K, const PodParams& pp, uint32_t n_pods, uint32_t n_nodes,
-                           uint32_t* wts, uint32_t* order, hipStream_t s);
+                           uint32_t* wts, uint32_t* order, K1WaveRec* rec, hipStream_t s);
 hipError_t launch_mem_rank(const uint64_t* m_u, uint32_t n_pods, const MemTab& mt, uint32_t* m32,
                            hipStream_t s);
 hipError_t launch_prep2(const uint64_t* maxima, uint32_t n_pods, double* rcp,
@@ -377,7 +377,7 @@ struct yoda_handle {
   void note_static(uint32_t n, uint64_t s) {
     if (n < ub_stat.size() && s <= ub_stat[n]) kbub_loose = true; else kbub_dirty = true;
   }
-  // the top tenth of the blocks by bound (ub[K]) at upload, per order: K2 visits them first
+  // the top tenth of the blocks by bound (lv[0]) at upload, per order: K2 visits them first
   DevBuf hot, hot_p;
   bool hot_ok = false;
   PermCopy perm_copy() const {
@@ -502,7 +502,8 @@ struct yoda_handle {
   // the block K1's own heaviest-first order (k1_probe's weights, ranked before the K1): valid
   // for this run once k1_sorted
   bool k1_sorted = false;
-  DevBuf k1_w, k1_order;
+  bool k1_rec_ok = false;  // k1_rec holds this run's records (written with the order)
+  DevBuf k1_w, k1_order, k1_rec;  // (k1_rec: the waves' K1WaveRec records, beside k1_w)
   uint32_t C2 = 1, chunk2 = 32;  // K2 / K3 node chunking
   int cap[2][3][2] = {};         // resident workgroups per (kernel, path, mode), cached
   int last_mode = -1;
@@ -566,7 +567,7 @@ struct yoda_handle {
                      &order_bstart, &order_slot, &order_bkt,
                      &rcp,       &best,       &idx,          &ties,
                      &lowest,    &pick,      &status,     &ties_out,     &flagged,
-                     &n_flagged, &bitmask,   &bitmask_t,  &blk,  &bsum, &p_max_u,      &p_cnt, &lpt_w, &lpt_order, &k1_w, &k1_order,
+                     &n_flagged, &bitmask,   &bitmask_t,  &blk,  &bsum, &p_max_u,      &p_cnt, &lpt_w, &lpt_order, &k1_w, &k1_order, &k1_rec,
                      &rows,      &rows_t,    &norm,      &tk_s_part,  &tk_i_part,    &tk_s,
                      &tk_i,      &upd_node,  &upd_val,    &upd_cn,    &g1_part,   &g1_done,
                      &p_best_f,  &p_best_i,  &p_idx,      &p_ties,       &p_low_f,
@@ -955,6 +956,7 @@ PodParams pod_params(yoda_t* h) {
     pp.lpt_w = h->lpt_w.as<uint32_t>();
     if (h->lpt_sorted) pp.lpt_order = h->lpt_order.as<uint32_t>();
     if (h->k1_sorted) pp.k1_order = h->k1_order.as<uint32_t>();
+    if (h->k1_sorted && h->k1_rec_ok) pp.k1_rec = h->k1_rec.as<K1WaveRec>();
   }
   return pp;
 }
@@ -1473,16 +1475,25 @@ int phase1(yoda_t* h, int mode, uint64_t* maxima, uint32_t* counts,
   // the block K1 visits its pod blocks heaviest first too (k1_probe: the per-node work its
   // whole-block decisions leave each wave on a sample of blocks; YODA_K1_LPT=0: launch order)
   static const bool k1_lpt_env = YODA_KNOB("YODA_K1_LPT", 1) != 0;
-  h->k1_sorted = false;
+  h->k1_sorted = h->k1_rec_ok = false;
   if (k1_lpt_env && h->lpt_active && h->k1_sub == 1u && mode == YODA_MODE_SCV) {
     const PodParams pp0 = pod_params(h);
     if (pp0.bsum != nullptr) {
       const uint32_t n_pb = (P + kBlock - 1) / kBlock;
       HIP_TRY(h, h->k1_w.ensure((size_t)((P + 63) / 64) * 4));
       HIP_TRY(h, h->k1_order.ensure((size_t)n_pb * 4));
+      // (a private run -- yoda_run, the only caller with final maxima: the probe leaves each
+      // wave's bounds for the block K1 of this run.  The row, shard and greedy entry points pass
+      // no record, and their K1 computes its set-up per chunk task; so does every run under the
+      // A/B knob YODA_K1_REC=0)
+      static const bool k1_rec_knob = YODA_KNOB("YODA_K1_REC", 1) != 0;
+      const bool k1_rec_env = k1_rec_knob && final_maxima;
+      if (k1_rec_env) HIP_TRY(h, h->k1_rec.ensure((size_t)((P + 63) / 64) * sizeof(K1WaveRec)));
       HIP_TRY(h, launch_k1_order(h->K, pp0, P, h->n_nodes, h->k1_w.as<uint32_t>(),
-                                 h->k1_order.as<uint32_t>(), h->stream));
+                                 h->k1_order.as<uint32_t>(),
+                                 k1_rec_env ? h->k1_rec.as<K1WaveRec>() : nullptr, h->stream));
       h->k1_sorted = true;
+      h->k1_rec_ok = k1_rec_env;
     }
   }
   // (the K1 profile events bracket the K1 launch alone, as rocprofv3's kernel trace does)
@@ -2616,7 +2627,7 @@ int yoda_upload_nodes(yoda_t* h, const yoda_node_soa* nd, uint32_t node_offset, 
     h->hot_ok = false;
     if (h->has_k2sum && h->g.tab && N > 0) {
       HIP_TRY(h, build_block_ub(h));
-      // the blocks whose bound with every card qualifying (ub[K]) is in the top tenth: a
+      // the blocks whose bound with every card qualifying (lv[0]) is in the top tenth: a
       // static visiting order hint for the argmax K2 (results do not depend on it)
       const uint32_t nb = (N + 63) / 64, KST = kbub_stride(K);
       std::vector<uint32_t> ubw(sum_words(nb, KST));
@@ -2627,8 +2638,8 @@ int yoda_upload_nodes(yoda_t* h, const yoda_node_soa* nd, uint32_t node_offset, 
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         std::vector<double> u(nb);
         for (uint32_t b = 0; b < nb; ++b) {
-          const uint64_t bits = (uint64_t)ubw[sum_index(b, 2 * K, KST)] |
-                                ((uint64_t)ubw[sum_index(b, 2 * K + 1, KST)] << 32);
+          const uint64_t bits = (uint64_t)ubw[sum_index(b, kbub_lvl(K), KST)] |
+                                ((uint64_t)ubw[sum_index(b, kbub_lvl(K) + 1u, KST)] << 32);
           std::memcpy(&u[b], &bits, 8);
         }
         std::vector<double> srt(u);

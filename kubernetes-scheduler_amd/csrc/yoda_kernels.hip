@@ -762,7 +762,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WIT ? 4 
     unsigned long long* __restrict__ seed_out = nullptr,
     unsigned long long* __restrict__ cmask = nullptr,
     const uint32_t* __restrict__ ids = nullptr,
-    const uint32_t* __restrict__ pb_order = nullptr) {
+    const uint32_t* __restrict__ pb_order = nullptr,
+    const K1WaveRec* __restrict__ wrec = nullptr) {
   static_assert(!(WIT && MIX), "the witness K1 serves one-model snapshots");
   static_assert(SUB == 1 || (SUB == kBlock / kWave && !WIT), "SUB: 1, or one pod wave per workgroup");
   constexpr uint32_t SS = k1sum_stride(K);
@@ -804,26 +805,64 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WIT ? 4 
     need_mem = need_mem_in[p];
     need_clk = need_clk_in[p];
   }
+  // lane l's free level (kb_levels), in the load round of the pod arrays (l_hi below)
+  uint32_t lev = 0u;
+  if (levels != nullptr) lev = levels[lane & (kKbLevels - 1u)];
   // ---- wave bounds (pm: pods with the scv/memory label, pc: with scv/clock) ----
-  const bool pm = live && need_mem > 0, pc = live && need_clk > 0;
-  const uint64_t pm_mask = ballot(pm), pc_mask = ballot(pc);
-  const bool any_pm = pm_mask != 0, all_pm = pm_mask == live_mask;
-  const bool any_pc = pc_mask != 0, all_pc = pc_mask == live_mask;
-  const uint64_t num_max = wave_max_u64(live ? number : 0ull);
-  const uint64_t num_min = wave_min_u64(live ? number : ~0ull);
-  const uint32_t nm_max = wave_max_u32(pm ? need_mem : 0u);
-  const uint32_t nm_min = wave_min_u32(pm ? need_mem : ~0u);
+  // wrec (yoda_run's K1, SUB = 1; nullptr from every other entry point): k1_probe computed
+  // them once for the wave; each of its chunk tasks reads the record in the load round of the
+  // pod arrays instead of reducing them again, and the per-lane values above are first waited
+  // for in the per-pod pass.
+  bool any_pm, all_pm, any_pc, all_pc, c_uni;
+  uint64_t num_max, num_min;
+  uint32_t nm_max, nm_min, nc_max, nc_min, cpc_max;
   // (bounds compared only against node-lane values stay in VGPRs: fewer SGPR spills, whose
   // v_readlane reloads cost issue slots in every block; profiles/r02/final/k1_occupancy_ab.txt)
-  const uint32_t mpm_max = wave_max_u32v(pm ? m : 0u);
-  const uint32_t mpm_min = wave_min_u32v(pm ? m : ~0u);
-  const uint32_t nc_max = wave_max_u32(pc ? need_clk : 0u);
-  const uint32_t nc_min = wave_min_u32(pc ? need_clk : ~0u);
-  const uint32_t cpc_max = wave_max_u32(pc ? c : 0u);
-  const uint32_t cpc_min = wave_min_u32(pc ? c : ~0u);
-  const uint32_t m_max = wave_max_u32v(live ? m : 0u), m_min = wave_min_u32v(live ? m : ~0u);
-  const uint32_t c_max = wave_max_u32v(live ? c : 0u), c_min = wave_min_u32v(live ? c : ~0u);
-  const bool c_uni = cpc_min == cpc_max;
+  uint32_t mpm_max, mpm_min, m_max, m_min, c_max, c_min;
+  uint32_t l_hi_rec = kKbLevels - 1u;
+  if (SUB == 1 && wrec != nullptr) {
+    const K1WaveRec* rv = wrec + (p >> 6);                // (per-lane address: VGPR values)
+    const K1WaveRec* rs = wrec + uniform_u32(p >> 6);     // (uniform address: scalar values)
+    mpm_min = rv->mpm_min;
+    mpm_max = rv->mpm_max;
+    m_min = rv->m_min;
+    m_max = rv->m_max;
+    c_min = rv->c_min;
+    c_max = rv->c_max;
+    num_min = rs->num_min;
+    num_max = rs->num_max;
+    cpc_max = rs->cpc_max;
+    nc_min = rs->nc_min;
+    nc_max = rs->nc_max;
+    nm_min = rs->nm_min;
+    nm_max = rs->nm_max;
+    const uint32_t fl = rs->flags;
+    any_pm = (fl & kK1RecAnyPm) != 0u;
+    all_pm = (fl & kK1RecAllPm) != 0u;
+    any_pc = (fl & kK1RecAnyPc) != 0u;
+    all_pc = (fl & kK1RecAllPc) != 0u;
+    c_uni = (fl & kK1RecCUni) != 0u;
+    l_hi_rec = fl >> 8;
+  } else {
+    const bool pm = live && need_mem > 0, pc = live && need_clk > 0;
+    const uint64_t pm_mask = ballot(pm), pc_mask = ballot(pc);
+    any_pm = pm_mask != 0, all_pm = pm_mask == live_mask;
+    any_pc = pc_mask != 0, all_pc = pc_mask == live_mask;
+    num_max = wave_max_u64(live ? number : 0ull);
+    num_min = wave_min_u64(live ? number : ~0ull);
+    nm_max = wave_max_u32(pm ? need_mem : 0u);
+    nm_min = wave_min_u32(pm ? need_mem : ~0u);
+    mpm_max = wave_max_u32v(pm ? m : 0u);
+    mpm_min = wave_min_u32v(pm ? m : ~0u);
+    nc_max = wave_max_u32(pc ? need_clk : 0u);
+    nc_min = wave_min_u32(pc ? need_clk : ~0u);
+    cpc_max = wave_max_u32(pc ? c : 0u);
+    const uint32_t cpc_min = wave_min_u32(pc ? c : ~0u);
+    m_max = wave_max_u32v(live ? m : 0u), m_min = wave_min_u32v(live ? m : ~0u);
+    c_max = wave_max_u32v(live ? c : 0u), c_min = wave_min_u32v(live ? c : ~0u);
+    c_uni = cpc_min == cpc_max;
+    l_hi_rec = kb_level_hi(ballot(lev < m_max), kKbLevels);
+  }
   // hfs slot of the (1-based) need; a need beyond the K slots has no such card (hfs = 0)
   const bool hfs_all_ok = nm_max <= (uint32_t)K, hfs_none_ok = nm_min <= (uint32_t)K;
   const uint32_t hfs_all = kSumHfs + (any_pm && hfs_all_ok ? nm_max - 1u : 0u);
@@ -904,8 +943,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WIT ? 4 
   if (seeding && lane == 0) *sdw = 0ull;
   // ALL blocks: kbub's lv[l_hi], l_hi = the smallest free level >= the wave's largest scv/memory
   uint32_t l_hi = kKbLevels - 1u;
-  if (seeding && kbub != nullptr && levels != nullptr)
-    for (uint32_t l = kKbLevels - 1u; l-- > 0u;) l_hi = levels[l] >= s_m_max ? l : l_hi;
+  if (seeding && kbub != nullptr && levels != nullptr) l_hi = l_hi_rec;
   const uint32_t bs_tn = kBsT + (uint32_t)K + (hfs_none_ok && nm_min > 0u ? nm_min - 1u : 0u);
   const uint32_t bs_ta = kBsT + (any_pm && hfs_all_ok && nm_max > 0u ? nm_max - 1u : 0u);
   const K1Wave kw{num_min, num_max, s_mpm_min, s_mpm_max, s_m_min, s_m_max, s_c_min, s_c_max,
@@ -1666,7 +1704,8 @@ __global__ __launch_bounds__(kBlock) void k1_probe(
     const uint32_t* __restrict__ m_in, const uint32_t* __restrict__ c_in,
     const uint64_t* __restrict__ number_in, const uint32_t* __restrict__ need_mem_in,
     const uint32_t* __restrict__ need_clk_in, uint32_t n_pods, uint32_t n_nodes,
-    const uint32_t* __restrict__ bsm, uint32_t bst, uint32_t K, uint32_t* __restrict__ wts) {
+    const uint32_t* __restrict__ bsm, uint32_t bst, uint32_t K, uint32_t* __restrict__ wts,
+    const uint32_t* __restrict__ levels, K1WaveRec* __restrict__ rec) {
   const uint32_t lane = lane_id();
   const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
   const bool live = p < n_pods;
@@ -1715,6 +1754,32 @@ __global__ __launch_bounds__(kBlock) void k1_probe(
   const K1BlockClass cls = k1_block_class(bsm + sum_index(bv ? bi : 0u, 0, bst), bv, w, false);
   const uint64_t und = ballot(bv && cls.nreal > 0u && !cls.none && !cls.all);
   if (lane == 0) wts[p >> 6] = 1u + (uint32_t)__builtin_popcountll(und);
+  if (rec != nullptr) {  // the wave's bounds for its chunk tasks of the block K1 (K1WaveRec)
+    // l_hi: the smallest free level >= the wave's largest scv/memory (the K1's seed bound)
+    uint32_t l_hi = kKbLevels - 1u;
+    if (levels != nullptr)
+      l_hi = kb_level_hi(ballot(levels[lane & (kKbLevels - 1u)] < w.m_max), kKbLevels);
+    if (lane == 0) {
+      K1WaveRec r;
+      r.num_min = w.num_min;
+      r.num_max = w.num_max;
+      r.mpm_min = w.mpm_min;
+      r.mpm_max = w.mpm_max;
+      r.m_min = w.m_min;
+      r.m_max = w.m_max;
+      r.c_min = w.c_min;
+      r.c_max = w.c_max;
+      r.cpc_max = w.cpc_max;
+      r.nc_min = w.nc_min;
+      r.nc_max = w.nc_max;
+      r.nm_min = nm_min;
+      r.nm_max = nm_max;
+      r.flags = (w.any_pm ? kK1RecAnyPm : 0u) | (w.all_pm ? kK1RecAllPm : 0u) |
+                (w.any_pc ? kK1RecAnyPc : 0u) | (w.all_pc ? kK1RecAllPc : 0u) |
+                (w.c_uni ? kK1RecCUni : 0u) | (l_hi << 8);
+      rec[p >> 6] = r;
+    }
+  }
 }
 
 __global__ __launch_bounds__(1024) void k_lpt_order(uint32_t* __restrict__ wts,
@@ -2114,15 +2179,15 @@ hipError_t launch_lpt_order(uint32_t* wts, uint32_t n_pods, uint32_t* order, hip
 }
 
 // The block K1's heaviest-first pod-block order: k1_probe's per-wave weights into wts, ranked by
-// k_lpt_order into order (n_pb entries).
+// k_lpt_order into order (n_pb entries); rec (optional): the waves' K1WaveRec records.
 hipError_t launch_k1_order(int K, const PodParams& pp, uint32_t n_pods, uint32_t n_nodes,
-                           uint32_t* wts, uint32_t* order, hipStream_t s) {
+                           uint32_t* wts, uint32_t* order, K1WaveRec* rec, hipStream_t s) {
   const uint32_t n_pb = (n_pods + kBlock - 1) / kBlock;
   if (n_pb == 0 || n_pb > kLptMax || pp.bsum == nullptr || K < 1 || K > 16)
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(k1_probe, dim3(n_pb), dim3(kBlock), 0, s, pp.m_32, pp.c_32, pp.number,
                      pp.need_mem, pp.need_clk, n_pods, n_nodes, pp.bsum, bsum_stride(K),
-                     (uint32_t)K, wts);
+                     (uint32_t)K, wts, pp.kb_levels, rec);
   const hipError_t e = hipGetLastError();
   return e != hipSuccess ? e : launch_lpt_order(wts, n_pods, order, s);
 }
@@ -2144,26 +2209,9 @@ __global__ __launch_bounds__(kWave) void k_block_ub(const uint32_t* __restrict__
                                             ((uint64_t)sum2[sum_index(n, kS2Static + 1, S2)] << 32)));
     cnt = (sum2[sum_index(n, kS2Meta, S2)] >> 8) & 0xffu;
   }
-  uint32_t bq = 0;  // B_G[min(j, cnt)], j ascending
-#pragma unroll
-  for (int j = 0; j <= K; ++j) {
-    if (j > 0 && v && (uint32_t)j <= cnt) bq = tab[sum_index(n, (uint32_t)j - 1u, GS)];
-    double u = v ? stat + (double)bq : -1.0;  // exact: integers below 2^53
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) u = fmax(u, __shfl_xor(u, off, kWave));
-    if (threadIdx.x == 0) {
-      const uint64_t ub = (uint64_t)__double_as_longlong(u);
-      o_at(2 * j) = (uint32_t)ub;
-      o_at(2 * j + 1) = (uint32_t)(ub >> 32);
-    }
-  }
   uint32_t fs[K];
 #pragma unroll
-  for (int k = 0; k < K; ++k) {
-    fs[k] = v ? sum2[sum_index(n, kS2Fs + (uint32_t)k, S2)] : 0u;
-    const uint32_t fm = wave_max_u32(fs[k]);
-    if (threadIdx.x == 0) o_at(kbub_fmax(K) + k) = fm;
-  }
+  for (int k = 0; k < K; ++k) fs[k] = v ? sum2[sum_index(n, kS2Fs + (uint32_t)k, S2)] : 0u;
   // the level bounds lv[l]: static + B_G[nq(t_l)] maximised over the block's real nodes
   for (uint32_t l = 0; l < kKbLevels; ++l) {
     const uint32_t t = levels[l];
@@ -2252,8 +2300,8 @@ __global__ __launch_bounds__(kWave) void k_block_dec(const uint32_t* __restrict_
     o_at(kDecPw) = mpw;
     put_d(kDecStat, st);
   }
-  for (uint32_t l = 0; l < kKbLevels; ++l) {
-    const uint32_t t = levels[l];
+  for (uint32_t l = 0; l < kKbDecLevels; ++l) {  // (every other level of kb_levels)
+    const uint32_t t = levels[2u * l];
     uint32_t q = 0;
     double f = 0.0, tt = 0.0;  // exact: sums of at most 16 values below 2^44
 #pragma unroll
@@ -2673,6 +2721,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(K <= 8 ?
   using RS = std::conditional_t<Q32, float, double>;  // small-field reciprocal type
   ScorerN32<RS> sc;
   if (live) sc.load(args, p, n_pods);
+  // lane l's free level (kb_levels; a power-of-two count), in the load round of the pod arrays:
+  // l_lo below is then a compare and a ballot, not a scalar search after the set detection
+  static_assert((kKbLevels & (kKbLevels - 1u)) == 0u && kKbLevels <= kWave, "one level per lane");
+  uint32_t lev = 0u;
+  if (args.levels != nullptr) lev = args.levels[lane & (kKbLevels - 1u)];
   // A pod feasible on no node has no bit in any mask: it takes no part in the wave's bounds
   // and reciprocal sets, and its outputs stay "no node".
   const bool act = live && (args.cnt == nullptr || args.cnt[p] != 0u);
@@ -2755,8 +2808,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(K <= 8 ?
   const uint32_t m_max = wave_max_u32(act ? sc.m : 0u), m_min = wave_min_u32(act ? sc.m : ~0u);
   const uint32_t c_max = wave_max_u32(act ? sc.c : 0u), c_min = wave_min_u32(act ? sc.c : ~0u);
   // Block pruning (argmax, G waves): a block whose bound -- the most any node of it can score
-  // for a pod with at most J qualifying cards, J from the block's largest frees and the wave's
-  // smallest scv/memory (kbub_*) -- is below every active lane's best so far cannot hold a
+  // for a pod whose scv/memory is at least the free level under the wave's smallest (kbub_*'s
+  // lv[l_lo]) -- is below every active lane's best so far cannot hold a
   // pick or a tie of any of them.  thr: the min over active lanes of that best, refreshed
   // after each block the wave works on (it only grows, so a stale value stays a lower bound).
   // TOPK (greedy windows): a block whose best possible key cannot beat any active lane's
@@ -2805,10 +2858,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(K <= 8 ?
   }
   // the largest free level <= the wave's smallest scv/memory: every active pod qualifies at
   // most nq(t) cards on every node, so kbub's lv[l_lo] bounds the block too (its word: lvw)
-  uint32_t lvw = 0, l_lo = 0;
+  // (without levels: lv[0], the bound with every card qualifying)
+  uint32_t lvw = kbub_lvl(K), l_lo = 0;
   if (prune && args.levels != nullptr) {
-    for (uint32_t l = 1; l < kKbLevels; ++l) l_lo = args.levels[l] <= m_min ? l : l_lo;
-    l_lo = uniform_u32(l_lo);
+    l_lo = kb_level_lo(ballot(lev <= m_min), kKbLevels);
     lvw = kbub_lvl(K) + 2u * l_lo;
   }
   uint64_t thrk = 0ull;
@@ -2841,9 +2894,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(K <= 8 ?
   // One block: the wave's mask of node nb + lane and its summary (kept for the per-pod pass,
   // read back with v_readlane), loaded together: one memory latency per block.
   bool worked = false;  // the last block() call did the block's work (not pruned / empty)
-  // a block's bound for this wave (kbub_*): J = the most cards any pod of the wave can
-  // qualify on any node of it (from the block's largest frees and the wave's smallest
-  // scv/memory), ub = static + B_G[J] maximised over the block's nodes
+  // a block's bound for this wave (kbub_*): static + B_G[nq(t)] maximised over the block's
+  // nodes, t the largest free level <= the wave's smallest scv/memory (no pod of the wave
+  // qualifies more than nq(t) cards on a node)
   auto block_ub = [&](uint32_t b) -> double {
     if (dec) {  // static + nq shared + 3 r_free F + r_total T, each maximised over the block
       constexpr uint32_t DS = kbdec_stride();
@@ -2853,9 +2906,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(K <= 8 ?
       const uint32_t ok = D[sum_index(b, kDecOk, DS)];
       const uint32_t wbw = D[sum_index(b, kDecBw, DS)], wck = D[sum_index(b, kDecCk, DS)];
       const uint32_t wco = D[sum_index(b, kDecCo, DS)], wpw = D[sum_index(b, kDecPw, DS)];
-      const uint32_t wq = D[sum_index(b, kDecQl + l_lo, DS)];
+      const uint32_t dl = kbdec_level(l_lo);  // (the table's level at or under l_lo's)
+      const uint32_t wq = D[sum_index(b, kDecQl + dl, DS)];
       uint32_t w2[6];
-      const uint32_t wsrc[3] = {kDecStat, kbdec_fl(l_lo), kbdec_tl(l_lo)};
+      const uint32_t wsrc[3] = {kDecStat, kbdec_fl(dl), kbdec_tl(dl)};
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
         w2[2 * i] = D[sum_index(b, wsrc[i], DS)];
@@ -2874,24 +2928,13 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(K <= 8 ?
       return ok == 0u ? HUGE_VAL : ub;
     }
     const uint32_t* U = args.kbub;
-    // (the level bound alone, without the fm[] loads and the dependent U[2J] trip, was measured:
-    // it works 30 % more blocks on config 3 and K2 is 4 µs slower -- DESIGN.md §4)
-    // the block's K largest frees and its level bound, all in flight together (the level
-    // words do not depend on J); then the J-indexed bound: two round trips
-    uint32_t fm[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) fm[k] = U[sum_index(b, kbub_fmax(K) + (uint32_t)k, KBST)];
-    // (lvw == 0: no level bound -- words 0 and 1 read and ignored, so no branch splits the group)
-    const uint32_t lv_lo = U[sum_index(b, lvw, KBST)], lv_hi = U[sum_index(b, lvw + 1u, KBST)];
-    __builtin_amdgcn_sched_group_barrier(0x0020, K + 2, 0);  // (the VMEM reads above, grouped)
-    uint32_t J = 0;
-#pragma unroll
-    for (int k = 0; k < K; ++k) J += fm[k] >= m_min ? 1u : 0u;
-    double ub = __longlong_as_double((long long)((uint64_t)U[sum_index(b, 2 * J, KBST)] |
-                                                 ((uint64_t)U[sum_index(b, 2 * J + 1, KBST)] << 32)));
-    if (lvw != 0u)
-      ub = fmin(ub, __longlong_as_double((long long)((uint64_t)lv_lo | ((uint64_t)lv_hi << 32))));
-    return ub;
+    // The level bound alone: two words in one round trip, in flight with the window's list
+    // words.  (Until the levels went from 32 to 64 the bound also took the min with a table
+    // entry ub[J], J from the block's K largest frees and the wave's exact smallest
+    // scv/memory: K more loads and a dependent trip.  At 64 levels that form prunes no more on config 3 and
+    // K2 is slower with it on the variant workloads -- DESIGN.md §4.)
+    return __longlong_as_double((long long)((uint64_t)U[sum_index(b, lvw, KBST)] |
+                                            ((uint64_t)U[sum_index(b, lvw + 1u, KBST)] << 32)));
   };
   auto pruned = [&](double ub) -> bool {
     if constexpr (TOPK) {  // (ub >= 0; a score is an integer <= floor(ub); beyond 2^52: none)
@@ -3302,11 +3345,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(K <= 8 ?
   // U nodes', and (gbest) every other chunk's, which this one publishes its own to); each
   // value is a score the lane reaches on a feasible node, so thr stays below every lane's best
   unsigned long long gpub = 0ull;  // the largest value this lane published to gbest
-  auto refresh_thr = [&]() {
+  // (g: the lane's gbest word, loaded by the caller -- the window's first refresh has it in
+  // flight with the window's words and bounds)
+  auto refresh_thr_g = [&](unsigned long long g) {
     const double wu = wave_allreduce(ubest, OpMaxF64{});
     double lb = act ? fmax(rties > 0u ? (double)rbest : -1.0, wu) : HUGE_VAL;
     if (args.gbest != nullptr && act) {  // (score + 1; 0: none yet)
-      const unsigned long long g = args.gbest[p];
       const unsigned long long mine = lb >= 0.0 ? (unsigned long long)lb + 1ull : 0ull;
       // (published once per value: the load may see a stale line, not this lane's own atomic)
 #ifndef YODA_GBEST_REPUB
@@ -3323,19 +3367,23 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(K <= 8 ?
     thr = fmax(thr, __longlong_as_double(
                         (long long)uniform_u64((uint64_t)__double_as_longlong(lb))));
   };
+  auto load_gbest = [&]() -> unsigned long long {
+    return (args.gbest != nullptr && act) ? args.gbest[p] : 0ull;
+  };
+  auto refresh_thr = [&]() { refresh_thr_g(load_gbest()); };
   // TOPK: thrk := the min over active lanes of their k-th key so far (own list or the U list:
   // the merged list's k-th is at least either) -- and (gbest) the largest k-th key any chunk
   // has published for the lane: a chunk whose own list has k keys >= x proves the lane's global
   // k-th key >= x, so a block that cannot beat it holds none of the lane's top k
-  auto refresh_thrk = [&]() {
+  auto refresh_thrk_g = [&](unsigned long long g) {
     uint64_t kth = act ? (pl[TL - 1] > ul[TL - 1] ? pl[TL - 1] : ul[TL - 1]) : ~0ull;
     if (args.gbest != nullptr && act) {
-      const unsigned long long g = args.gbest[p];
       if (kth > g) atomicMax(args.gbest + p, (unsigned long long)kth);
       kth = kth > g ? kth : g;
     }
     thrk = wave_min_u64(kth);
   };
+  auto refresh_thrk = [&]() { refresh_thrk_g(load_gbest()); };
   const uint64_t t_setup = STATS ? wall_clock64() : 0ull;
   if (blk) {
     // only the blocks K1 found a feasible pod of this wave in (bit b of word b/64)
@@ -3355,51 +3403,36 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(K <= 8 ?
       // the list words and the hot words of the window: up to four loads, issued together
       const uint64_t bits_w = window_bits(bw, blk_stride, wb, b1);
       const uint64_t hot_w = window_bits(hw, blk_stride, wb, b1);
-      // hot first, then the rest (bits, then rest: one list of blocks to visit)
-      uint64_t bits = hot_first ? bits_w & hot_w : bits_w;
-      uint64_t rest = hot_first ? bits_w & ~hot_w : 0ull;
-      // the bounds of the window's 64 blocks, lane = block (one coalesced pass; a block is
-      // then skipped on a v_readlane and a compare against the current threshold)
+      // the lane's gbest word and the bounds of the window's 64 blocks, lane = block, issued
+      // with the words above: nothing here waits for a list word (the block index is clamped
+      // into the chunk, so a window without a listed block reads bounds it does not use)
+      const unsigned long long g_w = prune ? load_gbest() : 0ull;
       double ub_l = 0.0;
-      if (prune && bits_w != 0ull) {
+      if (prune) {
         ub_l = block_ub(min(wb + lane, b1 - 1u));
         if (args.gbest != nullptr) {  // (the other chunks' progress)
-          if constexpr (TOPK) refresh_thrk(); else refresh_thr();
-        }
-        // every listed block of the window below the threshold: skipped at once
-#ifdef YODA_K2_WORDSKIP  // (A/B: off -- K2 0.218 vs 0.205 ms without, profiles/r05/g)
-        const double wmax = wave_max_f64(((bits_w >> lane) & 1ull) ? ub_l : -1.0);
-        if (pruned(wmax)) {
-#else
-        if (false) {
-#endif
-          if (STATS && !trace && lane == 0)
-            atomicAdd(stats + 13, (unsigned long long)__builtin_popcountll(bits_w));
-          bits = rest = 0ull;
+          if constexpr (TOPK) refresh_thrk_g(g_w); else refresh_thr_g(g_w);
         }
       }
-      while ((bits | rest) != 0ull) {
-        if (bits == 0ull) {
-          bits = rest;
-          rest = 0ull;
-        }
-        const uint32_t j = (uint32_t)__builtin_ctzll(bits);
-        bits &= bits - 1;
-        if (prune) {
-          const uint64_t ubb = (uint64_t)__double_as_longlong(ub_l);
-          const double ub = __longlong_as_double(
-              (long long)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(ubb >> 32), (int)j) << 32) |
-                          (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)ubb, (int)j)));
-          if (pruned(ub)) {
-            if (STATS && !trace && lane == 0) atomicAdd(stats + 13, 1ull);
-            continue;
-          }
-        }
+      // todo: the listed blocks neither visited nor pruned yet.  One compare and a ballot drop
+      // every block whose bound is below the threshold (again after each refresh: the threshold
+      // only rises); a window with none left ends here.  The hot blocks first, then the rest.
+      uint64_t todo = bits_w;
+      auto drop_pruned = [&]() {
+        const uint64_t cand = ballot(!pruned(ub_l));
+        if (STATS && !trace && lane == 0 && (todo & ~cand) != 0ull)
+          atomicAdd(stats + 13, (unsigned long long)__builtin_popcountll(todo & ~cand));
+        todo &= cand;
+      };
+      if (prune) drop_pruned();
+      while (todo != 0ull) {
+        const uint64_t first = (todo & hot_w) != 0ull ? (todo & hot_w) : todo;
+        const uint32_t j = (uint32_t)__builtin_ctzll(first);
+        todo &= ~(1ull << j);
         block((wb + j) << 6);
-        if (prune && worked && TOPK) {
-          refresh_thrk();
-        } else if (prune && worked) {
-          refresh_thr();
+        if (prune && worked) {
+          if constexpr (TOPK) refresh_thrk(); else refresh_thr();
+          drop_pruned();
         }
       }
     }
@@ -5032,7 +5065,7 @@ hipError_t launch_k1(int K, Path path, const unsigned char* nodes, const unsigne
                                       pp.kbub_exact ? pp.kbub : nullptr, pp.kb_levels,           \
                                       reinterpret_cast<unsigned long long*>(pp.seed),          \
                                       reinterpret_cast<unsigned long long*>(pp.cmask1), pp.ids, \
-                                      pp.k1_order))
+                                      pp.k1_order, sub == 1u ? pp.k1_rec : nullptr))
         if (sub == 1u) {
           if (stats) YODA_K1B(KK, true)
           else if (pp.one_model) YODA_K1B(KK, false, false)

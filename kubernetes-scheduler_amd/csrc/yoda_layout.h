@@ -145,26 +145,44 @@ __host__ __device__ constexpr uint32_t bsum_stride(int k) { return 4u * (kBsT + 
 // K2 block bounds (N32 path; waves whose reciprocals are the G table's): per 64-node block of a
 // summary order, u32 words (kbub_stride(K) bytes a block), in tiles of 64 blocks word-major
 // (sum_index(block, word, kbub_stride(K))) so that a wave reads 64 blocks' bounds coalesced:
-//   ub[j]    (f64, words 2j, 2j + 1; j = 0..K)  the max over the block's real nodes of
-//            static + B_G[min(j, len(CardList))] -- no pod with at most j qualifying cards on
-//            every node of the block scores more there (basic <= B_G[nq], nq <= j)
-//   fmax[k]  (u32, from word 2K + 2; k < K)  the max over the nodes of fs[k] (K2 summary): a
-//            pod with scv/memory m qualifies at most #{k : fmax[k] >= m} cards on any of them
 //   lv[l]    (f64, words kbub_lvl(K) + 2l, 2l + 1; l < kKbLevels)  the max over the block's real
 //            nodes of static + B_G[nq(t_l)], nq(t) = min(#{fs >= t}, len(CardList)), at the
-//            snapshot's free levels t_0 = 0 < t_1 < ... < t_{L-1} = 0xFFFFFFFF (kb_levels):
+//            snapshot's free levels t_0 = 0 < t_1 < ... < t_{L-1} = 0xFFFFFFFF (kb_levels);
+//            -1.0 for a block without a real node:
 //            - an UPPER bound for a wave whose smallest scv/memory is >= t_l (each pod qualifies
 //              at most nq(t_l) cards, B_G is non-decreasing in q): the argmax K2's pruning;
 //            - a LOWER bound on every pod's best score for a wave whose largest scv/memory is
 //              <= t_l when every node of the block is feasible for every pod of the wave (the
 //              maximising node scores at least that for each of them): the block K1's seed.
+//            lv[0] (t_0 = 0: every card qualifies) bounds every pod: a run without levels prunes
+//            with it, and the hot mask ranks the blocks by it.
+// (Until the levels went from 32 to 64 the table also held ub[j], the bound for a pod with at most
+// j qualifying cards, and the block's K largest frees fmax[] to derive j: DESIGN.md §4.)
 // Built from the K2 summaries and the G table on the device (k_block_ub), again whenever the
 // static scores changed (k_set_static).
-constexpr uint32_t kKbLevels = 32;
-__host__ __device__ constexpr uint32_t kbub_fmax(int k) { return 2u * (uint32_t)k + 2u; }
-__host__ __device__ constexpr uint32_t kbub_lvl(int k) { return kbub_fmax(k) + (uint32_t)k; }
+// (64 levels, one per lane of the kernels' level search: the level bound is then as tight as
+// the J bound the argmax K2 used with 32 levels -- DESIGN.md §4)
+constexpr uint32_t kKbLevels = 64;
+__host__ __device__ constexpr uint32_t kbub_lvl(int) { return 0u; }
 __host__ __device__ constexpr uint32_t kbub_stride(int k) {
   return (4u * (kbub_lvl(k) + 2u * kKbLevels) + 15u) & ~15u;
+}
+// The level indices the block kernels use, from one compare per level (lane l holds levels[l];
+// n_levels <= 64).  The levels are strictly increasing (build_kb_levels), so the levels that meet
+// either test are a prefix, and the index the sequential search finds is their count
+// (tools/check_k2_bounds.cpp holds both against the loops).
+//   kb_level_lo: the largest l in 1..L-1 with levels[l] <= m_min, else 0 (K2's upper bound);
+//                le_mask bit l = levels[l] <= m_min
+//   kb_level_hi: the smallest l in 0..L-2 with levels[l] >= m_max, else L-1 (K1's seed);
+//                lt_mask bit l = levels[l] < m_max
+__host__ __device__ inline uint64_t kb_low_bits(uint32_t n) {  // bits 0..n-1 (n <= 64)
+  return n >= 64u ? ~0ull : (1ull << n) - 1ull;
+}
+__host__ __device__ inline uint32_t kb_level_lo(uint64_t le_mask, uint32_t n_levels) {
+  return (uint32_t)__builtin_popcountll(le_mask & kb_low_bits(n_levels) & ~1ull);
+}
+__host__ __device__ inline uint32_t kb_level_hi(uint64_t lt_mask, uint32_t n_levels) {
+  return (uint32_t)__builtin_popcountll(lt_mask & kb_low_bits(n_levels - 1u));
 }
 
 // K2 block bounds for waves whose maxima M are NOT the G maxima (N32 path, one reciprocal set;
@@ -177,16 +195,21 @@ __host__ __device__ constexpr uint32_t kbub_stride(int k) {
 //   ok            1: every real node of the block is one GPU model (kSumUni4), values, not ranks
 //   bw, ck, co, pw   the max over the block's nodes of the model values (shared_M is monotone)
 //   stat (f64)    the max static score
-//   ql[l]         the max over the nodes of nq(t_l) (kb_levels, as kbub's lv[])
-//   fl[l] (f64)   the max over the nodes of the sum of the frees >= t_l
-//   tl[l] (f64)   the max over the nodes of the sum of the totals of those cards
+//   ql[d]         the max over the nodes of nq(t_2d): kKbDecLevels = 32 levels, every other one
+//                 of kb_levels (a wave at kbub level l reads d = l / 2: t_2d <= t_l, still a
+//                 lower bound of its smallest scv/memory; 64 levels here doubled the table and
+//                 its rebuild, 39 -> 74 us an order, for nothing measured -- DESIGN.md §4)
+//   fl[d] (f64)   the max over the nodes of the sum of the frees >= t_2d
+//   tl[d] (f64)   the max over the nodes of the sum of the totals of those cards
 // so that static + nq shared + 3 r_free F + r_total T <= stat + ql shared(bw, ck, co, pw) +
-// 3 r_free fl + r_total tl for every pod whose smallest scv/memory is >= t_l.
+// 3 r_free fl + r_total tl for every pod whose smallest scv/memory is >= t_2d.
 enum KbDecWord { kDecOk = 0, kDecBw = 1, kDecCk = 2, kDecCo = 3, kDecPw = 4, kDecStat = 5, kDecQl = 7 };
-__host__ __device__ constexpr uint32_t kbdec_fl(uint32_t l) { return kDecQl + kKbLevels + 2u * l; }
-__host__ __device__ constexpr uint32_t kbdec_tl(uint32_t l) { return kDecQl + 3u * kKbLevels + 2u * l; }
+constexpr uint32_t kKbDecLevels = kKbLevels / 2u;
+__host__ __device__ constexpr uint32_t kbdec_level(uint32_t l) { return l >> 1; }  // of kbub level l
+__host__ __device__ constexpr uint32_t kbdec_fl(uint32_t d) { return kDecQl + kKbDecLevels + 2u * d; }
+__host__ __device__ constexpr uint32_t kbdec_tl(uint32_t d) { return kDecQl + 3u * kKbDecLevels + 2u * d; }
 __host__ __device__ constexpr uint32_t kbdec_stride() {
-  return (4u * (kDecQl + 5u * kKbLevels) + 15u) & ~15u;
+  return (4u * (kDecQl + 5u * kKbDecLevels) + 15u) & ~15u;
 }
 
 // Per-card GPU models of every node (N32 path), in the K2 summary's descending-free card order,
@@ -274,6 +297,22 @@ __host__ __device__ inline uint64_t window_bits(const uint64_t* words, uint32_t 
   if (n < 64u) bits &= (1ull << n) - 1ull;
   return bits;
 }
+
+// The block K1's wave bounds (k1_block_n32's set-up: the minima / maxima of the wave's pod
+// fields, a pure function of the batch), written once per pod wave by the cost probe that runs
+// before the block K1 of a private run (k1_probe) and read by each of the wave's chunk tasks in
+// place of some twenty wave-wide reductions.  One 64-byte record per wave of the sorted batch.
+struct alignas(16) K1WaveRec {
+  uint64_t num_min, num_max;
+  uint32_t mpm_min, mpm_max;  // m over the pods with the scv/memory label
+  uint32_t m_min, m_max, c_min, c_max;
+  uint32_t cpc_max, nc_min, nc_max;  // c and the need over the pods with the scv/clock label
+  uint32_t nm_min, nm_max;           // the need over the pods with the scv/memory label
+  uint32_t flags;                    // kK1Rec* | l_hi << 8 (kb_level_hi of m_max)
+};
+static_assert(sizeof(K1WaveRec) == 64, "K1WaveRec layout");
+constexpr uint32_t kK1RecAnyPm = 1u, kK1RecAllPm = 2u, kK1RecAnyPc = 4u, kK1RecAllPc = 8u,
+                   kK1RecCUni = 16u;
 
 // The block-grouped copies of the node summaries (private batch runs) that k_set_static keeps
 // current with the originals: inv[node] = its internal position.
@@ -410,6 +449,9 @@ struct PodParams {
   const uint32_t* lpt_order = nullptr;
   // the block K1's heaviest-first pod blocks (k1_probe + k_lpt_order; nullptr: launch order)
   const uint32_t* k1_order = nullptr;
+  // the wave bounds k1_probe left for this batch in a private run (yoda_run); nullptr -- every
+  // other entry point -- : the block K1 computes its own
+  const K1WaveRec* k1_rec = nullptr;
   // K2 pruning seeds [waves] u64 (zeroed with the block list before the block K1): a lower
   // bound on every live pod's best raw score under the G maxima, found by the block K1 on the
   // nodes every pod of the wave passes (nullptr: none); the snapshot's free levels kb_levels
