@@ -411,7 +411,12 @@ int yoda_topk_k(void);
  * yoda_shard_phase1_witness (yoda_topk_k() after yoda_shard_phase1). */
 int yoda_topk_k_capacity(void);
 /* Set the allocated memory (and CardNumber) of the listed nodes (GLOBAL ids; ids outside
- * this handle's shard are ignored) and refresh their static score on the device. */
+ * this handle's shard are ignored) and refresh their static score on the device.  An id may
+ * appear more than once in the list: its LAST entry wins, on the device and in the host copies
+ * alike (the earlier ones are dropped before anything is written).  count == 0 is a no-op.  An
+ * allocation above the node's total memory is accepted: its Allocate score is 0, as in the
+ * reference (algorithm.go:305-307).  YODA_ERR_RANGE (a static score beyond the fast paths'
+ * range) leaves the handle as it was before the call. */
 int yoda_set_node_state(yoda_t* h, uint32_t count, const uint32_t* nodes, const uint64_t* alloc,
                         const uint64_t* card_number);
 /* After yoda_shard_phase1 (or _phase1_witness) and the caller's reduction of its buffers

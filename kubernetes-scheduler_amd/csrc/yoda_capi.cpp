@@ -483,6 +483,7 @@ struct yoda_handle {
   uint32_t greedy_refreshes = 0;  // flags-0 mid-window list refreshes (last yoda_greedy)
   hipEvent_t upd_event = nullptr;
   bool upd_pending = false;
+  std::vector<uint32_t> upd_slot;  // yoda_set_node_state: a node's entry in the list (~0u: none)
   std::vector<uint32_t> h_pos;  // yoda_shard_topk: caller pod index -> sorted position
   bool topk_ready = false;      // the bitmask / reciprocals of that batch are still valid
   uint32_t greedy_windows = 0, greedy_fallbacks = 0;
@@ -4130,31 +4131,46 @@ int yoda_set_node_state(yoda_t* h, uint32_t count, const uint32_t* nodes, const 
     return fail(h, YODA_ERR_INVALID_ARG, "NULL node state array");
   try {
     HIP_TRY(h, hipSetDevice(h->device));
+    // One entry per node, the last of a repeated id: k_set_static runs one thread per entry,
+    // and two of them storing to one node's words would leave the device with either value
+    // while the host copies keep the last.  upd_slot[i] = node i's entry in this list.
+    if (h->upd_slot.size() != h->n_nodes) h->upd_slot.assign(h->n_nodes, ~0u);
     std::vector<uint32_t> loc;
-    std::vector<uint64_t> stat, val, cn;
+    std::vector<uint64_t> al, val, cn;
+    auto forget = [&] { for (uint32_t i : loc) h->upd_slot[i] = ~0u; };
     for (uint32_t t = 0; t < count; ++t) {
       if (nodes[t] < h->node_offset || nodes[t] - h->node_offset >= h->n_nodes) continue;
       const uint32_t i = nodes[t] - h->node_offset;
       bool z = false;
       const uint64_t s = static_score(h->h_free_sum[i], h->h_total_sum[i], alloc[t], &z);
-      if (!h->generic && s >= (1ull << 51))
+      if (!h->generic && s >= (1ull << 51)) {
+        forget();
         return fail(h, YODA_ERR_RANGE, "static score leaves the fast path; re-upload the nodes");
-      loc.push_back(i);
-      stat.push_back(s);
-      cn.push_back(card_number[t]);
+      }
       uint64_t bits = s;
       if (!h->generic) {
         const double d = (double)s;
         std::memcpy(&bits, &d, 8);
       }
-      val.push_back(bits);
+      uint32_t& slot = h->upd_slot[i];
+      if (slot == ~0u) {
+        slot = (uint32_t)loc.size();
+        loc.push_back(i);
+        al.push_back(alloc[t]);
+        val.push_back(bits);
+        cn.push_back(card_number[t]);
+      } else {
+        al[slot] = alloc[t];
+        val[slot] = bits;
+        cn[slot] = card_number[t];
+      }
     }
+    forget();
     // keep the host copies current (yoda_update_alloc / yoda_greedy start from them)
     const size_t stride = h->path == Path::N32 ? n32_stride(h->K) : node_stride(h->K);
-    for (size_t t = 0, ti = 0; t < count; ++t) {
-      if (nodes[t] < h->node_offset || nodes[t] - h->node_offset >= h->n_nodes) continue;
+    for (size_t ti = 0; ti < loc.size(); ++ti) {
       const uint32_t i = loc[ti];
-      h->h_alloc[i] = alloc[t];
+      h->h_alloc[i] = al[ti];
       h->h_card_number[i] = cn[ti];
       unsigned char* r = h->host_records.data() + (size_t)i * stride;
       std::memcpy(r, &val[ti], 8);       // header word 0: static score
@@ -4163,12 +4179,13 @@ int yoda_set_node_state(yoda_t* h, uint32_t count, const uint32_t* nodes, const 
         h->host_k2sum[sum_index(i, kS2Static, k2sum_stride(h->K))] = (uint32_t)val[ti];
         h->host_k2sum[sum_index(i, kS2Static + 1, k2sum_stride(h->K))] = (uint32_t)(val[ti] >> 32);
       }
-      ++ti;
     }
     return push_node_state(h, loc, val, cn);
   } catch (const std::bad_alloc&) {
+    h->upd_slot.clear();  // (rebuilt empty by the next call)
     return fail(h, YODA_ERR_INVALID_ARG, "host allocation failed");
   } catch (...) {
+    h->upd_slot.clear();
     return fail(h, YODA_ERR_INVALID_ARG, "unexpected exception");
   }
 }

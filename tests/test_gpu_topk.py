@@ -13,12 +13,9 @@ from yoda_amd.soa import MODE_SCV
 pytestmark = pytest.mark.gpu
 
 
-def _lists(nodes, pods, force_f64=False, alloc=None):
+def lists_of(y, pods):
+    """The lists of `pods` on handle `y` as it stands (its snapshot and node-state pushes)."""
     import torch
-    y = Yoda(0)
-    y.upload_nodes(nodes, force_f64=force_f64)
-    if alloc is not None:
-        y.update_alloc(alloc)
     y.upload_pods(pods)
     P = pods.n_pods
     dmax = torch.zeros(6 * P, dtype=torch.int64, device="cuda:0")
@@ -26,6 +23,15 @@ def _lists(nodes, pods, force_f64=False, alloc=None):
     y.shard_phase1(MODE_SCV, dmax.data_ptr(), dcnt.data_ptr())
     out = y.shard_topk(dmax.data_ptr(), dcnt.data_ptr())
     torch.cuda.synchronize()
+    return out
+
+
+def _lists(nodes, pods, force_f64=False, alloc=None):
+    y = Yoda(0)
+    y.upload_nodes(nodes, force_f64=force_f64)
+    if alloc is not None:
+        y.update_alloc(alloc)
+    out = lists_of(y, pods)
     path = y.path
     y.close()
     return out, path
