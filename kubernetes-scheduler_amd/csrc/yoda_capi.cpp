@@ -3020,7 +3020,8 @@ static int prepare_run(yoda_t* h, int mode, bool pad = false) {
   h->n_work = padded ? h->n_pad : h->n_pods;
   plan_chunks(h, mode, h->n_work, h->n_nodes);
   // a run on the block kernels (argmax, or the greedy windows' top-k) visits its pod blocks
-  // heaviest first (the weights: K1's PART nodes per pod block; YODA_LPT=0: launch order)
+  // heaviest first (a block's weight: its heaviest wave's PART nodes in K1; YODA_LPT=0: launch
+  // order)
   static const bool lpt_env = YODA_KNOB("YODA_LPT", 1) != 0;
   const uint32_t n_pb = (h->n_work + kBlock - 1) / kBlock;
   h->lpt_sorted = false;

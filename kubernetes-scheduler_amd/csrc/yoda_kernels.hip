@@ -1648,8 +1648,12 @@ __device__ __forceinline__ void store_rcp(int f, uint64_t mx, uint32_t n_pods, u
 }
 
 // The block K2's pod-block order, heaviest first (longest processing time first: a heavy
-// pod block that starts late sets the kernel's tail).  Weight = the pod block's PART nodes in
-// K1 (wts [n_waves], summed over the chunks by k1_block_n32; zeroed here for the next run).
+// pod block that starts late sets the kernel's tail).  A pod block is one workgroup of four
+// independent waves whose slots and LDS return when the slowest of them ends, so its weight is
+// its heaviest wave's, not the sum of the four: one heavy wave beside three light ones holds
+// the workgroup as long as four heavy ones do, and by the sum it started mid-launch (config 3:
+// K1 0.171 -> 0.151 ms).  A wave's weight = its PART nodes in K1 (wts [n_waves],
+// summed over the chunks by k1_block_n32; zeroed here for the next run), or k1_probe's count.
 // One workgroup: each pod block's rank = the blocks heavier than it (ties: lower index
 // first), counted over an LDS copy of the weights; n_pb <= kLptMax.
 constexpr uint32_t kLptMax = 4096;
@@ -1660,10 +1664,10 @@ __device__ void lpt_order_body(uint32_t* __restrict__ wts, uint32_t n_waves, uin
     if (4 * i + 4 <= n_waves) {  // the block's four waves in one 16-byte load
       const uint4 q = reinterpret_cast<const uint4*>(wts)[i];
       reinterpret_cast<uint4*>(wts)[i] = make_uint4(0u, 0u, 0u, 0u);
-      s = q.x + q.y + q.z + q.w;
+      s = max(max(q.x, q.y), max(q.z, q.w));
     } else {
       for (uint32_t v = 4 * i; v < n_waves; ++v) {
-        s += wts[v];
+        s = max(s, wts[v]);
         wts[v] = 0u;
       }
     }

@@ -4,7 +4,9 @@
 The kernels stamp each task's start / end with s_memrealtime (100 MHz) when YODA_K2_TRACE=<slots>
 is set (YODA_K1_TRACE=1: the K1 records instead of the K2).  Prints the task count, the duration
 distribution, the kernel's span, the mean concurrency (sum of task durations / span) and the
-durations split by per-pod work (npart = 0: the task's fixed cost plus its lane = block pass).
+durations split by per-pod work (npart = 0: the task's fixed cost plus its lane = block pass),
+the tasks in flight at each tenth of the span and, with --chunks, the co-termination loss of a
+static grid's four-wave workgroups and the 20 last-ending tasks.
 
     YODA_K2_TRACE=200000 [YODA_K1_TRACE=1] python tools/dbg/task_trace.py [--pods P] [--nodes N]
 """
@@ -25,6 +27,10 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--pods", type=int, default=None)
 ap.add_argument("--nodes", type=int, default=None)
 ap.add_argument("--variant", default=None, help="a synth.VARIANTS name instead of config 3")
+ap.add_argument("--chunks", type=int, default=None,
+                help="the launch's node chunks (slot = wave * chunks + chunk): adds the per-"
+                     "workgroup co-termination loss of a static (pod blocks, chunks) grid and "
+                     "the waves of the last-ending tasks")
 a = ap.parse_args()
 slots = int(os.environ.get("YODA_K2_TRACE", "0"))
 if slots <= 0:
@@ -104,9 +110,36 @@ if kern == "k2":  # task time by wave kind: G waves, decoupled-bound (non-G) wav
 st = (t[:, 0] - t[:, 0].min()) / 100.0
 out["starts_by_tenth"] = np.histogram(st, bins=10, range=(0, span))[0].tolist()
 out["ends_by_tenth"] = np.histogram((t[:, 1] - t[:, 0].min()) / 100.0, bins=10, range=(0, span))[0].tolist()
+# tasks in flight at the end of each tenth of the span
+out["in_flight_by_tenth"] = (np.cumsum(out["starts_by_tenth"]) -
+                             np.cumsum(out["ends_by_tenth"])).tolist()
+slot = np.nonzero(used)[0]
+if a.chunks:
+    wave, chunk = slot // a.chunks, slot % a.chunks
+    # A static grid's workgroup is waves 4k..4k+3 of one chunk: its LDS and wave slots return
+    # when the slowest of the four ends.  Slot time held against slot time used (a kernel of
+    # resident waves holds a slot per wave, not per workgroup: the figure does not apply to it).
+    key = (wave // 4) * a.chunks + chunk
+    order = np.argsort(key, kind="stable")
+    ks, ds = key[order], dur[order]
+    first = np.r_[True, ks[1:] != ks[:-1]]
+    gmax = np.maximum.reduceat(ds, np.nonzero(first)[0])
+    out["workgroup_cotermination"] = {"held_us": float(4.0 * gmax.sum()), "used_us": float(ds.sum()),
+                                      "held_over_used": float(4.0 * gmax.sum() / ds.sum())}
+    # the 20 last-ending tasks.  start_rank: the wave's place among the waves by first task start
+    # (the grid is pod-major, so this follows its pod block's rank in the heaviest-first order)
+    first_start = np.full(int(wave.max()) + 1, np.iinfo(np.int64).max)
+    np.minimum.at(first_start, wave, t[:, 0])
+    rank = np.empty(len(first_start), np.int64)
+    rank[np.argsort(first_start, kind="stable")] = np.arange(len(first_start))
+    last = np.argsort(t[:, 1])[-20:][::-1]
+    out["last_ending"] = [{"wave": int(wave[i]), "chunk": int(chunk[i]), "start_us": float(st[i]),
+                           "dur_us": float(dur[i]), "npart": int(npart[i]),
+                           "start_rank": int(rank[wave[i]])} for i in last]
+    out["longest_task_share_of_span"] = float(dur.max() / span) if span > 0 else None
 print(json.dumps(out), flush=True)
 # raw records for offline analysis (TASK_TRACE_DUMP=<path.npz>): slot (= wave * chunks + chunk),
 # start, end, npart, word 3
 dump = os.environ.get("TASK_TRACE_DUMP")
 if dump:
-    np.savez_compressed(dump, slot=np.nonzero(used)[0], rec=tr[used])
+    np.savez_compressed(dump, slot=slot, rec=tr[used])
