@@ -419,6 +419,32 @@ int yoda_topk_k_capacity(void);
  * range) leaves the handle as it was before the call. */
 int yoda_set_node_state(yoda_t* h, uint32_t count, const uint32_t* nodes, const uint64_t* alloc,
                         const uint64_t* card_number);
+/* Replace the dynamic SCV metrics of the listed nodes -- every card's FreeMemory and Health,
+ * and FreeMemorySum -- without re-uploading the snapshot.  nodes: GLOBAL ids (ids outside this
+ * handle's shard are ignored); card arrays [count * max_cards], slot j of entry t at
+ * [t * max_cards + j], slots >= the node's uploaded card_count ignored; an id listed more than
+ * once keeps its LAST entry; count == 0 is a no-op.  Card count, CardNumber, TotalMemory[Sum],
+ * clock, bandwidth, core, power are NOT changed by this call (CardNumber: yoda_set_node_state;
+ * the rest: yoda_upload_nodes).  max_cards: 1..16 and at least the uploaded card count of every
+ * listed node.  After it the handle answers every entry point as a handle freshly uploaded with
+ * the modified snapshot would.  YODA_ERR_RANGE: a value the uploaded snapshot's format cannot
+ * hold -- on the 32-bit record path a FreeMemory above 0xFFFFFFFE or, with memory ranks
+ * (yoda_memory_ranks), one that is not a card FreeMemory value of the uploaded snapshot; on the
+ * f64 path a FreeMemory above 2^44; on either a static score (new FreeMemorySum, current
+ * allocation) of 2^51 or more.  Everything is validated before anything is written: a failed
+ * call leaves the handle exactly as it was; re-upload. */
+int yoda_update_node_cards(yoda_t* h, uint32_t count, const uint32_t* nodes, uint32_t max_cards,
+                           const uint64_t* card_free_memory, const uint8_t* card_healthy,
+                           const uint64_t* free_memory_sum);
+/* Diagnostic (synchronizes).  digest[8]: a 64-bit hash per table over its words as the device
+ * holds them -- records, K1 summaries, K2 summaries, per-card model rows, K1 mixed tiles, block
+ * summaries, G table, G maxima + reciprocals (0 where the record path has none).  mismatch[4]:
+ * words of the block-grouped copies that differ from the base rows permuted by the node order;
+ * words of the upload-order block summaries that differ from k_bsum_build run now into a
+ * scratch buffer; the same for the block-grouped order; words of the host mirrors that differ
+ * from the device.  CardNumber bounds are tightened first if node-state pushes left them
+ * loose. */
+int yoda_snapshot_check(yoda_t* h, uint64_t* digest, uint32_t* mismatch);
 /* After yoda_shard_phase1 (or _phase1_witness) and the caller's reduction of its buffers
  * (d_maxima, d_counts as there).  k = the list depth of that phase 1, yoda_shard_topk_depth(h)
  * (yoda_topk_k() after yoda_shard_phase1, yoda_topk_k_capacity() after the witness phase 1);

@@ -27,6 +27,7 @@
 
 #include "../../include/yoda.h"
 #include "yoda_layout.h"
+#include "yoda_node_pack.h"
 
 namespace yoda {
 // launchers (yoda_kernels.hip)
@@ -136,6 +137,13 @@ hipError_t launch_set_static(unsigned char* nodes, uint32_t stride, const uint32
                              uint32_t sum2_stride, const PermCopy& pc, hipStream_t s);
 hipError_t launch_bsum_cn(const unsigned char* sum, uint32_t sum_stride, uint32_t n_nodes,
                           uint32_t* bsum, uint32_t bsw, hipStream_t s);
+hipError_t launch_set_cards(unsigned char* nodes, uint32_t stride, const uint32_t* node,
+                            const uint32_t* rows, uint32_t row_words, uint32_t count, int K,
+                            uint32_t* sum, uint32_t* sum2, uint32_t* mix, uint32_t* x1,
+                            const PermCopy& pc, hipStream_t s);
+hipError_t launch_bsum_build(int K, const uint32_t* sum, const uint32_t* sum2, const uint32_t* x1,
+                             const uint32_t* mix, uint32_t n_nodes, uint32_t* bsum,
+                             hipStream_t s);
 hipError_t launch_block_ub(int K, const uint32_t* sum2, const uint32_t* tab, uint32_t n_nodes,
                            uint32_t* out, const uint32_t* levels, hipStream_t s);
 hipError_t launch_block_dec(int K, const uint32_t* sum2, const uint32_t* mix, uint32_t n_nodes,
@@ -386,6 +394,8 @@ struct yoda_handle {
       pc.inv = perm_inv.as<uint32_t>();
       pc.sum = k1sum_p.as<unsigned char>();
       pc.sum2 = k2sum_p.as<unsigned char>();
+      pc.mix = kmix_p.as<uint32_t>();
+      pc.x1 = kx1_p.as<uint32_t>();
       pc.bsum_p = blksum_p.p ? blksum_p.as<uint32_t>() : nullptr;
     }
     pc.bsum = blksum.p && path == Path::N32 ? blksum.as<uint32_t>() : nullptr;
@@ -409,6 +419,13 @@ struct yoda_handle {
   // bound on any raw score of this snapshot whatever the allocated memory (Basic + the
   // largest Allocate 300 + Actual): the packed top-k keys need score < 2^(64 - index bits)
   uint64_t score_bound = ~0ull;
+  long double sb_cards = 0.0L;  // its card and Allocate terms; sb_actual: the largest Actual
+  uint64_t sb_actual = 0;
+  uint64_t h_gmax[6] = {1, 1, 1, 1, 1, 1};  // the G maxima on the device (gtab_aux; N32)
+  // yoda_update_node_cards / yoda_snapshot_check: the changed nodes' packed rows (host), the
+  // block summaries k_bsum_build writes for the self-check
+  std::vector<uint32_t> cu_rows;
+  DevBuf bsum_chk;
 
   // pods: one device blob of per-pod arrays (PodArray order), staged through pinned memory
   bool has_pods = false;
@@ -577,7 +594,7 @@ struct yoda_handle {
                      &ex1,       &rec,       &rec_all,   &cg_max,    &cg_cnt,    &cg_wit,    &cg_gather, &k3rec,     &k3all,
                      &one_out,   &b_cab,     &b_cls,     &b_part,
                      &counts_alt, &best_alt, &maxima_alt, &win_dev,
-                     &xcnt,      &xbest,     &xidx,      &xties,     &xlow};
+                     &xcnt,      &xbest,     &xidx,      &xties,     &xlow,      &bsum_chk};
     for (DevBuf* b : all) b->release();
     pod_stage.release();
     upd_stage.release();
@@ -1987,6 +2004,9 @@ int yoda_upload_nodes(yoda_t* h, const yoda_node_soa* nd, uint32_t node_offset, 
       const long double b = (long double)K * (800.0L + 100.0L * (long double)max_clock) + 300.0L +
                             (long double)max_actual;
       h->score_bound = b < 9.0e18L ? (uint64_t)b + 1u : ~0ull;
+      // (yoda_update_node_cards raises the Actual term with the nodes' new FreeMemorySum)
+      h->sb_cards = (long double)K * (800.0L + 100.0L * (long double)max_clock) + 300.0L;
+      h->sb_actual = max_actual;
     }
     // N32: every small card field in u32, every quotient exact in f64 (x, M < 2^32: 300 x + M
     // < 2^53) -- the block K2 keeps the small-field quotients in f32 while those fields are
@@ -2045,165 +2065,44 @@ int yoda_upload_nodes(yoda_t* h, const yoda_node_soa* nd, uint32_t node_offset, 
     const size_t xstride = x1_stride(K);
     std::vector<uint32_t> x1m(want_sum ? (size_t)std::max<uint32_t>(N, 1) * xstride / 4 : 0, 0);
     for (uint32_t i = 0; i < N; ++i) {
-      unsigned char* r = rec.data() + (size_t)i * stride;
-      uint32_t hm = 0;
-      for (uint32_t j = 0; j < nd->card_count[i]; ++j)
-        if (nd->card_healthy[(size_t)i * KS + j]) hm |= 1u << j;
-      NodeHdrG hd{};  // NodeHdrF has the same layout; static_score's bits set below
-      hd.card_number = nd->card_number[i];
-      hd.healthy_mask = hm;
-      hd.zero_total = zt[i];
+      // the node's rows, packed by the one per-node packer (yoda_node_pack.h)
+      const size_t a = (size_t)i * KS;
       const uint32_t cnt = nd->card_count[i];
-      hd.real_mask = cnt >= 32 ? 0xffffffffu : ((1u << cnt) - 1u);
-      bool uni = cnt > 0;
-      for (uint32_t j = 1; j < cnt; ++j) {
-        const size_t a = (size_t)i * KS, b = a + j;
-        uni = uni && nd->card_clock[b] == nd->card_clock[a] &&
-              nd->card_bandwidth[b] == nd->card_bandwidth[a] &&
-              nd->card_core[b] == nd->card_core[a] && nd->card_power[b] == nd->card_power[a];
-      }
-      bool uni_total = uni;
-      for (uint32_t j = 1; j < cnt; ++j)
-        uni_total = uni_total && nd->card_total_memory[(size_t)i * KS + j] ==
-                                     nd->card_total_memory[(size_t)i * KS];
-      hd.flags = 0u;
-      if (uni && !(flags & YODA_UPLOAD_NO_UNIFORM))
-        hd.flags = kNodeUniform4 | (uni_total ? kNodeUniformTotal : 0u);
-      n_one_model += (hd.flags & (kNodeUniform4 | kNodeUniformTotal)) ==
-                     (kNodeUniform4 | kNodeUniformTotal);
-      n_uni4 += (hd.flags & kNodeUniform4) != 0u;
-      if (path == Path::U64) {
-        hd.static_score = stat[i];
-      } else {
-        const double sd = (double)stat[i];
-        std::memcpy(&hd.static_score, &sd, 8);
-      }
-      std::memcpy(r, &hd, sizeof(hd));
+      uint32_t fc[YODA_MAX_CARDS], tc[YODA_MAX_CARDS];
+      if (path == Path::N32)
+        for (uint32_t j = 0; j < cnt; ++j) {
+          fc[j] = code_f(nd->card_free_memory[a + j]);
+          tc[j] = code_t(nd->card_total_memory[a + j]);
+        }
+      NodePackIn in;
+      in.cnt = cnt;
+      in.card_number = nd->card_number[i];
+      in.stat = stat[i];
+      in.zero_total = zt[i] != 0;
+      in.no_uniform = (flags & YODA_UPLOAD_NO_UNIFORM) != 0u;
+      in.free_memory = nd->card_free_memory + a;
+      in.total_memory = nd->card_total_memory + a;
+      in.clock = nd->card_clock + a;
+      in.bandwidth = nd->card_bandwidth + a;
+      in.core = nd->card_core + a;
+      in.power = nd->card_power + a;
+      in.healthy = nd->card_healthy + a;
+      in.fcode = fc;
+      in.tcode = tc;
+      NodePackOut out;
+      out.zeroed = true;  // (the vectors above: value-initialised, each row packed once)
+      out.rec = rec.data() + (size_t)i * stride;
       if (want_sum) {
-        uint32_t* s = sum.data() + (size_t)i * sstride / 4;
-        const size_t a = (size_t)i * KS;
-        s[kSumCnLo] = (uint32_t)hd.card_number;
-        s[kSumCnHi] = (uint32_t)(hd.card_number >> 32);
-        s[kSumMeta] = ((hd.flags & kNodeUniform4) ? kSumUni4 : 0u) |
-                      ((hd.flags & kNodeUniformTotal) ? kSumUniTotal : 0u) |
-                      (zt[i] ? kSumZeroTotal : 0u) | ((uint32_t)__builtin_popcount(hm) << 8);
-        if (cnt > 0) {  // the model values of card 0 (all cards under kSumUni4)
-          s[kSumClock] = (uint32_t)nd->card_clock[a];
-          s[kSumTotal] = code_t(nd->card_total_memory[a]);
-          s[kSumBw] = (uint32_t)nd->card_bandwidth[a];
-          s[kSumCore] = (uint32_t)nd->card_core[a];
-          s[kSumPower] = (uint32_t)nd->card_power[a];
-        }
-        uint32_t mrf1 = 0, nhf = 0;
-        uint32_t hfs[YODA_MAX_CARDS];
-        for (uint32_t j = 0; j < cnt; ++j) {  // N32: free <= 0xFFFFFFFE, so free + 1 fits
-          const uint32_t f1 = code_f(nd->card_free_memory[a + j]) + 1u;
-          mrf1 = std::max(mrf1, f1);
-          if (nd->card_healthy[a + j]) hfs[nhf++] = f1;
-        }
-        std::sort(hfs, hfs + nhf, [](uint32_t x, uint32_t y) { return x > y; });
-        s[kSumMrf1] = mrf1;
-        for (uint32_t j = 0; j < nhf; ++j) s[kSumHfs + j] = hfs[j];
-        // K2 summary: real cards in descending free order (stable: ties keep card order)
-        uint32_t* s2 = sum2.data() + (size_t)i * s2stride / 4;
-        std::memcpy(s2 + kS2Static, &hd.static_score, 8);  // f64 bits (set above)
-        s2[kS2Clock] = s[kSumClock];
-        s2[kS2Meta] = ((hd.flags & kNodeUniform4) ? kSumUni4 : 0u) | (cnt << 8);
-        s2[kS2Bw] = s[kSumBw];
-        s2[kS2Core] = s[kSumCore];
-        s2[kS2Power] = s[kSumPower];
-        uint32_t ord[YODA_MAX_CARDS];
-        for (uint32_t j = 0; j < cnt; ++j) ord[j] = j;
-        std::stable_sort(ord, ord + cnt, [&](uint32_t x, uint32_t y) {
-          return nd->card_free_memory[a + x] > nd->card_free_memory[a + y];
-        });
-        uint32_t* mx = mix.data() + (size_t)i * mstride / 4;
-        uint32_t minclk = 0xffffffffu, hmf = 0;
-        for (uint32_t j = 0; j < cnt; ++j) {
-          const size_t b = a + ord[j];
-          s2[kS2Fs + j] = code_f(nd->card_free_memory[b]);
-          s2[kS2Fs + K + j] = code_t(nd->card_total_memory[b]);
-          // the per-card models in the same order (nodes without kSumUni4 read them)
-          mx[mix_word(kMixCk, (int)j, K)] = (uint32_t)nd->card_clock[b];
-          mx[mix_word(kMixBw, (int)j, K)] = (uint32_t)nd->card_bandwidth[b];
-          mx[mix_word(kMixCo, (int)j, K)] = (uint32_t)nd->card_core[b];
-          mx[mix_word(kMixPw, (int)j, K)] = (uint32_t)nd->card_power[b];
-          if (nd->card_healthy[b]) hmf |= 1u << j;
-          minclk = std::min(minclk, (uint32_t)nd->card_clock[b]);
-        }
-        mx[mix_hm(K)] = hmf;
-        s2[kS2MinClk] = minclk;
-        // K1 tile (K1MixWord): prefix maxima per 16-bit half, their change bits, the cards
-        // packed, the healthy-card counts per distinct clock
-        uint32_t* x = x1m.data() + (size_t)i * xstride / 4;
-        uint32_t pa = 0, pb = 0, pt = 0, chg = 0, nch = 0;
-        auto hmax = [](uint32_t u, uint32_t v) {
-          return std::max(u & 0xffffu, v & 0xffffu) | (std::max(u >> 16, v >> 16) << 16);
-        };
-        for (uint32_t j = 0; j < cnt; ++j) {
-          const size_t b = a + ord[j];
-          const uint32_t ca = (uint32_t)nd->card_clock[b] | ((uint32_t)nd->card_bandwidth[b] << 16);
-          const uint32_t cb = (uint32_t)nd->card_core[b] | ((uint32_t)nd->card_power[b] << 16);
-          const uint32_t na = hmax(pa, ca), nb2 = hmax(pb, cb);
-          const uint32_t nt = std::max(pt, s2[kS2Fs + K + j]);
-          if (j == 0 || na != pa || nb2 != pb || nt != pt) chg |= 1u << (j + 1);
-          pa = na;
-          pb = nb2;
-          pt = nt;
-          x[x1_pm((int)j, 0)] = pa;
-          x[x1_pm((int)j, 1)] = pb;
-          x[x1_pm((int)j, 2)] = pt;
-          x[x1_cd((int)j, 0, K)] = ca;
-          x[x1_cd((int)j, 1, K)] = cb;
-          if (nd->card_healthy[b]) {
-            const uint32_t ck = (uint32_t)nd->card_clock[b];
-            uint32_t e = 0;
-            while (e < nch && (x[kX1Ch + e] & 0xffffu) != ck) ++e;
-            if (e == nch) {
-              if (nch == 4) {
-                chg |= kX1ChgMany;
-                continue;
-              }
-              x[kX1Ch + nch++] = ck;
-            }
-            x[kX1Ch + e] += 1u << 16;
-          }
-        }
-        x[kX1Chg] = chg;
-        uint32_t* cr = clk_rng.data() + 4 * (size_t)i;
-        cr[0] = cr[2] = 0xffffffffu;
-        cr[1] = cr[3] = 0u;
-        for (uint32_t j = 0; j < cnt; ++j) {
-          const uint32_t ck = (uint32_t)nd->card_clock[a + j];
-          cr[0] = std::min(cr[0], ck);
-          cr[1] = std::max(cr[1], ck);
-          if (nd->card_healthy[a + j]) {
-            cr[2] = std::min(cr[2], ck);
-            cr[3] = std::max(cr[3], ck);
-          }
-        }
+        out.sum = sum.data() + (size_t)i * sstride / 4;
+        out.sum2 = sum2.data() + (size_t)i * s2stride / 4;
+        out.mix = mix.data() + (size_t)i * mstride / 4;
+        out.x1 = x1m.data() + (size_t)i * xstride / 4;
+        out.clk_rng = clk_rng.data() + 4 * (size_t)i;
       }
-      for (uint32_t j = 0; j < nd->card_count[i]; ++j) {
-        const size_t k = (size_t)i * KS + j;
-        const uint64_t v[6] = {nd->card_free_memory[k], nd->card_clock[k],
-                               nd->card_total_memory[k], nd->card_bandwidth[k],
-                               nd->card_core[k], nd->card_power[k]};  // CardField order
-        if (path == Path::N32) {
-          uint32_t* u = reinterpret_cast<uint32_t*>(r + 32);
-          for (int f = 0; f < kCardFields; ++f) u[f * K + j] = (uint32_t)v[f];
-          u[kFree * K + j] = code_f(v[kFree]);
-          u[kTotal * K + j] = code_t(v[kTotal]);
-          double* d = reinterpret_cast<double*>(r + n32_f64_off(0, K));
-          d[kF64Free * K + j] = (double)v[kFree];
-          d[kF64Total * K + j] = (double)v[kTotal];
-        } else if (path == Path::F64) {
-          double* d = reinterpret_cast<double*>(r + 32);
-          for (int f = 0; f < kCardFields; ++f) d[f * K + j] = (double)v[f];
-        } else {
-          uint64_t* u = reinterpret_cast<uint64_t*>(r + 32);
-          for (int f = 0; f < kCardFields; ++f) u[f * K + j] = v[f];
-        }
-      }
+      const uint32_t nf = pack_node(path, K, in, out);
+      n_one_model += (nf & (kNodeUniform4 | kNodeUniformTotal)) ==
+                     (kNodeUniform4 | kNodeUniformTotal);
+      n_uni4 += (nf & kNodeUniform4) != 0u;
     }
     HIP_TRY(h, h->nodes.ensure(rec.size()));
     HIP_TRY(h, hipMemcpyAsync(h->nodes.p, rec.data(), rec.size(), hipMemcpyHostToDevice,
@@ -2543,6 +2442,7 @@ int yoda_upload_nodes(yoda_t* h, const yoda_node_soa* nd, uint32_t node_offset, 
           gmax[kMaxTotal] = std::max(gmax[kMaxTotal], nd->card_total_memory[k]);
         }
       HIP_TRY(h, h->gtab.ensure(sum_words(std::max<uint32_t>(N, 1), gtab_stride(K)) * 4));
+      std::memcpy(h->h_gmax, gmax, sizeof(gmax));
       HIP_TRY(h, h->gtab_aux.ensure(kGTabAuxBytes));
       HIP_TRY(h, hipMemcpyAsync(h->gtab_aux.p, gmax, sizeof(gmax), hipMemcpyHostToDevice,
                                 h->stream));
@@ -4187,6 +4087,340 @@ int yoda_set_node_state(yoda_t* h, uint32_t count, const uint32_t* nodes, const 
     return fail(h, YODA_ERR_INVALID_ARG, "host allocation failed");
   } catch (...) {
     h->upd_slot.clear();
+    return fail(h, YODA_ERR_INVALID_ARG, "unexpected exception");
+  }
+}
+
+namespace {
+
+// One card of a host record (the formats of yoda_layout.h), back as the uint64 it was uploaded.
+uint64_t rec_field(const yoda_t* h, const unsigned char* r, int field, uint32_t j) {
+  const int K = h->K;
+  if (h->path == Path::N32) {
+    if (field == kFree || field == kTotal) {
+      double d;
+      std::memcpy(&d, r + n32_f64_off(field == kFree ? kF64Free : kF64Total, K) + 8u * j, 8);
+      return (uint64_t)d;
+    }
+    uint32_t u;
+    std::memcpy(&u, r + n32_u32_off(field, K) + 4u * j, 4);
+    return u;
+  }
+  if (h->path == Path::F64) {
+    double d;
+    std::memcpy(&d, r + 32 + 8u * ((size_t)field * K + j), 8);
+    return (uint64_t)d;
+  }
+  uint64_t u;
+  std::memcpy(&u, r + 32 + 8u * ((size_t)field * K + j), 8);
+  return u;
+}
+
+// The G table of both orders from the current K2 summaries and the maxima in gtab_aux.
+int relaunch_gtables(yoda_t* h) {
+  uint32_t* rcp_dev = reinterpret_cast<uint32_t*>(h->gtab_aux.as<unsigned char>() + 48);
+  const MemTab mt = h->mem_ranks ? h->mt : MemTab{};
+  HIP_TRY(h, launch_gtable(h->K, h->k2sum.as<uint32_t>(), h->kmix.as<uint32_t>(), h->n_nodes,
+                           h->gtab_aux.as<uint64_t>(), h->gtab.as<uint32_t>(), rcp_dev, mt,
+                           h->stream));
+  if (h->perm_on)
+    HIP_TRY(h, launch_gtable(h->K, h->k2sum_p.as<uint32_t>(), h->kmix_p.as<uint32_t>(),
+                             h->n_nodes, h->gtab_aux.as<uint64_t>(), h->gtab_p.as<uint32_t>(),
+                             rcp_dev, mt, h->stream));
+  return YODA_OK;
+}
+
+// The block summaries of both orders from the device summaries (k_bsum_build).
+int rebuild_block_sums(yoda_t* h) {
+  HIP_TRY(h, launch_bsum_build(h->K, h->k1sum.as<uint32_t>(), h->k2sum.as<uint32_t>(),
+                               h->kx1.as<uint32_t>(), h->kmix.as<uint32_t>(), h->n_nodes,
+                               h->blksum.as<uint32_t>(), h->stream));
+  if (h->perm_on)
+    HIP_TRY(h, launch_bsum_build(h->K, h->k1sum_p.as<uint32_t>(), h->k2sum_p.as<uint32_t>(),
+                                 h->kx1_p.as<uint32_t>(), h->kmix_p.as<uint32_t>(), h->n_nodes,
+                                 h->blksum_p.as<uint32_t>(), h->stream));
+  h->blksum_loose = false;
+  return YODA_OK;
+}
+
+}  // namespace
+
+int yoda_update_node_cards(yoda_t* h, uint32_t count, const uint32_t* nodes, uint32_t max_cards,
+                           const uint64_t* card_free_memory, const uint8_t* card_healthy,
+                           const uint64_t* free_memory_sum) {
+  if (!h) return YODA_ERR_INVALID_ARG;
+  if (!h->has_nodes) return fail(h, YODA_ERR_NO_NODES, "no node snapshot uploaded");
+  if (count == 0) return YODA_OK;
+  if (!nodes || !card_free_memory || !card_healthy || !free_memory_sum)
+    return fail(h, YODA_ERR_INVALID_ARG, "NULL card update array");
+  if (max_cards < 1 || max_cards > YODA_MAX_CARDS)
+    return fail(h, YODA_ERR_INVALID_ARG, "max_cards must be in 1..16");
+  try {
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int K = h->K;
+    const bool n32 = h->path == Path::N32;
+    const size_t stride = n32 ? n32_stride(K) : node_stride(K);
+    const uint32_t RW = (uint32_t)(stride / 4), SW = k1sum_stride(K) / 4u,
+                   S2W = k2sum_stride(K) / 4u, MW = mix_stride(K) / 4u, XW = x1_stride(K) / 4u;
+    const uint32_t row_words = RW + (n32 ? SW + S2W + MW + XW : 0u);
+    // one entry per node, the last of a repeated id (the upd_slot pattern of yoda_set_node_state)
+    if (h->upd_slot.size() != h->n_nodes) h->upd_slot.assign(h->n_nodes, ~0u);
+    std::vector<uint32_t> loc, ent;
+    auto forget = [&] { for (uint32_t i : loc) h->upd_slot[i] = ~0u; };
+    for (uint32_t t = 0; t < count; ++t) {
+      if (nodes[t] < h->node_offset || nodes[t] - h->node_offset >= h->n_nodes) continue;
+      const uint32_t i = nodes[t] - h->node_offset;
+      uint32_t& slot = h->upd_slot[i];
+      if (slot == ~0u) {
+        slot = (uint32_t)loc.size();
+        loc.push_back(i);
+        ent.push_back(t);
+      } else {
+        ent[slot] = t;
+      }
+    }
+    forget();
+    const uint32_t cnt = (uint32_t)loc.size();
+    if (cnt == 0) return YODA_OK;
+    // Validate and pack every row into host scratch; nothing of the handle is written before
+    // the whole list has passed.
+    h->cu_rows.assign((size_t)cnt * row_words, 0u);
+    std::vector<uint64_t> new_stat(cnt);
+    uint64_t new_actual = h->sb_actual, new_free_max = 0;
+    bool held_max = false;  // a changed node held the G maximum of FreeMemory
+    for (uint32_t ti = 0; ti < cnt; ++ti) {
+      const uint32_t i = loc[ti], t = ent[ti];
+      const unsigned char* r = h->host_records.data() + (size_t)i * stride;
+      NodeHdrG hd;
+      std::memcpy(&hd, r, sizeof(hd));
+      const uint32_t nc = (uint32_t)__builtin_popcount(hd.real_mask);
+      if (nc > max_cards)
+        return fail(h, YODA_ERR_INVALID_ARG, "max_cards below a listed node's card count");
+      uint64_t fr[YODA_MAX_CARDS], tot[YODA_MAX_CARDS], ck[YODA_MAX_CARDS], bw[YODA_MAX_CARDS],
+          co[YODA_MAX_CARDS], pw[YODA_MAX_CARDS];
+      uint8_t hl[YODA_MAX_CARDS];
+      uint32_t fc[YODA_MAX_CARDS], tc[YODA_MAX_CARDS];
+      for (uint32_t j = 0; j < nc; ++j) {
+        const uint64_t f = card_free_memory[(size_t)t * max_cards + j];
+        fr[j] = f;
+        hl[j] = card_healthy[(size_t)t * max_cards + j] ? 1 : 0;
+        tot[j] = rec_field(h, r, kTotal, j);
+        ck[j] = rec_field(h, r, kClock, j);
+        bw[j] = rec_field(h, r, kBandwidth, j);
+        co[j] = rec_field(h, r, kCore, j);
+        pw[j] = rec_field(h, r, kPower, j);
+        if (n32) {
+          std::memcpy(&tc[j], r + n32_u32_off(kTotal, K) + 4u * j, 4);
+          if (h->mem_ranks) {
+            const auto it = std::lower_bound(h->h_frees.begin(), h->h_frees.end(), f);
+            if (it == h->h_frees.end() || *it != f)
+              return fail(h, YODA_ERR_RANGE,
+                          "FreeMemory value outside the snapshot's rank table; re-upload the nodes");
+            fc[j] = 2u + (uint32_t)(it - h->h_frees.begin());
+          } else {
+            if (f > kN32FieldMax)
+              return fail(h, YODA_ERR_RANGE, "FreeMemory leaves the 32-bit path; re-upload the nodes");
+            fc[j] = (uint32_t)f;
+          }
+        } else if (h->path == Path::F64 && f > kFastFieldMax) {
+          return fail(h, YODA_ERR_RANGE, "FreeMemory leaves the fast path; re-upload the nodes");
+        }
+        new_free_max = std::max(new_free_max, f);
+        if (n32 && std::max<uint64_t>(rec_field(h, r, kFree, j), 1) == h->h_gmax[kMaxFree])
+          held_max = true;
+      }
+      bool z = false;
+      const uint64_t s = static_score(free_memory_sum[t], h->h_total_sum[i], h->h_alloc[i], &z);
+      if (!h->generic && s >= (1ull << 51))
+        return fail(h, YODA_ERR_RANGE, "static score leaves the fast path; re-upload the nodes");
+      new_stat[ti] = s;
+      if (h->h_total_sum[i] != 0)
+        new_actual = std::max(new_actual, free_memory_sum[t] * 100u / h->h_total_sum[i] * 2u);
+      NodePackIn in;
+      in.cnt = nc;
+      in.card_number = h->h_card_number[i];
+      in.stat = s;
+      in.zero_total = z;
+      in.no_uniform = !(hd.flags & kNodeUniform4);  // (as uploaded: the card models are the same)
+      in.free_memory = fr;
+      in.total_memory = tot;
+      in.clock = ck;
+      in.bandwidth = bw;
+      in.core = co;
+      in.power = pw;
+      in.healthy = hl;
+      in.fcode = fc;
+      in.tcode = tc;
+      uint32_t* row = h->cu_rows.data() + (size_t)ti * row_words;
+      NodePackOut out;
+      out.rec = reinterpret_cast<unsigned char*>(row);
+      if (n32) {
+        out.sum = row + RW;
+        out.sum2 = out.sum + SW;
+        out.mix = out.sum2 + S2W;
+        out.x1 = out.mix + MW;
+      }
+      pack_node(h->path, K, in, out);
+    }
+    // ---- the list passed: stage the rows, then the host copies, then the device ----
+    const size_t o_rows = ((size_t)cnt * 4 + 15) / 16 * 16;
+    const size_t bytes = o_rows + (size_t)cnt * row_words * 4;
+    if (h->upd_pending) HIP_TRY(h, hipEventSynchronize(h->upd_event));
+    HIP_TRY(h, h->upd_stage.ensure(bytes));
+    HIP_TRY(h, h->upd_node.ensure(bytes));
+    unsigned char* st = static_cast<unsigned char*>(h->upd_stage.p);
+    std::memcpy(st, loc.data(), (size_t)cnt * 4);
+    std::memcpy(st + o_rows, h->cu_rows.data(), (size_t)cnt * row_words * 4);
+    for (uint32_t ti = 0; ti < cnt; ++ti) {
+      const uint32_t i = loc[ti], t = ent[ti];
+      const uint32_t* row = h->cu_rows.data() + (size_t)ti * row_words;
+      std::memcpy(h->host_records.data() + (size_t)i * stride, row, stride);
+      if (n32)
+        for (uint32_t w = 0; w < S2W; ++w)
+          h->host_k2sum[sum_index(i, w, k2sum_stride(K))] = row[RW + SW + w];
+      h->h_free_sum[i] = free_memory_sum[t];
+    }
+    h->ran = false;
+    h->phase1_done = false;
+    h->topk_ready = false;
+    if (new_actual > h->sb_actual) {  // the score bound may only grow
+      h->sb_actual = new_actual;
+      const long double b = h->sb_cards + (long double)new_actual;
+      h->score_bound =
+          std::max<uint64_t>(h->score_bound, b < 9.0e18L ? (uint64_t)b + 1u : ~(uint64_t)0);
+    }
+    HIP_TRY(h, hipMemcpyAsync(h->upd_node.p, st, bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipEventRecord(h->upd_event, h->stream));
+    h->upd_pending = true;
+    unsigned char* d = h->upd_node.as<unsigned char>();
+    HIP_TRY(h, launch_set_cards(h->nodes.as<unsigned char>(), (uint32_t)stride,
+                                reinterpret_cast<const uint32_t*>(d),
+                                reinterpret_cast<const uint32_t*>(d + o_rows), row_words, cnt, K,
+                                n32 ? h->k1sum.as<uint32_t>() : nullptr, h->k2sum.as<uint32_t>(),
+                                h->kmix.as<uint32_t>(), h->kx1.as<uint32_t>(), h->perm_copy(),
+                                h->stream));
+    if (!n32) return YODA_OK;
+    // the block summaries of both orders: the old ones are wrong now, not merely loose
+    int rc = rebuild_block_sums(h);
+    if (rc) return rc;
+    // The G maximum of FreeMemory, exact: it rises with a larger free; when a changed node held
+    // it, recomputed from the host K2 summaries (word kS2Fs + 0: each node's largest free).
+    uint64_t gfree = std::max(h->h_gmax[kMaxFree], std::max<uint64_t>(new_free_max, 1));
+    if (held_max) {
+      gfree = 1;
+      const uint32_t S2 = k2sum_stride(K);
+      for (uint32_t n = 0; n < h->n_nodes; ++n) {
+        const uint32_t c = h->host_k2sum[sum_index(n, kS2Fs, S2)];
+        uint64_t v = c;
+        if (h->mem_ranks) v = c >= 2u && c - 2u < h->h_frees.size() ? h->h_frees[c - 2u] : 0;
+        gfree = std::max(gfree, v);
+      }
+    }
+    const bool g_moved = gfree != h->h_gmax[kMaxFree];
+    if (g_moved) {
+      h->h_gmax[kMaxFree] = gfree;
+      HIP_TRY(h, hipMemcpyAsync(h->gtab_aux.p, h->h_gmax, sizeof(h->h_gmax),
+                                hipMemcpyHostToDevice, h->stream));
+    }
+    if ((rc = relaunch_gtables(h))) return rc;
+    h->kbub_dirty = true;  // the K2 block bounds: rebuilt before their next reader
+    h->kbub_loose = false;
+    if (g_moved && h->g.tab) {  // the reciprocals of the new maxima, as the upload reads them
+      uint32_t g_rcp[10] = {};
+      HIP_TRY(h, hipMemcpyAsync(g_rcp, h->gtab_aux.as<unsigned char>() + 48, sizeof(g_rcp),
+                                hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(h, hipStreamSynchronize(h->stream));
+      std::memcpy(&h->g.r_bw, &g_rcp[0], 8);
+      std::memcpy(&h->g.r_core, &g_rcp[2], 8);
+      std::memcpy(&h->g.r_pow, &g_rcp[4], 8);
+      std::memcpy(&h->g.r_free, &g_rcp[6], 8);
+      std::memcpy(&h->g.r_tot, &g_rcp[8], 8);
+    }
+    return YODA_OK;
+  } catch (const std::bad_alloc&) {
+    h->upd_slot.clear();
+    return fail(h, YODA_ERR_INVALID_ARG, "host allocation failed");
+  } catch (...) {
+    h->upd_slot.clear();
+    return fail(h, YODA_ERR_INVALID_ARG, "unexpected exception");
+  }
+}
+
+int yoda_snapshot_check(yoda_t* h, uint64_t* digest, uint32_t* mismatch) {
+  if (!h) return YODA_ERR_INVALID_ARG;
+  if (!h->has_nodes) return fail(h, YODA_ERR_NO_NODES, "no node snapshot uploaded");
+  if (!digest || !mismatch) return fail(h, YODA_ERR_INVALID_ARG, "NULL buffer");
+  try {
+    HIP_TRY(h, hipSetDevice(h->device));
+    const uint32_t N = h->n_nodes;
+    const int K = h->K;
+    const bool n32 = h->path == Path::N32;
+    for (int k = 0; k < 8; ++k) digest[k] = 0;
+    for (int k = 0; k < 4; ++k) mismatch[k] = 0;
+    if (n32 && h->blksum_loose) HIP_TRY(h, tighten_block_sums(h));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    auto hash = [](const std::vector<uint32_t>& v) {
+      uint64_t x = 0xcbf29ce484222325ull;
+      for (uint32_t w : v) x = (x ^ w) * 0x100000001b3ull;
+      return x;
+    };
+    auto fetch = [&](const DevBuf& b, size_t words, std::vector<uint32_t>& out) -> int {
+      out.assign(words, 0u);
+      if (words) HIP_TRY(h, hipMemcpy(out.data(), b.p, words * 4, hipMemcpyDeviceToHost));
+      return YODA_OK;
+    };
+    int rc;
+    const size_t stride = n32 ? n32_stride(K) : node_stride(K);
+    std::vector<uint32_t> rec;
+    if ((rc = fetch(h->nodes, (size_t)N * stride / 4, rec))) return rc;
+    digest[0] = hash(rec);
+    for (size_t w = 0; w < rec.size(); ++w) {
+      uint32_t hw;
+      std::memcpy(&hw, h->host_records.data() + 4 * w, 4);
+      mismatch[3] += hw != rec[w];
+    }
+    if (!n32 || N == 0) return YODA_OK;
+    const uint32_t strides[5] = {k1sum_stride(K), k2sum_stride(K), mix_stride(K), x1_stride(K),
+                                 gtab_stride(K)};
+    const DevBuf* base[5] = {&h->k1sum, &h->k2sum, &h->kmix, &h->kx1, &h->gtab};
+    const DevBuf* copy[5] = {&h->k1sum_p, &h->k2sum_p, &h->kmix_p, &h->kx1_p, &h->gtab_p};
+    const int dig[5] = {1, 2, 3, 4, 6};
+    std::vector<uint32_t> ids, a, b;
+    if (h->perm_on && (rc = fetch(h->perm_ids, N, ids))) return rc;
+    for (int k = 0; k < 5; ++k) {
+      if ((rc = fetch(*base[k], sum_words(N, strides[k]), a))) return rc;
+      digest[dig[k]] = hash(a);
+      if (k == 1)
+        for (size_t w = 0; w < a.size() && w < h->host_k2sum.size(); ++w)
+          mismatch[3] += a[w] != h->host_k2sum[w];
+      if (!h->perm_on) continue;
+      if ((rc = fetch(*copy[k], sum_words(N, strides[k]), b))) return rc;
+      for (uint32_t q = 0; q < N; ++q)
+        for (uint32_t w = 0; w < strides[k] / 4u; ++w)
+          mismatch[0] += b[sum_index(q, w, strides[k])] != a[sum_index(ids[q], w, strides[k])];
+    }
+    // the block summaries of both orders against k_bsum_build run now
+    const size_t bw = sum_words((N + 63) / 64, bsum_stride(K));
+    HIP_TRY(h, h->bsum_chk.ensure(bw * 4));
+    for (int o = 0; o < (h->perm_on ? 2 : 1); ++o) {
+      HIP_TRY(h, hipMemsetAsync(h->bsum_chk.p, 0, bw * 4, h->stream));
+      HIP_TRY(h, launch_bsum_build(K, (o ? h->k1sum_p : h->k1sum).as<uint32_t>(),
+                                   (o ? h->k2sum_p : h->k2sum).as<uint32_t>(),
+                                   (o ? h->kx1_p : h->kx1).as<uint32_t>(),
+                                   (o ? h->kmix_p : h->kmix).as<uint32_t>(), N,
+                                   h->bsum_chk.as<uint32_t>(), h->stream));
+      HIP_TRY(h, hipStreamSynchronize(h->stream));
+      if ((rc = fetch(o ? h->blksum_p : h->blksum, bw, a))) return rc;
+      if ((rc = fetch(h->bsum_chk, bw, b))) return rc;
+      if (o == 0) digest[5] = hash(a);
+      for (size_t w = 0; w < bw; ++w) mismatch[1 + o] += a[w] != b[w];
+    }
+    if ((rc = fetch(h->gtab_aux, kGTabAuxBytes / 4, a))) return rc;
+    digest[7] = hash(a);
+    return YODA_OK;
+  } catch (const std::bad_alloc&) {
+    return fail(h, YODA_ERR_INVALID_ARG, "host allocation failed");
+  } catch (...) {
     return fail(h, YODA_ERR_INVALID_ARG, "unexpected exception");
   }
 }

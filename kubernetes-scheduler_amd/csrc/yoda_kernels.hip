@@ -5468,6 +5468,226 @@ hipError_t launch_set_static(unsigned char* nodes, uint32_t stride, const uint32
   return hipGetLastError();
 }
 
+// Sparse card-metric update (yoda_update_node_cards): the packed rows of a few nodes (the host's
+// pack_node, yoda_node_pack.h) scattered over the node records, the tiled K1 / K2 summaries, the
+// per-card model rows and the K1 mixed tiles, and the block-grouped copies of those four at the
+// node's internal position.  One thread per changed node; a row in `rows` is the record
+// (stride bytes) followed, when the snapshot has summaries (sum != nullptr), by the K1 summary,
+// the K2 summary, the model row and the K1 tile, each node-major.  Each node is listed once.
+__global__ __launch_bounds__(kBlock) void k_set_cards(unsigned char* __restrict__ nodes,
+                                                      uint32_t stride,
+                                                      const uint32_t* __restrict__ node,
+                                                      const uint32_t* __restrict__ rows,
+                                                      uint32_t row_words, uint32_t count,
+                                                      uint32_t K, uint32_t* __restrict__ sum,
+                                                      uint32_t* __restrict__ sum2,
+                                                      uint32_t* __restrict__ mix,
+                                                      uint32_t* __restrict__ x1, PermCopy pc) {
+  const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+  if (t >= count) return;
+  const uint32_t n = node[t];
+  const uint32_t* r = rows + (size_t)t * row_words;
+  uint32_t* rec = reinterpret_cast<uint32_t*>(nodes + (size_t)n * stride);
+  const uint32_t RW = stride / 4u;
+  for (uint32_t w = 0; w < RW; ++w) rec[w] = r[w];
+  if (!sum) return;
+  const uint32_t SS = k1sum_stride((int)K), S2 = k2sum_stride((int)K), MS = mix_stride((int)K),
+                 XS = x1_stride((int)K);
+  const uint32_t q = pc.inv ? pc.inv[n] : 0u;
+  uint32_t* sp = reinterpret_cast<uint32_t*>(pc.sum);
+  uint32_t* s2p = reinterpret_cast<uint32_t*>(pc.sum2);
+  r += RW;
+  for (uint32_t w = 0; w < SS / 4u; ++w) {
+    sum[sum_index(n, w, SS)] = r[w];
+    if (pc.inv) sp[sum_index(q, w, SS)] = r[w];
+  }
+  r += SS / 4u;
+  for (uint32_t w = 0; w < S2 / 4u; ++w) {
+    sum2[sum_index(n, w, S2)] = r[w];
+    if (pc.inv) s2p[sum_index(q, w, S2)] = r[w];
+  }
+  r += S2 / 4u;
+  for (uint32_t w = 0; w < MS / 4u; ++w) {
+    mix[sum_index(n, w, MS)] = r[w];
+    if (pc.inv) pc.mix[sum_index(q, w, MS)] = r[w];
+  }
+  r += MS / 4u;
+  for (uint32_t w = 0; w < XS / 4u; ++w) {
+    x1[sum_index(n, w, XS)] = r[w];
+    if (pc.inv) pc.x1[sum_index(q, w, XS)] = r[w];
+  }
+}
+
+hipError_t launch_set_cards(unsigned char* nodes, uint32_t stride, const uint32_t* node,
+                            const uint32_t* rows, uint32_t row_words, uint32_t count, int K,
+                            uint32_t* sum, uint32_t* sum2, uint32_t* mix, uint32_t* x1,
+                            const PermCopy& pc, hipStream_t s) {
+  if (count == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_set_cards, pod_grid(count), dim3(kBlock), 0, s, nodes, stride, node, rows,
+                     row_words, count, (uint32_t)K, sum, sum2, mix, x1, pc);
+  return hipGetLastError();
+}
+
+// The block summaries (yoda_layout.h BlockSumWord) of one summary order from its DEVICE K1 / K2
+// summaries, K1 tiles and model rows: what yoda_upload_nodes builds on the host, word for word
+// (yoda_snapshot_check compares the two).  One wave per 64-node block, lane = node; the whole
+// row is written, the CardNumber bounds tight.
+__global__ __launch_bounds__(kWave) void k_bsum_build(const uint32_t* __restrict__ sum,
+                                                      const uint32_t* __restrict__ sum2,
+                                                      const uint32_t* __restrict__ x1,
+                                                      const uint32_t* __restrict__ mix,
+                                                      uint32_t n_nodes, uint32_t K,
+                                                      uint32_t* __restrict__ bsum) {
+  __shared__ uint32_t o[kBsT + 2u * 16u];  // a BlockSumWord row at K = 16
+  __shared__ uint32_t chs[4][kWave];
+  const uint32_t b = blockIdx.x, lane = threadIdx.x, n = b * 64u + lane;
+  const bool v = n < n_nodes;
+  const uint32_t nreal = min(64u, n_nodes - b * 64u);
+  const uint32_t SS = k1sum_stride((int)K), S2 = k2sum_stride((int)K), MS = mix_stride((int)K),
+                 XS = x1_stride((int)K), BS = bsum_stride((int)K);
+  auto w1 = [&](uint32_t w) { return v ? sum[sum_index(n, w, SS)] : 0u; };
+  auto w2 = [&](uint32_t w) { return v ? sum2[sum_index(n, w, S2)] : 0u; };
+  auto wx = [&](uint32_t w) { return v ? x1[sum_index(n, w, XS)] : 0u; };
+  auto wm = [&](uint32_t w) { return v ? mix[sum_index(n, w, MS)] : 0u; };
+  const uint64_t cn = (uint64_t)w1(kSumCnLo) | ((uint64_t)w1(kSumCnHi) << 32);
+  const uint32_t meta = w1(kSumMeta), nh = (meta >> 8) & 0xffu, mrf1 = w1(kSumMrf1);
+  const uint32_t cnt = min((w2(kS2Meta) >> 8) & 0xffu, K);
+  const bool one = (meta & kSumUni4) && (meta & kSumUniTotal);
+  const uint32_t chg = wx(kX1Chg);
+  // the clocks of the node's real cards and of its healthy cards (model row, free order)
+  uint32_t c0 = ~0u, c1 = 0u, c2 = ~0u, c3 = 0u;
+  {
+    const uint32_t hm = wm(mix_hm((int)K));
+    for (uint32_t j = 0; j < cnt; ++j) {
+      const uint32_t ck = wm(mix_word(kMixCk, (int)j, (int)K));
+      c0 = min(c0, ck);
+      c1 = max(c1, ck);
+      if ((hm >> j) & 1u) c2 = min(c2, ck), c3 = max(c3, ck);
+    }
+  }
+  // saturation: 1 + the free of the last card (free order) where a prefix maximum changes
+  uint32_t sat1 = mrf1;
+  if (!one && cnt > 0u) {
+    const uint32_t c = chg & ((2u << K) - 2u);
+    const uint32_t jl = c ? 30u - (uint32_t)__clz((int)c) : 0u;  // bit jl + 1
+    sat1 = w2(kS2Fs + jl) + 1u;
+  }
+  // the six maxima contributions (kMax* order)
+  uint32_t mv[6] = {w1(kSumBw), w1(kSumClock), w1(kSumCore), mrf1 - (mrf1 != 0u ? 1u : 0u),
+                    w1(kSumPower), w1(kSumTotal)};
+  if (!one && cnt > 0u) {  // the all-card maxima (K1MixWord pm over every card)
+    const uint32_t a = wx(x1_pm((int)cnt - 1, 0)), bb = wx(x1_pm((int)cnt - 1, 1));
+    if (!(meta & kSumUni4)) {
+      mv[kMaxBw] = a >> 16;
+      mv[kMaxClock] = a & 0xffffu;
+      mv[kMaxCore] = bb & 0xffffu;
+      mv[kMaxPower] = bb >> 16;
+    }
+    mv[kMaxTotal] = wx(x1_pm((int)cnt - 1, 2));
+  }
+#pragma unroll
+  for (uint32_t e = 0; e < 4u; ++e) chs[e][lane] = wx(kX1Ch + e);
+  const uint32_t hc_bad =
+      wave_max_u32v((v && ((chg & kX1ChgMany) || (nh > 0u && c3 > 0xffffu))) ? 1u : 0u);
+  const uint64_t cmin = wave_min_u64v(v ? cn : ~0ull), cmax = wave_max_u64v(v ? cn : 0ull);
+  const uint32_t not4 = wave_max_u32v((v && !(meta & kSumUni4)) ? 1u : 0u);
+  const uint32_t nott = wave_max_u32v((v && !(meta & kSumUniTotal)) ? 1u : 0u);
+  const uint32_t nzt = wave_sum_u32((v && (meta & kSumZeroTotal)) ? 1u : 0u);
+  const uint32_t ckmin = wave_min_u32v(v ? c0 : ~0u), ckmax = wave_max_u32v(v ? c1 : 0u);
+  const uint32_t hmin = wave_min_u32v(v ? c2 : ~0u), hmax = wave_max_u32v(v ? c3 : 0u);
+  const uint32_t nhmin = wave_min_u32v(v ? nh : ~0u), nhmax = wave_max_u32v(v ? nh : 0u);
+  const uint32_t mrmin = wave_min_u32v(v ? mrf1 : ~0u), mrmax = wave_max_u32v(v ? mrf1 : 0u);
+  const uint32_t sat = wave_min_u32v(v ? sat1 : ~0u);
+  uint32_t mx[6], wc[6], wl[6];
+#pragma unroll
+  for (int f = 0; f < 6; ++f) {
+    mx[f] = wave_max_u32v(v ? mv[f] : 0u);
+    const bool hit = v && mv[f] == mx[f];
+    wc[f] = wave_sum_u32(hit ? 1u : 0u);
+    wl[f] = wave_min_u32v(hit ? lane : ~0u);
+  }
+  if (lane == 0u) {
+    uint32_t fl = kBsOneModel | kBsUni4;
+    if (not4) fl &= ~(kBsUni4 | kBsOneModel);
+    if (nott) fl &= ~kBsOneModel;
+    o[kBsCnMin] = (uint32_t)min(cmin, (uint64_t)0xffffffffu);
+    o[kBsCnMax] = (uint32_t)min(cmax, (uint64_t)0xffffffffu);
+    o[kBsFlags] = fl;
+    o[kBsCkMin] = ckmin;
+    o[kBsCkMax] = ckmax;
+    o[kBsHckMin] = hmin;
+    o[kBsHckMax] = hmax;
+    o[kBsNhMin] = nhmin;
+    o[kBsNhMax] = nhmax;
+    o[kBsMrfMin] = mrmin;
+    o[kBsMrfMax] = mrmax;
+    o[kBsNReal] = nreal;
+    o[kBsNzt] = nzt;
+    o[kBsSat] = sat;
+#pragma unroll
+    for (int f = 0; f < 6; ++f) {
+      o[kBsMx + f] = mx[f];
+      o[kBsWc + f] = wc[f];
+      o[kBsWl + f] = wl[f];
+    }
+#pragma unroll
+    for (uint32_t e = 0; e < 4u; ++e) o[kBsHc + e] = 0u;
+  }
+  for (uint32_t t = 0; t < K; ++t) {  // the per-need bounds of hfs[t]
+    const uint32_t hf = w1(kSumHfs + t);
+    const uint32_t lo = wave_min_u32v(v ? hf : ~0u), hi = wave_max_u32v(v ? hf : 0u);
+    if (lane == 0u) o[kBsT + t] = lo, o[kBsT + K + t] = hi;
+  }
+  __syncthreads();
+  // the healthy cards per clock over the block's nodes: the union of the nodes' ch entries in
+  // node order (at most 4 clocks, else no table), a short serial loop over LDS
+  if (lane == 0u && !hc_bad) {
+    uint32_t hc_clk[4] = {0, 0, 0, 0}, hc_lo[4] = {0, 0, 0, 0}, hc_hi[4] = {0, 0, 0, 0};
+    uint32_t n_hc = 0;
+    bool ok = true;
+    for (uint32_t l = 0; l < nreal && ok; ++l) {
+      uint32_t mine[4] = {0, 0, 0, 0};
+      for (uint32_t e = 0; e < 4u; ++e) {
+        const uint32_t xw = chs[e][l];
+        if ((xw >> 16) == 0u) continue;
+        const uint32_t ck = xw & 0xffffu;
+        uint32_t k = 0;
+        while (k < n_hc && hc_clk[k] != ck) ++k;
+        if (k == n_hc) {
+          if (n_hc == 4u) { ok = false; break; }
+          hc_clk[k] = ck;
+          hc_lo[k] = l == 0u ? ~0u : 0u;  // the nodes before lacked it
+          hc_hi[k] = 0u;
+          ++n_hc;
+        }
+        mine[k] = xw >> 16;
+      }
+      if (!ok) break;
+      for (uint32_t k = 0; k < n_hc; ++k) {
+        hc_lo[k] = min(hc_lo[k], mine[k]);
+        hc_hi[k] = max(hc_hi[k], mine[k]);
+      }
+    }
+    if (ok) {
+      o[kBsFlags] |= kBsHcTab | (n_hc << 8);
+      for (uint32_t k = 0; k < n_hc; ++k)
+        o[kBsHc + k] = hc_clk[k] | (hc_lo[k] << 16) | (hc_hi[k] << 24);
+    }
+  }
+  __syncthreads();
+  for (uint32_t w = lane; w < BS / 4u; w += kWave) bsum[sum_index(b, w, BS)] = o[w];
+}
+
+hipError_t launch_bsum_build(int K, const uint32_t* sum, const uint32_t* sum2, const uint32_t* x1,
+                             const uint32_t* mix, uint32_t n_nodes, uint32_t* bsum,
+                             hipStream_t s) {
+  if (n_nodes == 0) return hipSuccess;
+  if (K < 1 || K > 16) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_bsum_build, dim3((n_nodes + 63) / 64), dim3(kWave), 0, s, sum, sum2, x1,
+                     mix, n_nodes, (uint32_t)K, bsum);
+  return hipGetLastError();
+}
+
 int topk_k() { return kTopK; }
 int topk_k_capacity() { return kTopKCap; }
 

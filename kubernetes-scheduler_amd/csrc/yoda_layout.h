@@ -320,6 +320,9 @@ struct PermCopy {
   const uint32_t* inv = nullptr;
   unsigned char* sum = nullptr;
   unsigned char* sum2 = nullptr;
+  // the per-card model rows and the K1 mixed tiles in that order (k_set_cards writes them too)
+  uint32_t* mix = nullptr;
+  uint32_t* x1 = nullptr;
   // and the block summaries' CardNumber bounds (BlockSumWord), of the snapshot order and of
   // the block-grouped order, widened with atomics so that they stay valid bounds
   uint32_t* bsum = nullptr;

@@ -313,6 +313,25 @@ func (g *Handle) SetNodeState(idx []uint32, alloc, cardNumber []uint64) error {
 	return check(g.h, rc, "yoda_set_node_state")
 }
 
+// UpdateCards replaces the dynamic SCV metrics of a few nodes on the device -- every card's
+// FreeMemory and Health, and FreeMemorySum -- without re-uploading the snapshot
+// (yoda_update_node_cards).  idx are snapshot positions; free and healthy hold maxCards slots
+// per listed node.  An error that wraps YODA_ERR_RANGE leaves the handle as it was: upload the
+// snapshot again.
+func (g *Handle) UpdateCards(idx []uint32, maxCards int, free []uint64, healthy []uint8, freeSum []uint64) error {
+	if len(idx) != len(freeSum) || len(free) != len(idx)*maxCards || len(healthy) != len(free) {
+		return errors.New("yodagpu: UpdateCards arrays differ in length")
+	}
+	if len(idx) == 0 {
+		return nil
+	}
+	// plain-number Go slices passed directly as arguments: allowed by the cgo rules
+	rc := C.yoda_update_node_cards(g.h, C.uint32_t(len(idx)), (*C.uint32_t)(unsafe.Pointer(&idx[0])),
+		C.uint32_t(maxCards), (*C.uint64_t)(unsafe.Pointer(&free[0])),
+		(*C.uint8_t)(unsafe.Pointer(&healthy[0])), (*C.uint64_t)(unsafe.Pointer(&freeSum[0])))
+	return check(g.h, rc, "yoda_update_node_cards")
+}
+
 // packPods parses the scv/* labels and the diskIO annotation with the reference's own
 // helpers (filter.go:60-74, sort.go:12-18, algorithm.go:103-104) into the C-side
 // yoda_pod_soa arrays.

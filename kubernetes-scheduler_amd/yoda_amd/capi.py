@@ -77,6 +77,8 @@ _SIGS = {
     "yoda_topk_k": ([], C.c_int),
     "yoda_topk_k_capacity": ([], C.c_int),
     "yoda_set_node_state": ([_vp, _u32, _vp, _vp, _vp], C.c_int),
+    "yoda_update_node_cards": ([_vp, _u32, _vp, _u32, _vp, _vp, _vp], C.c_int),
+    "yoda_snapshot_check": ([_vp, _vp, _vp], C.c_int),
     "yoda_shard_topk": ([_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp], C.c_int),
     "yoda_shard_topk_depth": ([_vp], C.c_int),
     "yoda_greedy_cap_depth": ([], C.c_int),
@@ -448,6 +450,35 @@ class Yoda:
         c = np.ascontiguousarray(card_number, np.uint64)
         self._check(lib().yoda_set_node_state(self._h, n.size, _np_ptr(n), _np_ptr(a),
                                               _np_ptr(c)), "yoda_set_node_state")
+
+    def update_cards(self, nodes, card_free_memory, card_healthy, free_memory_sum):
+        """The dynamic SCV metrics of the listed GLOBAL node ids (others ignored), no re-upload
+        (yoda_update_node_cards): card_free_memory / card_healthy [n, max_cards], free_memory_sum
+        [n].  YodaError with code YODA_ERR_RANGE: the snapshot's format cannot hold a value --
+        the handle is unchanged; upload the snapshot again."""
+        n = np.ascontiguousarray(nodes, np.uint32).ravel()
+        f = np.ascontiguousarray(card_free_memory, np.uint64)
+        hl = np.ascontiguousarray(card_healthy, np.uint8)
+        s = np.ascontiguousarray(free_memory_sum, np.uint64).ravel()
+        if n.size == 0:
+            k = 1
+        else:
+            f = f.reshape(n.size, -1)
+            hl = hl.reshape(n.size, -1)
+            k = f.shape[1]
+            if hl.shape != f.shape or s.size != n.size:
+                raise ValueError("update_cards: arrays differ in shape")
+        self._check(lib().yoda_update_node_cards(self._h, n.size, _np_ptr(n), k, _np_ptr(f),
+                                                 _np_ptr(hl), _np_ptr(s)),
+                    "yoda_update_node_cards")
+
+    def snapshot_check(self):
+        """(digest [8] u64, mismatch [4] u32) of yoda_snapshot_check (diagnostic; synchronizes)."""
+        d = np.zeros(8, np.uint64)
+        m = np.zeros(4, np.uint32)
+        self._check(lib().yoda_snapshot_check(self._h, _np_ptr(d), _np_ptr(m)),
+                    "yoda_snapshot_check")
+        return d, m
 
     def shard_topk_depth(self) -> int:
         """Candidates per pod the next shard_topk lists (yoda_shard_topk_depth): topk_k() after

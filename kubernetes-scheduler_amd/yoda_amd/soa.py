@@ -172,6 +172,33 @@ class NodeSoA:
         )
 
 
+_STATIC_FIELDS = ("card_count", "total_memory_sum", "card_total_memory", "card_clock",
+                  "card_bandwidth", "card_core", "card_power")
+
+
+def card_delta(old: NodeSoA, new: NodeSoA):
+    """What Yoda.update_cards needs to take a handle uploaded with `old` to `new`: (ids u32 [n],
+    card_free_memory u64 [n, K], card_healthy u8 [n, K], free_memory_sum u64 [n]) of the nodes
+    whose dynamic SCV metrics -- a card's FreeMemory or Health, FreeMemorySum -- differ (n may
+    be 0).  None when n_nodes, max_cards, a card count or any static field (TotalMemory[Sum],
+    clock, bandwidth, core, power) differs: upload `new` instead.  CardNumber and the allocated
+    memory are not its business: their differences are neither reported nor a reason for None
+    (Yoda.set_node_state / update_alloc carry those).  cpu / disk_io (Mode B) are ignored too."""
+    a, b = old.normalized(), new.normalized()
+    if a.n_nodes != b.n_nodes or a.max_cards != b.max_cards:
+        return None
+    for f in _STATIC_FIELDS:
+        if not np.array_equal(getattr(a, f), getattr(b, f)):
+            return None
+    moved = ((a.card_free_memory != b.card_free_memory).any(axis=1) |
+             (a.card_healthy.astype(bool) != b.card_healthy.astype(bool)).any(axis=1) |
+             (a.free_memory_sum != b.free_memory_sum))
+    ids = np.flatnonzero(moved).astype(np.uint32)
+    return (ids, np.ascontiguousarray(b.card_free_memory[ids]),
+            np.ascontiguousarray(b.card_healthy[ids]),
+            np.ascontiguousarray(b.free_memory_sum[ids]))
+
+
 @dataclass
 class PodSoA:
     has_number: np.ndarray  # u8 [P]
