@@ -440,8 +440,10 @@ int yoda_update_node_cards(yoda_t* h, uint32_t count, const uint32_t* nodes, uin
  * holds them -- records, K1 summaries, K2 summaries, per-card model rows, K1 mixed tiles, block
  * summaries, G table, G maxima + reciprocals (0 where the record path has none).  mismatch[4]:
  * words of the block-grouped copies that differ from the base rows permuted by the node order;
- * words of the upload-order block summaries that differ from k_bsum_build run now into a
- * scratch buffer; the same for the block-grouped order; words of the host mirrors that differ
+ * words of the stored upload-order block summaries that differ from a fresh build (k_bsum_build,
+ * the builder of the upload and of the card updates, run now into a zeroed scratch buffer): a
+ * stale or loose row after yoda_set_node_state or a card update, or a padding word an older
+ * snapshot left; the same for the block-grouped order; words of the host mirrors that differ
  * from the device.  CardNumber bounds are tightened first if node-state pushes left them
  * loose. */
 int yoda_snapshot_check(yoda_t* h, uint64_t* digest, uint32_t* mismatch);

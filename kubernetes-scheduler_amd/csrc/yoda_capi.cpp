@@ -219,10 +219,18 @@ struct Status {
   std::string msg;
 };
 
-// Grow-only device buffer.
+// Grow-only device buffer; frees itself.  Not copyable: a handle's members, swapped in place.
 struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
+  void swap(DevBuf& o) {
+    std::swap(p, o.p);
+    std::swap(bytes, o.bytes);
+  }
   hipError_t ensure(size_t n) {
     if (n <= bytes) return hipSuccess;
     if (p) (void)hipFree(p);
@@ -244,12 +252,16 @@ struct DevBuf {
   }
 };
 
-// Grow-only pinned host buffer (fast async H2D).
+// Grow-only pinned host buffer (fast async H2D); frees itself, not copyable.
 struct PinnedBuf {
   void* p = nullptr;
   size_t bytes = 0;
   void* dp = nullptr;  // the same pages as seen by kernels (hipHostMalloc maps them)
   unsigned flags = hipHostMallocDefault;  // hipHostMallocCoherent: polled by the host
+  PinnedBuf() = default;
+  PinnedBuf(const PinnedBuf&) = delete;
+  PinnedBuf& operator=(const PinnedBuf&) = delete;
+  ~PinnedBuf() { release(); }
   hipError_t ensure(size_t n) {
     if (n <= bytes) return hipSuccess;
     if (p) (void)hipHostFree(p);
@@ -580,27 +592,6 @@ struct yoda_handle {
   ~yoda_handle() {
     if (comm && rccl().ok) (void)rccl().comm_destroy(comm);
     for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
-    DevBuf* all[] = {&kx1_p, &kmix_p, &win_inv, &nodes,     &nodes_b,   &k1sum,     &k2sum,    &kmix,    &kx1,     &memtab,    &k1sum_p,   &k2sum_p,   &gtab_p, &blksum, &blksum_p, &kbub, &kbub_p, &kbdec, &kbdec_p, &kb_levels, &hot, &hot_p,    &perm_ids,  &perm_inv,    &pod_blob,   &maxima,       &counts,
-                     &pod_sorted, &perm,     &order_scratch, &order_meta, &order_hist,
-                     &order_bstart, &order_slot, &order_bkt,
-                     &rcp,       &best,       &idx,          &ties,
-                     &lowest,    &pick,      &status,     &ties_out,     &flagged,
-                     &n_flagged, &bitmask,   &bitmask_t,  &blk,  &bsum, &p_max_u,      &p_cnt, &lpt_w, &lpt_order, &k1_w, &k1_order, &k1_rec,
-                     &rows,      &rows_t,    &norm,      &tk_s_part,  &tk_i_part,    &tk_s,
-                     &tk_i,      &upd_node,  &upd_val,    &upd_cn,    &g1_part,   &g1_done,
-                     &p_best_f,  &p_best_i,  &p_idx,      &p_ties,       &p_low_f,
-                     &p_low_i,   &p_err,     &pick_alt,   &status_alt,   &ties_out_alt,
-                     &p_wit,     &wit,       &stats_dev, &one_feas,  &one_part,  &one_done,
-                     &ex1,       &rec,       &rec_all,   &cg_max,    &cg_cnt,    &cg_wit,    &cg_gather, &k3rec,     &k3all,
-                     &one_out,   &b_cab,     &b_cls,     &b_part,
-                     &counts_alt, &best_alt, &maxima_alt, &win_dev,
-                     &xcnt,      &xbest,     &xidx,      &xties,     &xlow,      &bsum_chk};
-    for (DevBuf* b : all) b->release();
-    pod_stage.release();
-    upd_stage.release();
-    pick_stage.release();
-    poll_stage.release();
-    win_stage.release();
     if (stage_event) (void)hipEventDestroy(stage_event);
     if (switch_event) (void)hipEventDestroy(switch_event);
     if (upd_event) (void)hipEventDestroy(upd_event);
@@ -1220,7 +1211,7 @@ int unpermute_outputs(yoda_t* h) {
     }
   }
   HIP_TRY(h, launch_permute(t, h->perm.as<uint32_t>(), W, true, h->stream));
-  for (const Arr& a : arrs) std::swap(*a.buf, *a.alt);
+  for (const Arr& a : arrs) a.buf->swap(*a.alt);
   return YODA_OK;
 }
 
@@ -1726,7 +1717,7 @@ int finalize(yoda_t* h, int mode, const uint32_t* counts, const int64_t* best,
                                h->status_alt.as<int32_t>(), h->ties_out_alt.as<uint32_t>(),
                                h->flagged.as<uint32_t>(), h->n_flagged.as<uint32_t>(), sc,
                                h->stream));
-    for (auto& pr : pairs) std::swap(*pr[0], *pr[1]);
+    for (auto& pr : pairs) pr[0]->swap(*pr[1]);
     h->maxima_sorted = true;
     return YODA_OK;
   }
@@ -1857,7 +1848,543 @@ int topk_lists(yoda_t* h, uint32_t P, uint32_t KT, const uint32_t* d_counts, uin
   return YODA_OK;
 }
 
-bool is_pow2_le16(uint32_t k) { return k == 1 || k == 2 || k == 4 || k == 8 || k == 16; }
+// ---- the derived tables of an N32 snapshot: one builder each, for yoda_upload_nodes and for
+// yoda_update_node_cards ----
+
+// The tiled per-node tables: the row stride, the table in snapshot order, its copy in the
+// block-grouped order, its yoda_snapshot_check digest slot.  The first kPackedTables hold the
+// rows pack_node writes (PackedRows order); the G table is built on the device.
+struct SumTable {
+  uint32_t stride;
+  DevBuf yoda_handle::*base;
+  DevBuf yoda_handle::*grouped;
+  int digest;
+};
+constexpr int kPackedTables = 4, kSumTables = 5;
+std::array<SumTable, kSumTables> sum_tables(int K) {
+  return {{{k1sum_stride(K), &yoda_handle::k1sum, &yoda_handle::k1sum_p, 1},
+           {k2sum_stride(K), &yoda_handle::k2sum, &yoda_handle::k2sum_p, 2},
+           {mix_stride(K), &yoda_handle::kmix, &yoda_handle::kmix_p, 3},
+           {x1_stride(K), &yoda_handle::kx1, &yoda_handle::kx1_p, 4},
+           {gtab_stride(K), &yoda_handle::gtab, &yoda_handle::gtab_p, 6}}};
+}
+
+// The G table of both orders from the current K2 summaries and the maxima in gtab_aux.
+int relaunch_gtables(yoda_t* h) {
+  uint32_t* rcp_dev = reinterpret_cast<uint32_t*>(h->gtab_aux.as<unsigned char>() + 48);
+  const MemTab mt = h->mem_ranks ? h->mt : MemTab{};
+  HIP_TRY(h, launch_gtable(h->K, h->k2sum.as<uint32_t>(), h->kmix.as<uint32_t>(), h->n_nodes,
+                           h->gtab_aux.as<uint64_t>(), h->gtab.as<uint32_t>(), rcp_dev, mt,
+                           h->stream));
+  if (h->perm_on)
+    HIP_TRY(h, launch_gtable(h->K, h->k2sum_p.as<uint32_t>(), h->kmix_p.as<uint32_t>(),
+                             h->n_nodes, h->gtab_aux.as<uint64_t>(), h->gtab_p.as<uint32_t>(),
+                             rcp_dev, mt, h->stream));
+  return YODA_OK;
+}
+
+float ru32(double r) {  // the smallest float >= r (yoda_kernels.hip ru32_of)
+  float f = (float)r;
+  if ((double)f < r) f = std::nextafter(f, INFINITY);
+  return f;
+}
+
+// The reciprocals of the G maxima as k_gtable left them (ten words at gtab_aux + 48), into
+// h->g.  Synchronises the stream.
+int read_g_reciprocals(yoda_t* h) {
+  uint32_t g_rcp[10] = {};
+  HIP_TRY(h, hipMemcpyAsync(g_rcp, h->gtab_aux.as<unsigned char>() + 48, sizeof(g_rcp),
+                            hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  std::memcpy(&h->g.r_bw, &g_rcp[0], 8);
+  std::memcpy(&h->g.r_core, &g_rcp[2], 8);
+  std::memcpy(&h->g.r_pow, &g_rcp[4], 8);
+  std::memcpy(&h->g.r_free, &g_rcp[6], 8);
+  std::memcpy(&h->g.r_tot, &g_rcp[8], 8);
+  h->g.f_bw = ru32(h->g.r_bw);
+  h->g.f_core = ru32(h->g.r_core);
+  h->g.f_pow = ru32(h->g.r_pow);
+  return YODA_OK;
+}
+
+// The block summaries of both orders from the device summaries (k_bsum_build).
+int rebuild_block_sums(yoda_t* h) {
+  HIP_TRY(h, launch_bsum_build(h->K, h->k1sum.as<uint32_t>(), h->k2sum.as<uint32_t>(),
+                               h->kx1.as<uint32_t>(), h->kmix.as<uint32_t>(), h->n_nodes,
+                               h->blksum.as<uint32_t>(), h->stream));
+  if (h->perm_on)
+    HIP_TRY(h, launch_bsum_build(h->K, h->k1sum_p.as<uint32_t>(), h->k2sum_p.as<uint32_t>(),
+                                 h->kx1_p.as<uint32_t>(), h->kmix_p.as<uint32_t>(), h->n_nodes,
+                                 h->blksum_p.as<uint32_t>(), h->stream));
+  h->blksum_loose = false;
+  return YODA_OK;
+}
+
+// ---- yoda_upload_nodes, step by step ----
+
+// The caller's arrays: present, within the limits; *kmax: the largest card count (at least 1).
+int check_node_soa(yoda_t* h, const yoda_node_soa* nd, uint32_t node_offset, uint32_t* kmax) {
+  if (!nd) return fail(h, YODA_ERR_INVALID_ARG, "nodes is NULL");
+  const uint32_t N = nd->n_nodes, KS = nd->max_cards;
+  if (KS < 1 || KS > YODA_MAX_CARDS)
+    return fail(h, YODA_ERR_INVALID_ARG, "max_cards must be in 1..16");
+  if (N > 0 && (!nd->card_number || !nd->card_count || !nd->free_memory_sum ||
+                !nd->total_memory_sum || !nd->card_free_memory || !nd->card_total_memory ||
+                !nd->card_clock || !nd->card_bandwidth || !nd->card_core || !nd->card_power ||
+                !nd->card_healthy))
+    return fail(h, YODA_ERR_INVALID_ARG, "a required node array is NULL");
+  if ((uint64_t)node_offset + N > 0x7fffffffull)
+    return fail(h, YODA_ERR_RANGE, "node index exceeds int32");
+  *kmax = 1;
+  for (uint32_t i = 0; i < N; ++i) {
+    if (nd->card_count[i] > KS) return fail(h, YODA_ERR_INVALID_ARG, "card_count > max_cards");
+    *kmax = std::max(*kmax, nd->card_count[i]);
+  }
+  return YODA_OK;
+}
+
+// What an upload decides about the snapshot before it packs a row.
+struct UploadFormat {
+  int K = 1;
+  Path path = Path::N32;
+  bool ranks = false;   // the N32 memory fields hold ranks (yoda_layout.h MemTab)
+  bool pack16 = true, q32 = true;
+  bool all_one = true;  // every node one GPU model with one TotalMemory
+  uint64_t max_small = 0;
+  uint64_t score_bound = ~0ull;  // yoda_handle::score_bound, sb_cards, sb_actual
+  long double sb_cards = 0.0L;
+  uint64_t sb_actual = 0;
+  std::vector<uint64_t> stat;  // per node: the static score ...
+  std::vector<uint8_t> zt;     // ... and TotalMemorySum == 0
+};
+
+// Record format: the narrowest exact one.
+UploadFormat choose_format(const yoda_node_soa* nd, int K, uint32_t flags) {
+  const uint32_t N = nd->n_nodes, KS = nd->max_cards;
+  UploadFormat f;
+  f.K = K;
+  f.stat.resize(N);
+  f.zt.resize(N);
+  uint64_t max_field = 0, max_small = 0, max_clock = 0, max_static = 0, max_mem = 0;
+  uint64_t max_ckq = 0;  // the largest clock quotient a card can score
+  bool all_one = true;   // every node one GPU model with one TotalMemory
+  for (uint32_t i = 0; i < N; ++i) {
+    bool z = false;
+    const uint64_t alloc = nd->alloc_memory ? nd->alloc_memory[i] : 0;
+    f.stat[i] = static_score(nd->free_memory_sum[i], nd->total_memory_sum[i], alloc, &z);
+    f.zt[i] = z;
+    max_static = std::max(max_static, f.stat[i]);
+    for (uint32_t j = 0; j < nd->card_count[i]; ++j) {
+      const size_t k = (size_t)i * KS + j;
+      max_field = std::max({max_field, nd->card_free_memory[k], nd->card_total_memory[k],
+                            nd->card_clock[k], nd->card_bandwidth[k], nd->card_core[k],
+                            nd->card_power[k]});
+      max_small = std::max({max_small, nd->card_bandwidth[k], nd->card_core[k],
+                            nd->card_power[k], nd->card_clock[k]});
+      max_mem = std::max({max_mem, nd->card_free_memory[k], nd->card_total_memory[k]});
+      max_clock = std::max(max_clock, nd->card_clock[k]);
+      // clock / MaxBandwidth (algorithm.go:283): a scored card qualifies, so MaxBandwidth is
+      // at least its own bandwidth (and 1)
+      if (nd->card_clock[k] <= kN32FieldMax)
+        max_ckq = std::max(max_ckq, nd->card_clock[k] * 100u /
+                                        std::max<uint64_t>(1, nd->card_bandwidth[k]));
+    }
+    // one GPU model with one TotalMemory (the mixed-model K1 tiles pack small fields in 16 bits)
+    const size_t a = (size_t)i * KS;
+    bool one = nd->card_count[i] > 0 && !(flags & YODA_UPLOAD_NO_UNIFORM);
+    for (uint32_t j = 1; j < nd->card_count[i] && one; ++j)
+      one = nd->card_clock[a + j] == nd->card_clock[a] &&
+            nd->card_bandwidth[a + j] == nd->card_bandwidth[a] &&
+            nd->card_core[a + j] == nd->card_core[a] && nd->card_power[a + j] == nd->card_power[a] &&
+            nd->card_total_memory[a + j] == nd->card_total_memory[a];
+    all_one = all_one && one;
+  }
+  // per-card score <= 800 + 100*clock (five quotients <= 100, clock/MaxBandwidth <= 100*clock)
+  const long double score_bound =
+      (long double)K * (800.0L + 100.0L * (long double)max_clock) + (long double)max_static;
+  const bool f64_ok = max_field <= kFastFieldMax && score_bound < (long double)kFastScoreMax;
+  {
+    uint64_t max_actual = 0;  // Actual does not depend on the allocated memory
+    for (uint32_t i = 0; i < N; ++i)
+      if (nd->total_memory_sum[i] != 0)
+        max_actual = std::max(max_actual,
+                              nd->free_memory_sum[i] * 100u / nd->total_memory_sum[i] * 2u);
+    const long double b = (long double)K * (800.0L + 100.0L * (long double)max_clock) + 300.0L +
+                          (long double)max_actual;
+    f.score_bound = b < 9.0e18L ? (uint64_t)b + 1u : ~0ull;
+    // (yoda_update_node_cards raises the Actual term with the nodes' new FreeMemorySum)
+    f.sb_cards = (long double)K * (800.0L + 100.0L * (long double)max_clock) + 300.0L;
+    f.sb_actual = max_actual;
+  }
+  // N32: every small card field in u32, every quotient exact in f64 (x, M < 2^32: 300 x + M
+  // < 2^53) -- the block K2 keeps the small-field quotients in f32 while those fields are
+  // <= kF32SmallMax (q32) -- the card score summed in u32: per card at most 800 + the clock
+  // quotient.  Small fields beyond that need one-model nodes (the mixed-model K1 tiles pack
+  // them in 16 bits, and the f64 block K2 is instantiated without the mixed-model rows); beyond
+  // 16 bits the K1 writes unpacked partial words (kWideWords).  Memory fields beyond 32 bits (e.g.
+  // bytes) keep the N32 path with memory RANKS in the u32 fields (yoda_layout.h MemTab):
+  // every compare and max is unchanged, the values come back for the quotients and the
+  // maxima (all <= 2^44: exact in f64).
+  f.pack16 = max_small <= kPack16Max;
+  f.q32 = max_small <= kF32SmallMax && !(flags & YODA_UPLOAD_F64_QUOTIENTS);
+  const bool n32_ok = f64_ok && max_small <= kN32FieldMax && (f.q32 || all_one) &&
+                      (uint64_t)K * (800u + max_ckq) < (1ull << 32);
+  f.path = n32_ok ? Path::N32 : (f64_ok ? Path::F64 : Path::U64);
+  if ((flags & YODA_UPLOAD_FORCE_F64) && f.path == Path::N32) f.path = Path::F64;
+  if (flags & YODA_UPLOAD_FORCE_GENERIC) f.path = Path::U64;
+  f.ranks = f.path == Path::N32 &&
+            (max_mem > kN32FieldMax || (flags & YODA_UPLOAD_MEM_RANKS) != 0u);
+  f.all_one = all_one;
+  f.max_small = max_small;
+  return f;
+}
+
+// Memory ranks: the distinct card FreeMemory / TotalMemory values, ascending (empty without
+// ranks), and the u32 code of a value: the value itself, or 2 + its rank.
+struct MemCodes {
+  bool ranks = false;
+  std::vector<uint64_t> frees, totals;
+  static uint32_t code(bool ranks, const std::vector<uint64_t>& v, uint64_t x) {
+    if (!ranks) return (uint32_t)x;
+    return 2u + (uint32_t)(std::lower_bound(v.begin(), v.end(), x) - v.begin());
+  }
+  uint32_t code_f(uint64_t x) const { return code(ranks, frees, x); }
+  uint32_t code_t(uint64_t x) const { return code(ranks, totals, x); }
+};
+
+MemCodes build_mem_codes(const yoda_node_soa* nd, bool ranks) {
+  MemCodes mc;
+  mc.ranks = ranks;
+  if (!ranks) return mc;
+  const uint32_t N = nd->n_nodes, KS = nd->max_cards;
+  for (uint32_t i = 0; i < N; ++i)
+    for (uint32_t j = 0; j < nd->card_count[i]; ++j) {
+      mc.frees.push_back(nd->card_free_memory[(size_t)i * KS + j]);
+      mc.totals.push_back(nd->card_total_memory[(size_t)i * KS + j]);
+    }
+  for (auto* v : {&mc.frees, &mc.totals}) {
+    std::sort(v->begin(), v->end());
+    v->erase(std::unique(v->begin(), v->end()), v->end());
+  }
+  return mc;
+}
+
+// Every node's rows, node-major as pack_node writes them (sum .. x1: the N32 path only).
+struct PackedRows {
+  std::vector<unsigned char> rec;
+  std::vector<uint32_t> sum, sum2, mix, x1;
+  uint32_t n_one_model = 0, n_uni4 = 0;
+};
+
+PackedRows pack_rows(const yoda_node_soa* nd, const UploadFormat& f, const MemCodes& mc,
+                     uint32_t flags) {
+  const uint32_t N = nd->n_nodes, KS = nd->max_cards;
+  const int K = f.K;
+  const Path path = f.path;
+  PackedRows r;
+  const size_t stride = path == Path::N32 ? n32_stride(K) : node_stride(K);
+  r.rec.assign((size_t)std::max<uint32_t>(N, 1) * stride, 0);
+  // K1 node summaries (N32 path): the facts the block-classified K1 reads per node
+  const bool want_sum = path == Path::N32;
+  const size_t rows = want_sum ? std::max<uint32_t>(N, 1) : 0;
+  const size_t sstride = k1sum_stride(K), s2stride = k2sum_stride(K), mstride = mix_stride(K),
+               xstride = x1_stride(K);
+  r.sum.assign(rows * sstride / 4, 0);
+  r.sum2.assign(rows * s2stride / 4, 0);
+  r.mix.assign(rows * mstride / 4, 0);
+  r.x1.assign(rows * xstride / 4, 0);
+  for (uint32_t i = 0; i < N; ++i) {
+    // the node's rows, packed by the one per-node packer (yoda_node_pack.h)
+    const size_t a = (size_t)i * KS;
+    const uint32_t cnt = nd->card_count[i];
+    uint32_t fc[YODA_MAX_CARDS], tc[YODA_MAX_CARDS];
+    if (path == Path::N32)
+      for (uint32_t j = 0; j < cnt; ++j) {
+        fc[j] = mc.code_f(nd->card_free_memory[a + j]);
+        tc[j] = mc.code_t(nd->card_total_memory[a + j]);
+      }
+    NodePackIn in;
+    in.cnt = cnt;
+    in.card_number = nd->card_number[i];
+    in.stat = f.stat[i];
+    in.zero_total = f.zt[i] != 0;
+    in.no_uniform = (flags & YODA_UPLOAD_NO_UNIFORM) != 0u;
+    in.free_memory = nd->card_free_memory + a;
+    in.total_memory = nd->card_total_memory + a;
+    in.clock = nd->card_clock + a;
+    in.bandwidth = nd->card_bandwidth + a;
+    in.core = nd->card_core + a;
+    in.power = nd->card_power + a;
+    in.healthy = nd->card_healthy + a;
+    in.fcode = fc;
+    in.tcode = tc;
+    NodePackOut out;
+    out.zeroed = true;  // (the vectors above: value-initialised, each row packed once)
+    out.rec = r.rec.data() + (size_t)i * stride;
+    if (want_sum) {
+      out.sum = r.sum.data() + (size_t)i * sstride / 4;
+      out.sum2 = r.sum2.data() + (size_t)i * s2stride / 4;
+      out.mix = r.mix.data() + (size_t)i * mstride / 4;
+      out.x1 = r.x1.data() + (size_t)i * xstride / 4;
+    }
+    const uint32_t nf = pack_node(path, K, in, out);
+    r.n_one_model += (nf & (kNodeUniform4 | kNodeUniformTotal)) ==
+                     (kNodeUniform4 | kNodeUniformTotal);
+    r.n_uni4 += (nf & kNodeUniform4) != 0u;
+  }
+  return r;
+}
+
+// Block-grouped node order for the private batch runs (node order): a
+// snapshot of one-model nodes is dealt into 64-node blocks of one clock each (PodFitsClock
+// then rules whole blocks out for a clock-labelled wave, and K2 skips them), whole blocks
+// round-robin in proportion to each clock's block count so that every node chunk keeps
+// the snapshot's mix, the groups' remainders last.  Copies of the K1 / K2 summaries in
+// that order; the kernels compare the nodes' local ids (perm_ids) on score ties.
+// `sum`: the node-major K1 summaries of an N32 snapshot.  Returns the node of each position,
+// empty when the snapshot keeps its own order.
+std::vector<uint32_t> grouped_node_order(const std::vector<uint32_t>& sum, uint32_t N, int K,
+                                         bool ranks, bool all_one_model, uint32_t flags) {
+  static const bool perm_env = YODA_KNOB("YODA_NODE_PERM", 1) != 0;
+  std::vector<uint32_t> nperm;
+  // Mixed-model nodes (cards of several GPU models) form a group of their own, so that
+  // the one-model nodes still fill one-model blocks, which the block summaries decide
+  // whole (50 % mixed-model nodes: every block mixed without it).  YODA_NODE_PERM_MIXED=0
+  // (A/B knob): one-model snapshots only, as in round 5.
+  static const bool perm_mixed = YODA_KNOB("YODA_NODE_PERM_MIXED", 1) != 0;
+  if (!(perm_env && (all_one_model || perm_mixed) && N >= 4096 &&
+        !(flags & YODA_UPLOAD_PER_NODE_K1) && !(flags & YODA_UPLOAD_PER_NODE_K2)))
+    return nperm;
+  const uint32_t SW = k1sum_stride(K) / 4u;
+  std::vector<uint32_t> keys;
+  std::vector<std::vector<uint32_t>> grp;
+  bool ok = true;
+  for (uint32_t i = 0; i < N && ok; ++i) {
+    // (a mixed-model node's kSumClock is its first card's: the key of its group is ~0)
+    const uint32_t ck = (sum[(size_t)i * SW + kSumMeta] & kSumUni4)
+                            ? sum[(size_t)i * SW + kSumClock] : 0xffffffffu;
+    size_t g = 0;
+    while (g < keys.size() && keys[g] != ck) ++g;
+    if (g == keys.size()) {
+      if (keys.size() == 64) ok = false;  // too many clocks to group usefully
+      keys.push_back(ck);
+      grp.emplace_back();
+    }
+    if (ok) grp[g].push_back(i);
+  }
+  const size_t G = grp.size();
+  // Inside a clock group the nodes go into blocks by their healthy frees: sorted on a
+  // Z-order key of hfs[0], hfs[1], hfs[3], hfs[7] (the frees that PodFitsMemory compares
+  // for 1, 2, 4, 8 GPUs; hfs[15] too at K = 16), so that a block's nodes are alike and its
+  // bounds decide it for a whole wave (tools: 16 % of (wave, block)s undecided on config 3
+  // with the blocks as uploaded, 4 % sorted); the sorted blocks are then taken in
+  // bit-reversed order, so that any run of consecutive blocks -- a node chunk -- still
+  // samples every free level (the chunks stay even).
+  // Not with memory ranks: there the rank-space K2 ran slower on the sorted blocks
+  // (memory in bytes: 1.91 vs 1.80 ms, profiles/r05/y/ab.txt).
+  static const bool zorder_env = YODA_KNOB("YODA_NODE_ZORDER", 1) != 0;  // A/B knob
+  // (YODA_ZORDER_RANKS=1, A/B knob: with memory ranks too)
+  static const bool zorder_ranks = YODA_KNOB("YODA_ZORDER_RANKS", 0) != 0;
+  if (ok && zorder_env && (!ranks || zorder_ranks)) {
+    std::vector<uint32_t> hix;
+    for (uint32_t t = 1; t <= (uint32_t)K; t <<= 1) hix.push_back(t - 1);
+    const uint32_t nc = (uint32_t)hix.size(), bits = 64 / nc > 16 ? 16 : 64 / nc;
+    std::vector<std::pair<uint64_t, uint32_t>> zk;
+    for (auto& g : grp) {
+      uint32_t mx[8] = {};
+      for (uint32_t i : g)
+        for (uint32_t c = 0; c < nc; ++c)
+          mx[c] = std::max(mx[c], sum[(size_t)i * SW + kSumHfs + hix[c]]);
+      zk.clear();
+      for (uint32_t i : g) {
+        uint64_t z = 0;
+        for (uint32_t c = 0; c < nc; ++c) {
+          const uint64_t v = sum[(size_t)i * SW + kSumHfs + hix[c]];
+          const uint64_t qv = mx[c] ? std::min<uint64_t>((v << bits) / ((uint64_t)mx[c] + 1),
+                                                         (1ull << bits) - 1) : 0;
+          for (uint32_t b = 0; b < bits; ++b) z |= ((qv >> b) & 1ull) << (b * nc + c);
+        }
+        zk.emplace_back(z, i);
+      }
+      std::stable_sort(zk.begin(), zk.end(), [](const std::pair<uint64_t, uint32_t>& a,
+                                                const std::pair<uint64_t, uint32_t>& b) {
+        return a.first < b.first;
+      });
+      const size_t nbg = g.size() / 64;
+      size_t lg = 0;
+      while (((size_t)1 << lg) < nbg) ++lg;
+      std::vector<uint32_t> out;
+      out.reserve(g.size());
+      for (size_t j = 0; j < ((size_t)1 << lg); ++j) {  // bit-reversed block order
+        size_t r = 0;
+        for (size_t b = 0; b < lg; ++b) r |= ((j >> b) & 1u) << (lg - 1 - b);
+        if (r < nbg)
+          for (size_t k = 0; k < 64; ++k) out.push_back(zk[r * 64 + k].second);
+      }
+      for (size_t k = nbg * 64; k < g.size(); ++k) out.push_back(zk[k].second);
+      g.swap(out);
+    }
+  }
+  if (ok && G >= 1) {
+    std::vector<size_t> nb(G), done(G, 0);
+    size_t total = 0;
+    for (size_t g = 0; g < G; ++g) total += (nb[g] = grp[g].size() / 64);
+    nperm.reserve(N);
+    for (size_t b = 0; b < total; ++b) {
+      size_t best = G;
+      double bt = 0.0;
+      for (size_t g = 0; g < G; ++g) {
+        if (done[g] == nb[g]) continue;
+        const double t = (done[g] + 0.5) / (double)nb[g];
+        if (best == G || t < bt) best = g, bt = t;
+      }
+      const size_t o = done[best]++ * 64;
+      nperm.insert(nperm.end(), grp[best].begin() + o, grp[best].begin() + o + 64);
+    }
+    for (size_t g = 0; g < G; ++g)
+      nperm.insert(nperm.end(), grp[g].begin() + done[g] * 64, grp[g].end());
+    if (nperm.size() != N) nperm.clear();
+  }
+  return nperm;
+}
+
+// Node-major rows -> 64-node tiles (sum_index, yoda_layout.h); position q of the result holds
+// the row of node order[q] (order == nullptr: of node q).
+void tile_rows(const std::vector<uint32_t>& v, uint32_t stride, uint32_t N, const uint32_t* order,
+               std::vector<uint32_t>& t) {
+  t.assign(sum_words(std::max<uint32_t>(N, 1), stride), 0u);
+  const uint32_t W = stride / 4u;
+  for (uint32_t q = 0; q < N; ++q) {
+    const uint32_t* r = v.data() + (size_t)(order ? order[q] : q) * W;
+    for (uint32_t w = 0; w < W; ++w) t[sum_index(q, w, stride)] = r[w];
+  }
+}
+
+// The packed tables tiled and copied to the device: in snapshot order, and with a grouped order
+// (nperm not empty) in that order too, with the order itself (perm_ids) and its inverse.  The
+// copies are asynchronous: `staged` holds their host sides and must outlive the caller's
+// synchronisation.  The tiled K2 summaries of the snapshot order are the handle's host mirror.
+int upload_sum_tables(yoda_t* h, const PackedRows& rows, const std::vector<uint32_t>& nperm,
+                      std::vector<std::vector<uint32_t>>& staged) {
+  const uint32_t N = h->n_nodes;
+  auto put = [&](DevBuf& d, const std::vector<uint32_t>& v) -> int {
+    HIP_TRY(h, d.ensure(v.size() * 4));
+    HIP_TRY(h, hipMemcpyAsync(d.p, v.data(), v.size() * 4, hipMemcpyHostToDevice, h->stream));
+    return YODA_OK;
+  };
+  const std::vector<uint32_t>* src[kPackedTables] = {&rows.sum, &rows.sum2, &rows.mix, &rows.x1};
+  const auto tabs = sum_tables(h->K);
+  staged.assign(2 * kPackedTables + 1, {});
+  for (int k = 0; k < kPackedTables; ++k) {
+    std::vector<uint32_t>& t = tabs[k].base == &yoda_handle::k2sum ? h->host_k2sum : staged[2 * k];
+    tile_rows(*src[k], tabs[k].stride, N, nullptr, t);
+    if (int rc = put(h->*tabs[k].base, t)) return rc;
+    if (nperm.empty()) continue;
+    tile_rows(*src[k], tabs[k].stride, N, nperm.data(), staged[2 * k + 1]);
+    if (int rc = put(h->*tabs[k].grouped, staged[2 * k + 1])) return rc;
+  }
+  if (!nperm.empty()) {
+    std::vector<uint32_t>& inv = staged[2 * kPackedTables];
+    inv.resize(N);
+    for (uint32_t q = 0; q < N; ++q) inv[nperm[q]] = q;
+    if (int rc = put(h->perm_ids, nperm)) return rc;
+    if (int rc = put(h->perm_inv, inv)) return rc;
+  }
+  return YODA_OK;
+}
+
+// The block summaries of the snapshot order and of the block-grouped copy's (BlockSumWord),
+// built from the tables already enqueued.  k_bsum_build writes the real blocks only and DevBuf
+// is grow-only, so the tile padding is cleared first: it may hold an older, larger snapshot's
+// words, which yoda_snapshot_check would compare.
+int upload_block_sums(yoda_t* h) {
+  const size_t bytes =
+      sum_words(std::max<uint32_t>((h->n_nodes + 63) / 64, 1), bsum_stride(h->K)) * 4;
+  HIP_TRY(h, h->blksum.ensure(bytes));
+  HIP_TRY(h, hipMemsetAsync(h->blksum.p, 0, bytes, h->stream));
+  if (h->perm_on) {
+    HIP_TRY(h, h->blksum_p.ensure(bytes));
+    HIP_TRY(h, hipMemsetAsync(h->blksum_p.p, 0, bytes, h->stream));
+  }
+  return rebuild_block_sums(h);
+}
+
+// The G table: per field the max over every real card (floor 1, collection.go:31-38),
+// the CollectMaxValues result of any pod feasible on the maximal cards' nodes; with memory
+// ranks the value tables the kernels read the memory fields through (h->mt).
+int upload_gtables(yoda_t* h, const yoda_node_soa* nd, const MemCodes& mc) {
+  const uint32_t N = nd->n_nodes, KS = nd->max_cards;
+  uint64_t gmax[6] = {1, 1, 1, 1, 1, 1};
+  for (uint32_t i = 0; i < N; ++i)
+    for (uint32_t j = 0; j < nd->card_count[i]; ++j) {
+      const size_t k = (size_t)i * KS + j;
+      gmax[kMaxBw] = std::max(gmax[kMaxBw], nd->card_bandwidth[k]);
+      gmax[kMaxClock] = std::max(gmax[kMaxClock], nd->card_clock[k]);
+      gmax[kMaxCore] = std::max(gmax[kMaxCore], nd->card_core[k]);
+      gmax[kMaxFree] = std::max(gmax[kMaxFree], nd->card_free_memory[k]);
+      gmax[kMaxPower] = std::max(gmax[kMaxPower], nd->card_power[k]);
+      gmax[kMaxTotal] = std::max(gmax[kMaxTotal], nd->card_total_memory[k]);
+    }
+  const size_t tab_bytes = sum_words(std::max<uint32_t>(N, 1), gtab_stride(h->K)) * 4;
+  HIP_TRY(h, h->gtab.ensure(tab_bytes));
+  if (h->perm_on) HIP_TRY(h, h->gtab_p.ensure(tab_bytes));  // (the same rows, reordered)
+  std::memcpy(h->h_gmax, gmax, sizeof(gmax));
+  HIP_TRY(h, h->gtab_aux.ensure(kGTabAuxBytes));
+  HIP_TRY(h, hipMemcpyAsync(h->gtab_aux.p, h->h_gmax, sizeof(h->h_gmax), hipMemcpyHostToDevice,
+                            h->stream));
+  h->mt = MemTab{};
+  if (mc.ranks) {  // value tables: v[0] = v[1] = 0, v[2 + i] = the i-th distinct value
+    std::vector<double> vt(4 + mc.frees.size() + mc.totals.size(), 0.0);
+    for (size_t i = 0; i < mc.frees.size(); ++i) vt[2 + i] = (double)mc.frees[i];
+    for (size_t i = 0; i < mc.totals.size(); ++i) vt[4 + mc.frees.size() + i] = (double)mc.totals[i];
+    HIP_TRY(h, h->memtab.ensure(vt.size() * 8));
+    HIP_TRY(h, hipMemcpy(h->memtab.p, vt.data(), vt.size() * 8, hipMemcpyHostToDevice));
+    h->mt.vf = h->memtab.as<double>();
+    h->mt.vt = h->memtab.as<double>() + 2 + mc.frees.size();
+    h->mt.nf = (uint32_t)mc.frees.size();
+  }
+  return relaunch_gtables(h);
+}
+
+// The blocks whose bound with every card qualifying (lv[0]) is in the top tenth, per order: a
+// static visiting order hint for the argmax K2 (results do not depend on it).
+int build_hot_masks(yoda_t* h) {
+  const int K = h->K;
+  const uint32_t nb = (h->n_nodes + 63) / 64, KST = kbub_stride(K);
+  std::vector<uint32_t> ubw(sum_words(nb, KST));
+  std::vector<uint64_t> words((nb + 63) / 64), words_p((nb + 63) / 64);
+  auto hot_bits = [&](const DevBuf& src, std::vector<uint64_t>& out) -> int {
+    HIP_TRY(h, hipMemcpyAsync(ubw.data(), src.p, ubw.size() * 4, hipMemcpyDeviceToHost,
+                              h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    std::vector<double> u(nb);
+    for (uint32_t b = 0; b < nb; ++b) {
+      const uint64_t bits = (uint64_t)ubw[sum_index(b, kbub_lvl(K), KST)] |
+                            ((uint64_t)ubw[sum_index(b, kbub_lvl(K) + 1u, KST)] << 32);
+      std::memcpy(&u[b], &bits, 8);
+    }
+    std::vector<double> srt(u);
+    const size_t q = srt.size() - 1 - srt.size() / 10;
+    std::nth_element(srt.begin(), srt.begin() + q, srt.end());
+    const double thr = srt[q];
+    std::fill(out.begin(), out.end(), 0ull);
+    for (uint32_t b = 0; b < nb; ++b)
+      if (u[b] >= thr) out[b >> 6] |= 1ull << (b & 63);
+    return YODA_OK;
+  };
+  int hr = hot_bits(h->kbub, words);
+  if (!hr && h->perm_on) hr = hot_bits(h->kbub_p, words_p);
+  if (hr) return hr;
+  HIP_TRY(h, h->hot.ensure(words.size() * 8));
+  HIP_TRY(h, hipMemcpy(h->hot.p, words.data(), words.size() * 8, hipMemcpyHostToDevice));
+  if (h->perm_on) {
+    HIP_TRY(h, h->hot_p.ensure(words_p.size() * 8));
+    HIP_TRY(h, hipMemcpy(h->hot_p.p, words_p.data(), words_p.size() * 8,
+                         hipMemcpyHostToDevice));
+  }
+  h->hot_ok = true;
+  return YODA_OK;
+}
 
 }  // namespace
 
@@ -1935,544 +2462,56 @@ int yoda_synchronize(yoda_t* h) {
 int yoda_upload_nodes(yoda_t* h, const yoda_node_soa* nd, uint32_t node_offset, uint32_t flags) {
   if (!h) return YODA_ERR_INVALID_ARG;
   try {
-    if (!nd) return fail(h, YODA_ERR_INVALID_ARG, "nodes is NULL");
-    const uint32_t N = nd->n_nodes, KS = nd->max_cards;
     h->topk_ready = false;
-    if (KS < 1 || KS > YODA_MAX_CARDS)
-      return fail(h, YODA_ERR_INVALID_ARG, "max_cards must be in 1..16");
-    if (N > 0 && (!nd->card_number || !nd->card_count || !nd->free_memory_sum ||
-                  !nd->total_memory_sum || !nd->card_free_memory || !nd->card_total_memory ||
-                  !nd->card_clock || !nd->card_bandwidth || !nd->card_core || !nd->card_power ||
-                  !nd->card_healthy))
-      return fail(h, YODA_ERR_INVALID_ARG, "a required node array is NULL");
-    if ((uint64_t)node_offset + N > 0x7fffffffull)
-      return fail(h, YODA_ERR_RANGE, "node index exceeds int32");
-    HIP_TRY(h, hipSetDevice(h->device));
     uint32_t kmax = 1;
-    for (uint32_t i = 0; i < N; ++i) {
-      if (nd->card_count[i] > KS) return fail(h, YODA_ERR_INVALID_ARG, "card_count > max_cards");
-      kmax = std::max(kmax, nd->card_count[i]);
-    }
-    const int K = pow2_cards(kmax);
-    // Record format: the narrowest exact one.
-    std::vector<uint64_t> stat(N);
-    std::vector<uint8_t> zt(N);
-    uint64_t max_field = 0, max_small = 0, max_clock = 0, max_static = 0, max_mem = 0;
-    uint64_t max_ckq = 0;  // the largest clock quotient a card can score
-    bool all_one = true;   // every node one GPU model with one TotalMemory
-    for (uint32_t i = 0; i < N; ++i) {
-      bool z = false;
-      const uint64_t alloc = nd->alloc_memory ? nd->alloc_memory[i] : 0;
-      stat[i] = static_score(nd->free_memory_sum[i], nd->total_memory_sum[i], alloc, &z);
-      zt[i] = z;
-      max_static = std::max(max_static, stat[i]);
-      for (uint32_t j = 0; j < nd->card_count[i]; ++j) {
-        const size_t k = (size_t)i * KS + j;
-        max_field = std::max({max_field, nd->card_free_memory[k], nd->card_total_memory[k],
-                              nd->card_clock[k], nd->card_bandwidth[k], nd->card_core[k],
-                              nd->card_power[k]});
-        max_small = std::max({max_small, nd->card_bandwidth[k], nd->card_core[k],
-                              nd->card_power[k], nd->card_clock[k]});
-        max_mem = std::max({max_mem, nd->card_free_memory[k], nd->card_total_memory[k]});
-        max_clock = std::max(max_clock, nd->card_clock[k]);
-        // clock / MaxBandwidth (algorithm.go:283): a scored card qualifies, so MaxBandwidth is
-        // at least its own bandwidth (and 1)
-        if (nd->card_clock[k] <= kN32FieldMax)
-          max_ckq = std::max(max_ckq, nd->card_clock[k] * 100u /
-                                          std::max<uint64_t>(1, nd->card_bandwidth[k]));
-      }
-      // one GPU model with one TotalMemory (the mixed-model K1 tiles pack small fields in 16 bits)
-      const size_t a = (size_t)i * KS;
-      bool one = nd->card_count[i] > 0 && !(flags & YODA_UPLOAD_NO_UNIFORM);
-      for (uint32_t j = 1; j < nd->card_count[i] && one; ++j)
-        one = nd->card_clock[a + j] == nd->card_clock[a] &&
-              nd->card_bandwidth[a + j] == nd->card_bandwidth[a] &&
-              nd->card_core[a + j] == nd->card_core[a] && nd->card_power[a + j] == nd->card_power[a] &&
-              nd->card_total_memory[a + j] == nd->card_total_memory[a];
-      all_one = all_one && one;
-    }
-    // per-card score <= 800 + 100*clock (five quotients <= 100, clock/MaxBandwidth <= 100*clock)
-    const long double score_bound =
-        (long double)K * (800.0L + 100.0L * (long double)max_clock) + (long double)max_static;
-    const bool f64_ok = max_field <= kFastFieldMax && score_bound < (long double)kFastScoreMax;
-    {
-      uint64_t max_actual = 0;  // Actual does not depend on the allocated memory
-      for (uint32_t i = 0; i < N; ++i)
-        if (nd->total_memory_sum[i] != 0)
-          max_actual = std::max(max_actual,
-                                nd->free_memory_sum[i] * 100u / nd->total_memory_sum[i] * 2u);
-      const long double b = (long double)K * (800.0L + 100.0L * (long double)max_clock) + 300.0L +
-                            (long double)max_actual;
-      h->score_bound = b < 9.0e18L ? (uint64_t)b + 1u : ~0ull;
-      // (yoda_update_node_cards raises the Actual term with the nodes' new FreeMemorySum)
-      h->sb_cards = (long double)K * (800.0L + 100.0L * (long double)max_clock) + 300.0L;
-      h->sb_actual = max_actual;
-    }
-    // N32: every small card field in u32, every quotient exact in f64 (x, M < 2^32: 300 x + M
-    // < 2^53) -- the block K2 keeps the small-field quotients in f32 while those fields are
-    // <= kF32SmallMax (q32) -- the card score summed in u32: per card at most 800 + the clock
-    // quotient.  Small fields beyond that need one-model nodes (the mixed-model K1 tiles pack
-    // them in 16 bits, and the f64 block K2 is instantiated without the mixed-model rows); beyond
-    // 16 bits the K1 writes unpacked partial words (kWideWords).  Memory fields beyond 32 bits (e.g.
-    // bytes) keep the N32 path with memory RANKS in the u32 fields (yoda_layout.h MemTab):
-    // every compare and max is unchanged, the values come back for the quotients and the
-    // maxima (all <= 2^44: exact in f64).
-    const bool pack16 = max_small <= kPack16Max;
-    const bool q32 = max_small <= kF32SmallMax && !(flags & YODA_UPLOAD_F64_QUOTIENTS);
-    const bool n32_ok = f64_ok && max_small <= kN32FieldMax && (q32 || all_one) &&
-                        (uint64_t)K * (800u + max_ckq) < (1ull << 32);
-    Path path = n32_ok ? Path::N32 : (f64_ok ? Path::F64 : Path::U64);
-    if ((flags & YODA_UPLOAD_FORCE_F64) && path == Path::N32) path = Path::F64;
-    if (flags & YODA_UPLOAD_FORCE_GENERIC) path = Path::U64;
-    const bool ranks = path == Path::N32 &&
-                       (max_mem > kN32FieldMax || (flags & YODA_UPLOAD_MEM_RANKS) != 0u);
-    std::vector<uint64_t> frees, totals;  // distinct values, ascending (ranks)
-    if (ranks) {
-      for (uint32_t i = 0; i < N; ++i)
-        for (uint32_t j = 0; j < nd->card_count[i]; ++j) {
-          frees.push_back(nd->card_free_memory[(size_t)i * KS + j]);
-          totals.push_back(nd->card_total_memory[(size_t)i * KS + j]);
-        }
-      for (auto* v : {&frees, &totals}) {
-        std::sort(v->begin(), v->end());
-        v->erase(std::unique(v->begin(), v->end()), v->end());
-      }
-    }
-    // the u32 code of a card's FreeMemory / TotalMemory: its value, or 2 + its rank
-    auto code_f = [&](uint64_t x) -> uint32_t {
-      if (!ranks) return (uint32_t)x;
-      return 2u + (uint32_t)(std::lower_bound(frees.begin(), frees.end(), x) - frees.begin());
-    };
-    auto code_t = [&](uint64_t x) -> uint32_t {
-      if (!ranks) return (uint32_t)x;
-      return 2u + (uint32_t)(std::lower_bound(totals.begin(), totals.end(), x) - totals.begin());
-    };
-    // Build records.
-    const size_t stride = path == Path::N32 ? n32_stride(K) : node_stride(K);
-    std::vector<unsigned char> rec((size_t)std::max<uint32_t>(N, 1) * stride, 0);
-    // K1 node summaries (N32 path): the facts the block-classified K1 reads per node
+    if (int rc = check_node_soa(h, nd, node_offset, &kmax)) return rc;
+    const uint32_t N = nd->n_nodes;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int K = pow2_cards(kmax);  // 1, 2, 4, 8 or 16
+    // Host side: the format, the memory codes, every node's rows.
+    const UploadFormat fmt = choose_format(nd, K, flags);
+    MemCodes mc = build_mem_codes(nd, fmt.ranks);
+    PackedRows rows = pack_rows(nd, fmt, mc, flags);
+    const Path path = fmt.path;
     const bool want_sum = path == Path::N32;
-    uint32_t g_rcp[10] = {};  // the G table's reciprocals, read back from the device
-    const size_t sstride = k1sum_stride(K);
-    std::vector<uint32_t> sum(want_sum ? (size_t)std::max<uint32_t>(N, 1) * sstride / 4 : 0, 0);
-    const size_t s2stride = k2sum_stride(K);
-    std::vector<uint32_t> sum2(want_sum ? (size_t)std::max<uint32_t>(N, 1) * s2stride / 4 : 0, 0);
-    const size_t mstride = mix_stride(K);
-    std::vector<uint32_t> mix(want_sum ? (size_t)std::max<uint32_t>(N, 1) * mstride / 4 : 0, 0);
-    uint32_t n_one_model = 0, n_uni4 = 0;
-    // per node: the clocks of its real cards and of its healthy cards, min / max (block sums)
-    std::vector<uint32_t> clk_rng(want_sum ? 4 * (size_t)N : 0);
-    const size_t xstride = x1_stride(K);
-    std::vector<uint32_t> x1m(want_sum ? (size_t)std::max<uint32_t>(N, 1) * xstride / 4 : 0, 0);
-    for (uint32_t i = 0; i < N; ++i) {
-      // the node's rows, packed by the one per-node packer (yoda_node_pack.h)
-      const size_t a = (size_t)i * KS;
-      const uint32_t cnt = nd->card_count[i];
-      uint32_t fc[YODA_MAX_CARDS], tc[YODA_MAX_CARDS];
-      if (path == Path::N32)
-        for (uint32_t j = 0; j < cnt; ++j) {
-          fc[j] = code_f(nd->card_free_memory[a + j]);
-          tc[j] = code_t(nd->card_total_memory[a + j]);
-        }
-      NodePackIn in;
-      in.cnt = cnt;
-      in.card_number = nd->card_number[i];
-      in.stat = stat[i];
-      in.zero_total = zt[i] != 0;
-      in.no_uniform = (flags & YODA_UPLOAD_NO_UNIFORM) != 0u;
-      in.free_memory = nd->card_free_memory + a;
-      in.total_memory = nd->card_total_memory + a;
-      in.clock = nd->card_clock + a;
-      in.bandwidth = nd->card_bandwidth + a;
-      in.core = nd->card_core + a;
-      in.power = nd->card_power + a;
-      in.healthy = nd->card_healthy + a;
-      in.fcode = fc;
-      in.tcode = tc;
-      NodePackOut out;
-      out.zeroed = true;  // (the vectors above: value-initialised, each row packed once)
-      out.rec = rec.data() + (size_t)i * stride;
-      if (want_sum) {
-        out.sum = sum.data() + (size_t)i * sstride / 4;
-        out.sum2 = sum2.data() + (size_t)i * s2stride / 4;
-        out.mix = mix.data() + (size_t)i * mstride / 4;
-        out.x1 = x1m.data() + (size_t)i * xstride / 4;
-        out.clk_rng = clk_rng.data() + 4 * (size_t)i;
-      }
-      const uint32_t nf = pack_node(path, K, in, out);
-      n_one_model += (nf & (kNodeUniform4 | kNodeUniformTotal)) ==
-                     (kNodeUniform4 | kNodeUniformTotal);
-      n_uni4 += (nf & kNodeUniform4) != 0u;
-    }
-    HIP_TRY(h, h->nodes.ensure(rec.size()));
-    HIP_TRY(h, hipMemcpyAsync(h->nodes.p, rec.data(), rec.size(), hipMemcpyHostToDevice,
+    // From here on the handle describes the new snapshot: the table builders below read K,
+    // n_nodes, perm_on and the memory ranks from it.  A call that fails on the way leaves no
+    // snapshot.
+    h->has_nodes = false;
+    h->score_bound = fmt.score_bound;
+    h->sb_cards = fmt.sb_cards;
+    h->sb_actual = fmt.sb_actual;
+    if (h->K != K || h->path != path) std::memset(h->cap, 0, sizeof(h->cap));
+    h->K = K;
+    h->path = path;
+    h->generic = path == Path::U64;
+    h->n_nodes = N;
+    h->node_offset = node_offset;
+    h->mem_ranks = fmt.ranks;
+    h->mt = MemTab{};
+    h->pack16 = fmt.pack16;
+    h->q32 = fmt.q32;
+    h->small_max = fmt.max_small;
+    h->perm_on = false;
+    h->host_k2sum.clear();
+    HIP_TRY(h, h->nodes.ensure(rows.rec.size()));
+    HIP_TRY(h, hipMemcpyAsync(h->nodes.p, rows.rec.data(), rows.rec.size(), hipMemcpyHostToDevice,
                               h->stream));
-    if (want_sum) {  // node-major as built -> 64-node tiles (sum_index, yoda_layout.h)
-      auto tiles = [N](const std::vector<uint32_t>& v, uint32_t stride) {
-        std::vector<uint32_t> t(sum_words(std::max<uint32_t>(N, 1), stride), 0u);
-        const uint32_t W = stride / 4u;
-        for (uint32_t i = 0; i < N; ++i)
-          for (uint32_t w = 0; w < W; ++w) t[sum_index(i, w, stride)] = v[(size_t)i * W + w];
-        return t;
-      };
-      // Block-grouped node order for the private batch runs (node order): a
-      // snapshot of one-model nodes is dealt into 64-node blocks of one clock each (PodFitsClock
-      // then rules whole blocks out for a clock-labelled wave, and K2 skips them), whole blocks
-      // round-robin in proportion to each clock's block count so that every node chunk keeps
-      // the snapshot's mix, the groups' remainders last.  Copies of the K1 / K2 summaries in
-      // that order; the kernels compare the nodes' local ids (perm_ids) on score ties.
-      h->perm_on = false;
-      static const bool perm_env = YODA_KNOB("YODA_NODE_PERM", 1) != 0;
-      std::vector<uint32_t> nperm;
-      // Mixed-model nodes (cards of several GPU models) form a group of their own, so that
-      // the one-model nodes still fill one-model blocks, which the block summaries decide
-      // whole (50 % mixed-model nodes: every block mixed without it).  YODA_NODE_PERM_MIXED=0
-      // (A/B knob): one-model snapshots only, as in round 5.
-      static const bool perm_mixed = YODA_KNOB("YODA_NODE_PERM_MIXED", 1) != 0;
-      if (perm_env && path == Path::N32 && (n_one_model == N || perm_mixed) && N >= 4096 &&
-          !(flags & YODA_UPLOAD_PER_NODE_K1) && !(flags & YODA_UPLOAD_PER_NODE_K2)) {
-        const uint32_t SW = (uint32_t)(sstride / 4);
-        std::vector<uint32_t> keys;
-        std::vector<std::vector<uint32_t>> grp;
-        bool ok = true;
-        for (uint32_t i = 0; i < N && ok; ++i) {
-          // (a mixed-model node's kSumClock is its first card's: the key of its group is ~0)
-          const uint32_t ck = (sum[(size_t)i * SW + kSumMeta] & kSumUni4)
-                                  ? sum[(size_t)i * SW + kSumClock] : 0xffffffffu;
-          size_t g = 0;
-          while (g < keys.size() && keys[g] != ck) ++g;
-          if (g == keys.size()) {
-            if (keys.size() == 64) ok = false;  // too many clocks to group usefully
-            keys.push_back(ck);
-            grp.emplace_back();
-          }
-          if (ok) grp[g].push_back(i);
-        }
-        const size_t G = grp.size();
-        // Inside a clock group the nodes go into blocks by their healthy frees: sorted on a
-        // Z-order key of hfs[0], hfs[1], hfs[3], hfs[7] (the frees that PodFitsMemory compares
-        // for 1, 2, 4, 8 GPUs; hfs[15] too at K = 16), so that a block's nodes are alike and its
-        // bounds decide it for a whole wave (tools: 16 % of (wave, block)s undecided on config 3
-        // with the blocks as uploaded, 4 % sorted); the sorted blocks are then taken in
-        // bit-reversed order, so that any run of consecutive blocks -- a node chunk -- still
-        // samples every free level (the chunks stay even).
-        // Not with memory ranks: there the rank-space K2 ran slower on the sorted blocks
-        // (memory in bytes: 1.91 vs 1.80 ms, profiles/r05/y/ab.txt).
-        static const bool zorder_env = YODA_KNOB("YODA_NODE_ZORDER", 1) != 0;  // A/B knob
-        // (YODA_ZORDER_RANKS=1, A/B knob: with memory ranks too)
-        static const bool zorder_ranks = YODA_KNOB("YODA_ZORDER_RANKS", 0) != 0;
-        if (ok && zorder_env && (!ranks || zorder_ranks)) {
-          std::vector<uint32_t> hix;
-          for (uint32_t t = 1; t <= (uint32_t)K; t <<= 1) hix.push_back(t - 1);
-          const uint32_t nc = (uint32_t)hix.size(), bits = 64 / nc > 16 ? 16 : 64 / nc;
-          std::vector<std::pair<uint64_t, uint32_t>> zk;
-          for (auto& g : grp) {
-            uint32_t mx[8] = {};
-            for (uint32_t i : g)
-              for (uint32_t c = 0; c < nc; ++c)
-                mx[c] = std::max(mx[c], sum[(size_t)i * SW + kSumHfs + hix[c]]);
-            zk.clear();
-            for (uint32_t i : g) {
-              uint64_t z = 0;
-              for (uint32_t c = 0; c < nc; ++c) {
-                const uint64_t v = sum[(size_t)i * SW + kSumHfs + hix[c]];
-                const uint64_t qv = mx[c] ? std::min<uint64_t>((v << bits) / ((uint64_t)mx[c] + 1),
-                                                               (1ull << bits) - 1) : 0;
-                for (uint32_t b = 0; b < bits; ++b) z |= ((qv >> b) & 1ull) << (b * nc + c);
-              }
-              zk.emplace_back(z, i);
-            }
-            std::stable_sort(zk.begin(), zk.end(), [](const std::pair<uint64_t, uint32_t>& a,
-                                                      const std::pair<uint64_t, uint32_t>& b) {
-              return a.first < b.first;
-            });
-            const size_t nbg = g.size() / 64;
-            size_t lg = 0;
-            while (((size_t)1 << lg) < nbg) ++lg;
-            std::vector<uint32_t> out;
-            out.reserve(g.size());
-            for (size_t j = 0; j < ((size_t)1 << lg); ++j) {  // bit-reversed block order
-              size_t r = 0;
-              for (size_t b = 0; b < lg; ++b) r |= ((j >> b) & 1u) << (lg - 1 - b);
-              if (r < nbg)
-                for (size_t k = 0; k < 64; ++k) out.push_back(zk[r * 64 + k].second);
-            }
-            for (size_t k = nbg * 64; k < g.size(); ++k) out.push_back(zk[k].second);
-            g.swap(out);
-          }
-        }
-        if (ok && G >= 1) {
-          std::vector<size_t> nb(G), done(G, 0);
-          size_t total = 0;
-          for (size_t g = 0; g < G; ++g) total += (nb[g] = grp[g].size() / 64);
-          nperm.reserve(N);
-          for (size_t b = 0; b < total; ++b) {
-            size_t best = G;
-            double bt = 0.0;
-            for (size_t g = 0; g < G; ++g) {
-              if (done[g] == nb[g]) continue;
-              const double t = (done[g] + 0.5) / (double)nb[g];
-              if (best == G || t < bt) best = g, bt = t;
-            }
-            const size_t o = done[best]++ * 64;
-            nperm.insert(nperm.end(), grp[best].begin() + o, grp[best].begin() + o + 64);
-          }
-          for (size_t g = 0; g < G; ++g)
-            nperm.insert(nperm.end(), grp[g].begin() + done[g] * 64, grp[g].end());
-          h->perm_on = nperm.size() == N;
-        }
-      }
-      if (h->perm_on) {
-        const uint32_t SW = (uint32_t)(sstride / 4), S2W = (uint32_t)(s2stride / 4);
-        std::vector<uint32_t> sp((size_t)N * SW), s2p((size_t)N * S2W), inv(N);
-        const uint32_t MW = (uint32_t)(mstride / 4), XW = (uint32_t)(xstride / 4);
-        std::vector<uint32_t> mp((size_t)N * MW), xp((size_t)N * XW);
-        for (uint32_t q = 0; q < N; ++q) {
-          const uint32_t i = nperm[q];
-          std::memcpy(sp.data() + (size_t)q * SW, sum.data() + (size_t)i * SW, SW * 4);
-          std::memcpy(s2p.data() + (size_t)q * S2W, sum2.data() + (size_t)i * S2W, S2W * 4);
-          std::memcpy(mp.data() + (size_t)q * MW, mix.data() + (size_t)i * MW, MW * 4);
-          std::memcpy(xp.data() + (size_t)q * XW, x1m.data() + (size_t)i * XW, XW * 4);
-          inv[i] = q;
-        }
-        sp = tiles(sp, (uint32_t)sstride);
-        s2p = tiles(s2p, (uint32_t)s2stride);
-        mp = tiles(mp, (uint32_t)mstride);
-        xp = tiles(xp, (uint32_t)xstride);
-        HIP_TRY(h, h->kmix_p.ensure(mp.size() * 4));
-        HIP_TRY(h, h->kx1_p.ensure(xp.size() * 4));
-        HIP_TRY(h, hipMemcpyAsync(h->kmix_p.p, mp.data(), mp.size() * 4, hipMemcpyHostToDevice,
-                                  h->stream));
-        HIP_TRY(h, hipMemcpyAsync(h->kx1_p.p, xp.data(), xp.size() * 4, hipMemcpyHostToDevice,
-                                  h->stream));
-        HIP_TRY(h, h->k1sum_p.ensure(sp.size() * 4));
-        HIP_TRY(h, h->k2sum_p.ensure(s2p.size() * 4));
-        HIP_TRY(h, h->perm_ids.ensure((size_t)N * 4));
-        HIP_TRY(h, h->perm_inv.ensure((size_t)N * 4));
-        HIP_TRY(h, hipMemcpyAsync(h->k1sum_p.p, sp.data(), sp.size() * 4, hipMemcpyHostToDevice,
-                                  h->stream));
-        HIP_TRY(h, hipMemcpyAsync(h->k2sum_p.p, s2p.data(), s2p.size() * 4,
-                                  hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(h->perm_ids.p, nperm.data(), (size_t)N * 4,
-                                  hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(h->perm_inv.p, inv.data(), (size_t)N * 4,
-                                  hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));  // (the host copies go out of scope)
-      }
-      // block summaries of the snapshot order and of the block-grouped copy's (BlockSumWord)
-      {
-        const uint32_t SW = (uint32_t)(sstride / 4);
-        auto bsums = [&](const uint32_t* order) {
-          const uint32_t nb = (N + 63) / 64, BW = bsum_stride(K) / 4;
-          std::vector<uint32_t> b(sum_words(std::max<uint32_t>(nb, 1), bsum_stride(K)), 0u);
-          std::vector<uint32_t> o(BW);
-          for (uint32_t blk = 0; blk < nb; ++blk) {
-            std::fill(o.begin(), o.end(), 0u);
-            uint64_t cmin = ~0ull, cmax = 0;
-            uint32_t fl = kBsOneModel | kBsUni4, ckmin = ~0u, ckmax = 0, hmin = ~0u, hmax = 0;
-            uint32_t nhmin = ~0u, nhmax = 0, mrmin = ~0u, mrmax = 0, nreal = 0, nzt = 0;
-            uint32_t mx[6] = {0, 0, 0, 0, 0, 0}, wc[6] = {0, 0, 0, 0, 0, 0};
-            uint32_t wl[6] = {~0u, ~0u, ~0u, ~0u, ~0u, ~0u};
-            uint32_t tmin[YODA_MAX_CARDS], tmax[YODA_MAX_CARDS];
-            for (int t = 0; t < K; ++t) tmin[t] = ~0u, tmax[t] = 0;
-            uint32_t sat = ~0u;
-            // the healthy-card clocks of the block's nodes: clock, min / max count over the
-            // nodes seen so far (a node without the clock counts 0: hc_seen tracks it)
-            uint32_t hc_clk[4] = {0, 0, 0, 0}, hc_lo[4] = {0, 0, 0, 0}, hc_hi[4] = {0, 0, 0, 0};
-            uint32_t n_hc = 0;
-            bool hc_ok = true;
-            for (uint32_t l = 0; l < 64 && blk * 64 + l < N; ++l) {
-              const uint32_t i = order ? order[blk * 64 + l] : blk * 64 + l;
-              const uint32_t* w = sum.data() + (size_t)i * SW;
-              const uint64_t cn = (uint64_t)w[kSumCnLo] | ((uint64_t)w[kSumCnHi] << 32);
-              const uint32_t meta = w[kSumMeta], nh = (meta >> 8) & 0xffu;
-              const uint32_t* cr = clk_rng.data() + 4 * (size_t)i;
-              const uint32_t* s2n = sum2.data() + (size_t)i * (s2stride / 4);
-              const uint32_t* xn = x1m.data() + (size_t)i * (xstride / 4);
-              const uint32_t cnt = (s2n[kS2Meta] >> 8) & 0xffu;
-              const bool one = (meta & kSumUni4) && (meta & kSumUniTotal);
-              // saturation: 1 + the free of the last card (free order) where a prefix maximum
-              // changes (K1MixWord chg bits 1..K); one-model nodes of one total: card 0
-              uint32_t sat1 = w[kSumMrf1];
-              if (!one && cnt > 0) {
-                const uint32_t chg = xn[kX1Chg] & ((2u << K) - 2u);
-                const uint32_t jl = chg ? 30u - (uint32_t)__builtin_clz(chg) : 0u;  // bit jl+1
-                sat1 = s2n[kS2Fs + jl] + 1u;
-              }
-              sat = std::min(sat, sat1);
-              // healthy cards per clock (K1MixWord ch; more than 4 clocks or a clock beyond 16
-              // bits: no table)
-              if ((xn[kX1Chg] & kX1ChgMany) || (nh > 0 && cr[3] > 0xffffu)) hc_ok = false;
-              if (hc_ok) {
-                uint32_t mine[4] = {0, 0, 0, 0};  // this node's count per table entry
-                for (uint32_t e = 0; e < 4; ++e) {
-                  const uint32_t xw = xn[kX1Ch + e];
-                  if ((xw >> 16) == 0u) continue;
-                  const uint32_t ck = xw & 0xffffu;
-                  uint32_t k = 0;
-                  while (k < n_hc && hc_clk[k] != ck) ++k;
-                  if (k == n_hc) {
-                    if (n_hc == 4) { hc_ok = false; break; }
-                    hc_clk[k] = ck;
-                    hc_lo[k] = nreal == 0 ? ~0u : 0u;  // the nodes before lacked it
-                    hc_hi[k] = 0u;
-                    ++n_hc;
-                  }
-                  mine[k] = xw >> 16;
-                }
-                for (uint32_t k = 0; k < n_hc; ++k) {
-                  hc_lo[k] = std::min(hc_lo[k], mine[k]);
-                  hc_hi[k] = std::max(hc_hi[k], mine[k]);
-                }
-              }
-              ++nreal;
-              cmin = std::min(cmin, cn);
-              cmax = std::max(cmax, cn);
-              if (!(meta & kSumUni4)) fl &= ~(kBsUni4 | kBsOneModel);
-              if (!(meta & kSumUniTotal)) fl &= ~kBsOneModel;
-              if (meta & kSumZeroTotal) ++nzt;
-              ckmin = std::min(ckmin, cr[0]);
-              ckmax = std::max(ckmax, cr[1]);
-              hmin = std::min(hmin, cr[2]);
-              hmax = std::max(hmax, cr[3]);
-              nhmin = std::min(nhmin, nh);
-              nhmax = std::max(nhmax, nh);
-              mrmin = std::min(mrmin, w[kSumMrf1]);
-              mrmax = std::max(mrmax, w[kSumMrf1]);
-              const uint32_t mr = w[kSumMrf1];
-              uint32_t v[6] = {w[kSumBw], w[kSumClock], w[kSumCore], mr - (mr != 0u ? 1u : 0u),
-                               w[kSumPower], w[kSumTotal]};  // kMax* order
-              if (!one && cnt > 0) {  // the all-card maxima (K1MixWord pm over every card)
-                const uint32_t a = xn[x1_pm((int)cnt - 1, 0)], b = xn[x1_pm((int)cnt - 1, 1)];
-                if (!(meta & kSumUni4)) {  // (16-bit halves: such snapshots keep them <= 65535)
-                  v[kMaxBw] = a >> 16;
-                  v[kMaxClock] = a & 0xffffu;
-                  v[kMaxCore] = b & 0xffffu;
-                  v[kMaxPower] = b >> 16;
-                }
-                v[kMaxTotal] = xn[x1_pm((int)cnt - 1, 2)];
-              }
-              for (int f = 0; f < 6; ++f) {
-                if (wc[f] == 0 || v[f] > mx[f]) {
-                  mx[f] = v[f];
-                  wc[f] = 1;
-                  wl[f] = l;
-                } else if (v[f] == mx[f]) {
-                  ++wc[f];
-                }
-              }
-              for (int t = 0; t < K; ++t) {
-                tmin[t] = std::min(tmin[t], w[kSumHfs + t]);
-                tmax[t] = std::max(tmax[t], w[kSumHfs + t]);
-              }
-            }
-            if (nreal == 0) continue;
-            o[kBsCnMin] = (uint32_t)std::min<uint64_t>(cmin, 0xffffffffull);
-            o[kBsCnMax] = (uint32_t)std::min<uint64_t>(cmax, 0xffffffffull);
-            o[kBsFlags] = fl;
-            o[kBsCkMin] = ckmin;
-            o[kBsCkMax] = ckmax;
-            o[kBsHckMin] = hmin;
-            o[kBsHckMax] = hmax;
-            o[kBsNhMin] = nhmin;
-            o[kBsNhMax] = nhmax;
-            o[kBsMrfMin] = mrmin;
-            o[kBsMrfMax] = mrmax;
-            o[kBsNReal] = nreal;
-            o[kBsNzt] = nzt;
-            o[kBsSat] = sat;
-            if (hc_ok) {
-              o[kBsFlags] |= kBsHcTab | (n_hc << 8);
-              for (uint32_t k = 0; k < n_hc; ++k)
-                o[kBsHc + k] = hc_clk[k] | (hc_lo[k] << 16) | (hc_hi[k] << 24);
-            }
-            for (int f = 0; f < 6; ++f) {
-              o[kBsMx + f] = mx[f];
-              o[kBsWc + f] = wc[f];
-              o[kBsWl + f] = wl[f];
-            }
-            for (int t = 0; t < K; ++t) {
-              o[kBsT + t] = tmin[t];
-              o[kBsT + K + t] = tmax[t];
-            }
-            for (uint32_t w = 0; w < BW; ++w) b[sum_index(blk, w, bsum_stride(K))] = o[w];
-          }
-          return b;
-        };
-        const std::vector<uint32_t> bo = bsums(nullptr);
-        HIP_TRY(h, h->blksum.ensure(bo.size() * 4));
-        HIP_TRY(h, hipMemcpyAsync(h->blksum.p, bo.data(), bo.size() * 4, hipMemcpyHostToDevice,
-                                  h->stream));
-        if (h->perm_on) {
-          const std::vector<uint32_t> bp = bsums(nperm.data());
-          HIP_TRY(h, h->blksum_p.ensure(bp.size() * 4));
-          HIP_TRY(h, hipMemcpyAsync(h->blksum_p.p, bp.data(), bp.size() * 4,
-                                    hipMemcpyHostToDevice, h->stream));
-        }
-        HIP_TRY(h, hipStreamSynchronize(h->stream));  // (the host copies go out of scope)
-        h->blksum_loose = false;
-      }
-      sum = tiles(sum, (uint32_t)sstride);
-      sum2 = tiles(sum2, (uint32_t)s2stride);
-      mix = tiles(mix, (uint32_t)mstride);
-      x1m = tiles(x1m, (uint32_t)xstride);
-      HIP_TRY(h, h->kx1.ensure(x1m.size() * 4));
-      HIP_TRY(h, hipMemcpyAsync(h->kx1.p, x1m.data(), x1m.size() * 4, hipMemcpyHostToDevice,
-                                h->stream));
-      HIP_TRY(h, h->kmix.ensure(mix.size() * 4));
-      HIP_TRY(h, hipMemcpyAsync(h->kmix.p, mix.data(), mix.size() * 4, hipMemcpyHostToDevice,
-                                h->stream));
-      HIP_TRY(h, h->k1sum.ensure(sum.size() * 4));
-      HIP_TRY(h, hipMemcpyAsync(h->k1sum.p, sum.data(), sum.size() * 4, hipMemcpyHostToDevice,
-                                h->stream));
-      HIP_TRY(h, h->k2sum.ensure(sum2.size() * 4));
-      HIP_TRY(h, hipMemcpyAsync(h->k2sum.p, sum2.data(), sum2.size() * 4, hipMemcpyHostToDevice,
-                                h->stream));
-      // the G table: per field the max over every real card (floor 1, collection.go:31-38),
-      // the CollectMaxValues result of any pod feasible on the maximal cards' nodes
-      uint64_t gmax[6] = {1, 1, 1, 1, 1, 1};
-      for (uint32_t i = 0; i < N; ++i)
-        for (uint32_t j = 0; j < nd->card_count[i]; ++j) {
-          const size_t k = (size_t)i * KS + j;
-          gmax[kMaxBw] = std::max(gmax[kMaxBw], nd->card_bandwidth[k]);
-          gmax[kMaxClock] = std::max(gmax[kMaxClock], nd->card_clock[k]);
-          gmax[kMaxCore] = std::max(gmax[kMaxCore], nd->card_core[k]);
-          gmax[kMaxFree] = std::max(gmax[kMaxFree], nd->card_free_memory[k]);
-          gmax[kMaxPower] = std::max(gmax[kMaxPower], nd->card_power[k]);
-          gmax[kMaxTotal] = std::max(gmax[kMaxTotal], nd->card_total_memory[k]);
-        }
-      HIP_TRY(h, h->gtab.ensure(sum_words(std::max<uint32_t>(N, 1), gtab_stride(K)) * 4));
-      std::memcpy(h->h_gmax, gmax, sizeof(gmax));
-      HIP_TRY(h, h->gtab_aux.ensure(kGTabAuxBytes));
-      HIP_TRY(h, hipMemcpyAsync(h->gtab_aux.p, gmax, sizeof(gmax), hipMemcpyHostToDevice,
-                                h->stream));
-      uint32_t* rcp_dev = reinterpret_cast<uint32_t*>(h->gtab_aux.as<unsigned char>() + 48);
-      MemTab mt{};
-      if (ranks) {  // value tables: v[0] = v[1] = 0, v[2 + i] = the i-th distinct value
-        std::vector<double> vt(4 + frees.size() + totals.size(), 0.0);
-        for (size_t i = 0; i < frees.size(); ++i) vt[2 + i] = (double)frees[i];
-        for (size_t i = 0; i < totals.size(); ++i) vt[4 + frees.size() + i] = (double)totals[i];
-        HIP_TRY(h, h->memtab.ensure(vt.size() * 8));
-        HIP_TRY(h, hipMemcpy(h->memtab.p, vt.data(), vt.size() * 8, hipMemcpyHostToDevice));
-        mt.vf = h->memtab.as<double>();
-        mt.vt = h->memtab.as<double>() + 2 + frees.size();
-        mt.nf = (uint32_t)frees.size();
-      }
-      h->mt = mt;
-      HIP_TRY(h, launch_gtable(K, h->k2sum.as<uint32_t>(), h->kmix.as<uint32_t>(), N,
-                               h->gtab_aux.as<uint64_t>(),
-                               h->gtab.as<uint32_t>(), rcp_dev, mt, h->stream));
-      if (h->perm_on) {  // the G table of the block-grouped copy (the same rows, reordered)
-        HIP_TRY(h, h->gtab_p.ensure(sum_words(std::max<uint32_t>(N, 1), gtab_stride(K)) * 4));
-        HIP_TRY(h, launch_gtable(K, h->k2sum_p.as<uint32_t>(), h->kmix_p.as<uint32_t>(), N,
-                                 h->gtab_aux.as<uint64_t>(), h->gtab_p.as<uint32_t>(), rcp_dev,
-                                 mt, h->stream));
-      }
-      HIP_TRY(h, hipMemcpyAsync(g_rcp, rcp_dev, sizeof(g_rcp), hipMemcpyDeviceToHost, h->stream));
+    // N32: the summaries in both node orders, then what the device derives from them
+    std::vector<uint32_t> nperm;
+    std::vector<std::vector<uint32_t>> staged;  // (host sides of the copies in flight)
+    if (want_sum) {
+      nperm = grouped_node_order(rows.sum, N, K, fmt.ranks, rows.n_one_model == N, flags);
+      h->perm_on = !nperm.empty();
+      int rc = upload_sum_tables(h, rows, nperm, staged);
+      if (!rc) rc = upload_block_sums(h);
+      if (!rc) rc = upload_gtables(h, nd, mc);
+      if (rc) return rc;
     }
     const bool diskio = nd->cpu && nd->disk_io;
-    if (diskio && N > 0) {  // (g_rcp: read back by the synchronize below)
-      std::vector<NodeRecB> rb(N);
+    std::vector<NodeRecB> rb;
+    if (diskio && N > 0) {
+      rb.resize(N);
       for (uint32_t i = 0; i < N; ++i) {
         rb[i].v = nd->cpu[i] / 100.0;     // algorithm.go:73
         rb[i].u = nd->disk_io[i] / 50.0;  // algorithm.go:71
@@ -2481,91 +2520,36 @@ int yoda_upload_nodes(yoda_t* h, const yoda_node_soa* nd, uint32_t node_offset, 
       HIP_TRY(h, hipMemcpyAsync(h->nodes_b.p, rb.data(), (size_t)N * sizeof(NodeRecB),
                                 hipMemcpyHostToDevice, h->stream));
     }
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->host_records.swap(rec);
-    h->host_k2sum.swap(sum2);
+    h->has_k1sum = want_sum && !(flags & YODA_UPLOAD_PER_NODE_K1);
+    h->has_k2sum = want_sum && !(flags & YODA_UPLOAD_PER_NODE_K2);
+    static const bool no_gtab = YODA_KNOB("YODA_NO_GTAB", 0) != 0;  // A/B knob
+    // The upload's one wait, for every copy and table kernel above; with a G table in use its
+    // reciprocals come back in the same wait.
+    h->g = GTab{};
+    if (h->has_k2sum && N > 0 && !no_gtab && !(flags & YODA_UPLOAD_NO_GTAB)) {
+      h->g.tab = h->gtab.as<uint32_t>();
+      if (int rc = read_g_reciprocals(h)) return rc;
+    } else {
+      HIP_TRY(h, hipStreamSynchronize(h->stream));
+    }
+    h->host_records.swap(rows.rec);
     h->h_total_sum.assign(nd->total_memory_sum, nd->total_memory_sum + N);
     h->h_free_sum.assign(nd->free_memory_sum, nd->free_memory_sum + N);
     h->h_card_number.assign(nd->card_number, nd->card_number + N);
     h->h_alloc.assign(N, 0);
     if (nd->alloc_memory) h->h_alloc.assign(nd->alloc_memory, nd->alloc_memory + N);
     h->nodes_diskio = diskio;
-    h->n_nodes = N;
-    h->node_offset = node_offset;
-    if (h->K != K || h->path != path) std::memset(h->cap, 0, sizeof(h->cap));
-    h->K = K;
-    h->path = path;
-    h->has_k1sum = want_sum && !(flags & YODA_UPLOAD_PER_NODE_K1);
-    h->all_one_model = n_one_model == N;
-    h->all_uni4 = n_uni4 == N;
-    h->has_k2sum = want_sum && !(flags & YODA_UPLOAD_PER_NODE_K2);
-    h->g = GTab{};
-    static const bool no_gtab = YODA_KNOB("YODA_NO_GTAB", 0) != 0;  // A/B knob
-    if (h->has_k2sum && N > 0 && !no_gtab && !(flags & YODA_UPLOAD_NO_GTAB)) {
-      h->g.tab = h->gtab.as<uint32_t>();
-      std::memcpy(&h->g.r_bw, &g_rcp[0], 8);
-      std::memcpy(&h->g.r_core, &g_rcp[2], 8);
-      std::memcpy(&h->g.r_pow, &g_rcp[4], 8);
-      std::memcpy(&h->g.r_free, &g_rcp[6], 8);
-      std::memcpy(&h->g.r_tot, &g_rcp[8], 8);
-      auto ru32 = [](double r) {  // the smallest float >= r (yoda_kernels.hip ru32_of)
-        float f = (float)r;
-        if ((double)f < r) f = std::nextafter(f, INFINITY);
-        return f;
-      };
-      h->g.f_bw = ru32(h->g.r_bw);
-      h->g.f_core = ru32(h->g.r_core);
-      h->g.f_pow = ru32(h->g.r_pow);
-    }
-    h->generic = path == Path::U64;
-    h->mem_ranks = ranks;
-    h->pack16 = pack16;
-    h->q32 = q32;
-    h->small_max = max_small;
+    h->all_one_model = rows.n_one_model == N;
+    h->all_uni4 = rows.n_uni4 == N;
     h->kbub_dirty = true;
     h->kbub_loose = false;
     h->kb_levels_ok = false;
     h->hot_ok = false;
     if (h->has_k2sum && h->g.tab && N > 0) {
       HIP_TRY(h, build_block_ub(h));
-      // the blocks whose bound with every card qualifying (lv[0]) is in the top tenth: a
-      // static visiting order hint for the argmax K2 (results do not depend on it)
-      const uint32_t nb = (N + 63) / 64, KST = kbub_stride(K);
-      std::vector<uint32_t> ubw(sum_words(nb, KST));
-      std::vector<uint64_t> words((nb + 63) / 64), words_p((nb + 63) / 64);
-      auto hot_bits = [&](const DevBuf& src, std::vector<uint64_t>& out) -> int {
-        HIP_TRY(h, hipMemcpyAsync(ubw.data(), src.p, ubw.size() * 4, hipMemcpyDeviceToHost,
-                                  h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        std::vector<double> u(nb);
-        for (uint32_t b = 0; b < nb; ++b) {
-          const uint64_t bits = (uint64_t)ubw[sum_index(b, kbub_lvl(K), KST)] |
-                                ((uint64_t)ubw[sum_index(b, kbub_lvl(K) + 1u, KST)] << 32);
-          std::memcpy(&u[b], &bits, 8);
-        }
-        std::vector<double> srt(u);
-        const size_t q = srt.size() - 1 - srt.size() / 10;
-        std::nth_element(srt.begin(), srt.begin() + q, srt.end());
-        const double thr = srt[q];
-        std::fill(out.begin(), out.end(), 0ull);
-        for (uint32_t b = 0; b < nb; ++b)
-          if (u[b] >= thr) out[b >> 6] |= 1ull << (b & 63);
-        return YODA_OK;
-      };
-      int hr = hot_bits(h->kbub, words);
-      if (!hr && h->perm_on) hr = hot_bits(h->kbub_p, words_p);
-      if (hr) return hr;
-      HIP_TRY(h, h->hot.ensure(words.size() * 8));
-      HIP_TRY(h, hipMemcpy(h->hot.p, words.data(), words.size() * 8, hipMemcpyHostToDevice));
-      if (h->perm_on) {
-        HIP_TRY(h, h->hot_p.ensure(words_p.size() * 8));
-        HIP_TRY(h, hipMemcpy(h->hot_p.p, words_p.data(), words_p.size() * 8,
-                             hipMemcpyHostToDevice));
-      }
-      h->hot_ok = true;
+      if (int rc = build_hot_masks(h)) return rc;
     }
-    if (!ranks) h->mt = MemTab{};
-    h->h_frees.swap(frees);
+    h->h_frees.swap(mc.frees);
     h->has_nodes = true;
     // the uploaded pods' N32 memory thresholds follow the snapshot (ranks or the clamp)
     if (h->has_pods && path == Path::N32) {
@@ -2579,7 +2563,6 @@ int yoda_upload_nodes(yoda_t* h, const yoda_node_soa* nd, uint32_t node_offset, 
     }
     h->ran = false;
     h->phase1_done = false;
-    if (!is_pow2_le16((uint32_t)K)) return fail(h, YODA_ERR_INVALID_ARG, "bad K");
     return YODA_OK;
   } catch (const std::bad_alloc&) {
     return fail(h, YODA_ERR_INVALID_ARG, "host allocation failed");
@@ -3055,7 +3038,7 @@ int yoda_download(yoda_t* h, yoda_eval_out* out) {
         ++t.n;
       }
       HIP_TRY(h, launch_permute(t, h->perm.as<uint32_t>(), W, true, s));
-      std::swap(h->maxima, h->maxima_alt);
+      h->maxima.swap(h->maxima_alt);
       h->maxima_sorted = false;
     }
     if (out->maxima) {
@@ -4116,33 +4099,6 @@ uint64_t rec_field(const yoda_t* h, const unsigned char* r, int field, uint32_t 
   return u;
 }
 
-// The G table of both orders from the current K2 summaries and the maxima in gtab_aux.
-int relaunch_gtables(yoda_t* h) {
-  uint32_t* rcp_dev = reinterpret_cast<uint32_t*>(h->gtab_aux.as<unsigned char>() + 48);
-  const MemTab mt = h->mem_ranks ? h->mt : MemTab{};
-  HIP_TRY(h, launch_gtable(h->K, h->k2sum.as<uint32_t>(), h->kmix.as<uint32_t>(), h->n_nodes,
-                           h->gtab_aux.as<uint64_t>(), h->gtab.as<uint32_t>(), rcp_dev, mt,
-                           h->stream));
-  if (h->perm_on)
-    HIP_TRY(h, launch_gtable(h->K, h->k2sum_p.as<uint32_t>(), h->kmix_p.as<uint32_t>(),
-                             h->n_nodes, h->gtab_aux.as<uint64_t>(), h->gtab_p.as<uint32_t>(),
-                             rcp_dev, mt, h->stream));
-  return YODA_OK;
-}
-
-// The block summaries of both orders from the device summaries (k_bsum_build).
-int rebuild_block_sums(yoda_t* h) {
-  HIP_TRY(h, launch_bsum_build(h->K, h->k1sum.as<uint32_t>(), h->k2sum.as<uint32_t>(),
-                               h->kx1.as<uint32_t>(), h->kmix.as<uint32_t>(), h->n_nodes,
-                               h->blksum.as<uint32_t>(), h->stream));
-  if (h->perm_on)
-    HIP_TRY(h, launch_bsum_build(h->K, h->k1sum_p.as<uint32_t>(), h->k2sum_p.as<uint32_t>(),
-                                 h->kx1_p.as<uint32_t>(), h->kmix_p.as<uint32_t>(), h->n_nodes,
-                                 h->blksum_p.as<uint32_t>(), h->stream));
-  h->blksum_loose = false;
-  return YODA_OK;
-}
-
 }  // namespace
 
 int yoda_update_node_cards(yoda_t* h, uint32_t count, const uint32_t* nodes, uint32_t max_cards,
@@ -4325,17 +4281,8 @@ int yoda_update_node_cards(yoda_t* h, uint32_t count, const uint32_t* nodes, uin
     if ((rc = relaunch_gtables(h))) return rc;
     h->kbub_dirty = true;  // the K2 block bounds: rebuilt before their next reader
     h->kbub_loose = false;
-    if (g_moved && h->g.tab) {  // the reciprocals of the new maxima, as the upload reads them
-      uint32_t g_rcp[10] = {};
-      HIP_TRY(h, hipMemcpyAsync(g_rcp, h->gtab_aux.as<unsigned char>() + 48, sizeof(g_rcp),
-                                hipMemcpyDeviceToHost, h->stream));
-      HIP_TRY(h, hipStreamSynchronize(h->stream));
-      std::memcpy(&h->g.r_bw, &g_rcp[0], 8);
-      std::memcpy(&h->g.r_core, &g_rcp[2], 8);
-      std::memcpy(&h->g.r_pow, &g_rcp[4], 8);
-      std::memcpy(&h->g.r_free, &g_rcp[6], 8);
-      std::memcpy(&h->g.r_tot, &g_rcp[8], 8);
-    }
+    // the reciprocals of the new maxima, as the upload reads them
+    if (g_moved && h->g.tab && (rc = read_g_reciprocals(h))) return rc;
     return YODA_OK;
   } catch (const std::bad_alloc&) {
     h->upd_slot.clear();
@@ -4380,26 +4327,21 @@ int yoda_snapshot_check(yoda_t* h, uint64_t* digest, uint32_t* mismatch) {
       mismatch[3] += hw != rec[w];
     }
     if (!n32 || N == 0) return YODA_OK;
-    const uint32_t strides[5] = {k1sum_stride(K), k2sum_stride(K), mix_stride(K), x1_stride(K),
-                                 gtab_stride(K)};
-    const DevBuf* base[5] = {&h->k1sum, &h->k2sum, &h->kmix, &h->kx1, &h->gtab};
-    const DevBuf* copy[5] = {&h->k1sum_p, &h->k2sum_p, &h->kmix_p, &h->kx1_p, &h->gtab_p};
-    const int dig[5] = {1, 2, 3, 4, 6};
     std::vector<uint32_t> ids, a, b;
     if (h->perm_on && (rc = fetch(h->perm_ids, N, ids))) return rc;
-    for (int k = 0; k < 5; ++k) {
-      if ((rc = fetch(*base[k], sum_words(N, strides[k]), a))) return rc;
-      digest[dig[k]] = hash(a);
-      if (k == 1)
+    for (const SumTable& t : sum_tables(K)) {
+      if ((rc = fetch(h->*t.base, sum_words(N, t.stride), a))) return rc;
+      digest[t.digest] = hash(a);
+      if (t.base == &yoda_handle::k2sum)
         for (size_t w = 0; w < a.size() && w < h->host_k2sum.size(); ++w)
           mismatch[3] += a[w] != h->host_k2sum[w];
       if (!h->perm_on) continue;
-      if ((rc = fetch(*copy[k], sum_words(N, strides[k]), b))) return rc;
+      if ((rc = fetch(h->*t.grouped, sum_words(N, t.stride), b))) return rc;
       for (uint32_t q = 0; q < N; ++q)
-        for (uint32_t w = 0; w < strides[k] / 4u; ++w)
-          mismatch[0] += b[sum_index(q, w, strides[k])] != a[sum_index(ids[q], w, strides[k])];
+        for (uint32_t w = 0; w < t.stride / 4u; ++w)
+          mismatch[0] += b[sum_index(q, w, t.stride)] != a[sum_index(ids[q], w, t.stride)];
     }
-    // the block summaries of both orders against k_bsum_build run now
+    // the stored block summaries of both orders against a fresh build (k_bsum_build run now)
     const size_t bw = sum_words((N + 63) / 64, bsum_stride(K));
     HIP_TRY(h, h->bsum_chk.ensure(bw * 4));
     for (int o = 0; o < (h->perm_on ? 2 : 1); ++o) {

@@ -5529,9 +5529,12 @@ hipError_t launch_set_cards(unsigned char* nodes, uint32_t stride, const uint32_
 }
 
 // The block summaries (yoda_layout.h BlockSumWord) of one summary order from its DEVICE K1 / K2
-// summaries, K1 tiles and model rows: what yoda_upload_nodes builds on the host, word for word
-// (yoda_snapshot_check compares the two).  One wave per 64-node block, lane = node; the whole
-// row is written, the CardNumber bounds tight.
+// summaries, K1 tiles and model rows: the one builder, run by yoda_upload_nodes, by
+// yoda_update_node_cards and again by yoda_snapshot_check (stored summaries against a fresh
+// build).  tests/golden/upload_digests.json pins its output on fresh uploads to the words of
+// the host builder it replaced.  One wave per 64-node block, lane = node; the whole row of a
+// real block is written (rows of the tile padding are not: the caller clears them), the
+// CardNumber bounds tight.
 __global__ __launch_bounds__(kWave) void k_bsum_build(const uint32_t* __restrict__ sum,
                                                       const uint32_t* __restrict__ sum2,
                                                       const uint32_t* __restrict__ x1,

@@ -1,8 +1,10 @@
 // yoda_node_pack.h — one node of a snapshot packed into the device layout of yoda_layout.h:
-// its record, its K1 and K2 summary rows, its per-card model row, its K1 mixed tile and its
-// clock ranges.  Host code without a HIP runtime call: yoda_upload_nodes packs every node with
-// it, yoda_update_node_cards the nodes whose card metrics changed, and tools/check_node_pack.cpp
-// runs it under AddressSanitizer.  One packer, so the sparse path cannot drift from the upload.
+// its record, its K1 and K2 summary rows, its per-card model row and its K1 mixed tile.  Host
+// code without a HIP runtime call: yoda_upload_nodes packs every node with it,
+// yoda_update_node_cards the nodes whose card metrics changed, and tools/check_node_pack.cpp
+// runs it under AddressSanitizer.  One packer, so the sparse path cannot drift from the upload;
+// what is derived from these rows (block summaries, G table) has one builder too, on the device
+// (k_bsum_build, k_gtable), which both callers run.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -35,15 +37,13 @@ struct NodePackIn {
 
 // Where the node's rows go, node-major (contiguous words): rec has n32_stride(K) (N32) or
 // node_stride(K) bytes; sum / sum2 / mix / x1 (N32 only, else nullptr) have k1sum_stride(K) / 4,
-// k2sum_stride(K) / 4, mix_stride(K) / 4, x1_stride(K) / 4 words; clk_rng (optional) 4 words:
-// the clocks of the real cards min / max, of the healthy cards min / max.
+// k2sum_stride(K) / 4, mix_stride(K) / 4, x1_stride(K) / 4 words.
 struct NodePackOut {
   unsigned char* rec = nullptr;
   uint32_t* sum = nullptr;
   uint32_t* sum2 = nullptr;
   uint32_t* mix = nullptr;
   uint32_t* x1 = nullptr;
-  uint32_t* clk_rng = nullptr;
   // the rows are known to hold zeros (the upload's fresh vectors): pack_node skips clearing them
   bool zeroed = false;
 };
@@ -174,20 +174,6 @@ inline uint32_t pack_node(Path path, int K, const NodePackIn& in, const NodePack
       }
     }
     x[kX1Chg] = chg;
-    if (out.clk_rng) {
-      uint32_t* cr = out.clk_rng;
-      cr[0] = cr[2] = 0xffffffffu;
-      cr[1] = cr[3] = 0u;
-      for (uint32_t j = 0; j < cnt; ++j) {
-        const uint32_t ck = (uint32_t)in.clock[j];
-        cr[0] = std::min(cr[0], ck);
-        cr[1] = std::max(cr[1], ck);
-        if (in.healthy[j]) {
-          cr[2] = std::min(cr[2], ck);
-          cr[3] = std::max(cr[3], ck);
-        }
-      }
-    }
   }
   for (uint32_t j = 0; j < cnt; ++j) {
     const uint64_t v[6] = {in.free_memory[j], in.clock[j], in.total_memory[j], in.bandwidth[j],

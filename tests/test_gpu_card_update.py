@@ -3,8 +3,8 @@ entry point.  At every check three things are compared, exactly and in every fie
 assert_same: the handle that saw only the steps, a fresh upload of the model's snapshot, and the
 C oracle (scenarios: tests/card_update_cases.py; tests/test_card_update_cases.py shows that each
 of them moves a large share of the picks or feasible counts).  yoda_snapshot_check then looks at
-what no pick shows: block-grouped copies that left the base rows, block summaries that differ
-from k_bsum_build, host mirrors that differ from the device; and on shapes without a grouped node
+what no pick shows: block-grouped copies that left the base rows, stored block summaries that
+differ from a fresh k_bsum_build, host mirrors that differ from the device; and on shapes without a grouped node
 order the table digests of the long-lived handle equal a fresh upload's (no stale tail word, an
 exact G table)."""
 import numpy as np
@@ -12,9 +12,9 @@ import pytest
 
 import card_update_cases as cases
 import oracle
+import upload_cases
 from test_gpu_node_state import (Fleet, _scatter, assert_equal_results, check_state)
 from test_gpu_parity import assert_same
-from yoda_amd import synth
 from yoda_amd.capi import Yoda, YodaError
 from yoda_amd.soa import MODE_SCV
 
@@ -235,43 +235,21 @@ def test_score_bound_only_grows():
         assert dev.score_bound == filled >= fresh_bound(fleet.model.nodes())
 
 
-def _six_clock_fleet():
-    """test_gpu_robust.test_mixed_block_rules' fleet: blocks with six healthy-card clocks (no
-    per-clock table), mixed models, nodes without cards."""
-    rng = np.random.default_rng(7300)
-    n = 4096
-    nodes = synth.mixed_models(synth.make_nodes(n, 77), 0.7, seed=78)
-    clocks6 = np.array([1200, 1300, 1410, 1500, 1600, 1755], dtype=np.uint64)
-    real = np.arange(8)[None, :] < nodes.card_count[:, None]
-    six = np.arange(n) < 1024
-    nodes.card_clock[six] = np.where(real[six], clocks6[rng.integers(0, 6, size=(1024, 8))], 0)
-    empty = rng.random(n) < 0.02
-    for a in (nodes.card_free_memory, nodes.card_total_memory, nodes.card_clock,
-              nodes.card_bandwidth, nodes.card_core, nodes.card_power, nodes.card_healthy):
-        a[empty] = 0
-    nodes.card_count[empty] = 0
-    return nodes.normalized()
-
-
-def _wide_clock_fleet():
-    big, _ = synth.make_config(2, pods=10, nodes=3000)
-    big.card_clock[:] = np.where(big.card_clock > 0, big.card_clock * 100, 0)
-    return big.normalized()
-
-
-@pytest.mark.parametrize("shape", list(cases.SHAPES) + ["six_clocks", "wide_clocks"])
+@pytest.mark.parametrize("shape", upload_cases.NAMES)
 def test_builder_equivalence_on_fresh_uploads(shape):
-    """k_bsum_build equals the upload's host builder word for word, in both orders, and the
-    block-grouped copies are the base rows permuted, before any update."""
-    if shape == "six_clocks":
-        nodes, kw = _six_clock_fleet(), {}
-    elif shape == "wide_clocks":
-        nodes, kw = _wide_clock_fleet(), {}
-    else:
-        nodes, kw = cases.shape_workload(shape, mixed_pods=10)[0], cases.UPLOAD_KW.get(shape, {})
+    """A fresh upload against tests/golden/upload_digests.json, recorded at the last commit whose
+    upload built the block summaries on the host (where a zero mismatch meant host builder ==
+    k_bsum_build).  Digest 5: the block summaries k_bsum_build writes at upload equal that host
+    builder's, word for word; digests 0-4, 6 and 7: the records, every other base table, the G
+    table, its maxima and reciprocals are the ones that upload made; path and grouped order
+    too.  The mismatch words: the stored block summaries of both orders equal a build into
+    zeroed scratch (no stale padding word: small_after_base uploads over a larger snapshot) and
+    the block-grouped copies are the base rows permuted, before any update."""
     with Yoda(0) as y:
-        y.upload_nodes(nodes, **kw)
+        for nodes, kw in upload_cases.uploads(shape):
+            y.upload_nodes(nodes, **kw)
         d, m = y.snapshot_check()
         assert m.tolist() == ZERO
         assert d[0] != 0
         assert (d[1:] != 0).all() == (y.path == "n32")
+        assert upload_cases.entry(y, d) == upload_cases.golden()[shape]

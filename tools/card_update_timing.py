@@ -92,7 +92,9 @@ def main():
                    "upload_call_ms": round(med(t_up_call), 3),
                    "update_plus_run_ms": {str(s): round(med(t_upd[s]), 3) for s in sizes},
                    "update_call_ms": {str(s): round(med(t_upd_call[s]), 3) for s in sizes},
-                   "upload_plus_run_all_ms": [round(t, 2) for t in t_up]}
+                   "upload_plus_run_all_ms": [round(t, 2) for t in t_up],
+                   "update_plus_run_all_ms": {str(s): [round(t, 3) for t in t_upd[s]]
+                                              for s in sizes}}
             print(json.dumps(out), flush=True)
 
 

@@ -69,7 +69,7 @@ struct Node {
 // Rows of exactly their size on the heap.
 struct Rows {
   std::unique_ptr<unsigned char[]> rec;
-  std::unique_ptr<uint32_t[]> sum, sum2, mix, x1, cr;
+  std::unique_ptr<uint32_t[]> sum, sum2, mix, x1;
   NodePackOut out;
   Rows(Path path, int K, bool zero) {
     const size_t rs = path == Path::N32 ? n32_stride(K) : node_stride(K);
@@ -78,7 +78,6 @@ struct Rows {
     sum2.reset(new uint32_t[k2sum_stride(K) / 4]);
     mix.reset(new uint32_t[mix_stride(K) / 4]);
     x1.reset(new uint32_t[x1_stride(K) / 4]);
-    cr.reset(new uint32_t[4]);
     const int fill = zero ? 0 : 0xa5;  // a used buffer: whatever an older row left
     std::memset(rec.get(), fill, rs);
     std::memset(sum.get(), fill, k1sum_stride(K));
@@ -92,7 +91,6 @@ struct Rows {
       out.sum2 = sum2.get();
       out.mix = mix.get();
       out.x1 = x1.get();
-      out.clk_rng = cr.get();
     }
   }
 };
@@ -104,8 +102,7 @@ bool same(const Rows& a, const Rows& b, Path path, int K) {
   return !std::memcmp(a.sum.get(), b.sum.get(), k1sum_stride(K)) &&
          !std::memcmp(a.sum2.get(), b.sum2.get(), k2sum_stride(K)) &&
          !std::memcmp(a.mix.get(), b.mix.get(), mix_stride(K)) &&
-         !std::memcmp(a.x1.get(), b.x1.get(), x1_stride(K)) &&
-         !std::memcmp(a.cr.get(), b.cr.get(), 16);
+         !std::memcmp(a.x1.get(), b.x1.get(), x1_stride(K));
 }
 
 void random_node(Node& nd, int K, uint32_t cnt, int style) {
