@@ -458,8 +458,9 @@ int yoda_shard_topk(yoda_t* h, const uint64_t* d_maxima, const uint32_t* d_count
                     uint32_t* counts, double* top_score, uint32_t* top_node);
 /* Capacity windows across shards (the window sequence of yoda_comm_greedy and yoda_greedy):
  * yoda_shard_topk after yoda_shard_phase1_witness, but the lists are `deep` long
- * (yoda_greedy_cap_depth()) -- the chunks' lists merged deeper, exact down to their last entry
- * and 0xFFFFFFFF-ended past it; top_score / top_node are [deep][P]. */
+ * (yoda_greedy_cap_depth()) -- the chunks' k-deep lists merged deeper, exact down to their last
+ * entry (at least the first min(k, n_feasible), as yoda_shard_topk lists them) and
+ * 0xFFFFFFFF-ended past it; top_score / top_node are [deep][P]. */
 int yoda_greedy_cap_depth(void);
 int yoda_shard_topk_deep(yoda_t* h, const uint64_t* d_maxima, const uint32_t* d_counts,
                          uint32_t k, uint32_t deep, uint32_t* counts, double* top_score,
@@ -488,7 +489,9 @@ int yoda_shard_best_one(yoda_t* h, uint32_t pod, double* score, int32_t* node);
  * d_wit[0, 6P) and MIN-reduce (unsigned) d_wit[6P, 12P).  yoda_shard_topk with
  * k = yoda_topk_k_capacity() (the deeper lists of the capacity windows); then
  * yoda_shard_witness_download gives maxima [6][P] and wit [12][P] in the caller's pod order
- * for yoda_gs_set_witness.  A pod the session cannot certify starts the next window. */
+ * for yoda_gs_set_witness.  A pod the session cannot certify starts the next window.
+ * For a field whose maximum is the floor 1 the witness words are unspecified (the session
+ * never reads them: no node's value decides such a maximum). */
 int yoda_shard_phase1_witness(yoda_t* h, uint64_t* d_maxima, uint32_t* d_counts,
                               uint32_t* d_wit);
 int yoda_shard_witness_prepare(yoda_t* h, const uint64_t* d_maxima_global,

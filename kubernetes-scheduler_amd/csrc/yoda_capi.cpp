@@ -1086,12 +1086,16 @@ constexpr uint32_t kOrderMaxGroups = 16384;
 // sort (groups built at upload) fills h->n_work sorted positions: n_pad when the run pads
 // its groups to whole waves (prepare_run), else n_pods; the radix sort is the fallback for
 // batches with too many groups.
-int order_pods(yoda_t* h, int mode) {
+// shared: the exchange buffers are in the shards' common radix order (the capacity windows'
+// witness phase 1), so a shard without nodes sorts too: it downloads the reduced buffers of
+// the others through its own permutation.  Otherwise an empty snapshot runs nothing to order.
+int order_pods(yoda_t* h, int mode, bool shared = false) {
   const uint32_t P = h->n_pods, W = h->n_work;
   h->ordered = false;
   h->blk_zeroed = false;
   h->maxima_sorted = false;
-  if (!h->order_enabled || mode != YODA_MODE_SCV || P < kOrderMinPods || h->n_nodes == 0)
+  if (!h->order_enabled || mode != YODA_MODE_SCV || P < kOrderMinPods ||
+      (h->n_nodes == 0 && !shared))
     return YODA_OK;
   const unsigned char* b = h->pod_blob.as<unsigned char>();
   HIP_TRY(h, h->perm.ensure((size_t)W * 4));
@@ -4385,8 +4389,9 @@ int yoda_shard_topk(yoda_t* h, const uint64_t* d_maxima, const uint32_t* d_count
 
 namespace {
 // deep > 0 (libyoda's sharded capacity windows): lists `deep` long, exact down to their last
-// entry and empty past it -- the 8-deep chunk lists merged deeper where the block kernels run
-// (k_topk_merge_deep), else the k-deep lists padded -- whatever this shard's kernels.
+// entry, at least min(k, n_feasible) entries, and empty past it -- the k-deep chunk lists merged
+// deeper where the block kernels run (k_topk_merge_deep), else the k-deep lists padded --
+// whatever this shard's kernels.
 int shard_topk_impl(yoda_t* h, const uint64_t* d_maxima, const uint32_t* d_counts, uint32_t k,
                     uint32_t deep, uint32_t* counts, double* top_score, uint32_t* top_node) {
   int rc = check_ready(h, YODA_MODE_SCV);
@@ -4422,7 +4427,10 @@ int shard_topk_impl(yoda_t* h, const uint64_t* d_maxima, const uint32_t* d_count
       HIP_TRY(h, launch_prep2(h->maxima.as<uint64_t>(), P, h->rcp.as<double>(),
                                h->stream));
       if (deep > KT && topk_block_ok(h)) {
-        if ((rc = topk_lists(h, P, (uint32_t)topk_k(), d_counts, deep, &KD))) return rc;
+        // (the chunks' lists at this phase 1's depth: a deep list is never shorter than the
+        // KT-deep list yoda_shard_topk gives -- with 8-deep chunk lists after the witness phase
+        // 1, pods whose best scores all tie came back with 8 entries of 300 feasible nodes)
+        if ((rc = topk_lists(h, P, KT, d_counts, deep, &KD))) return rc;
       } else if ((rc = topk_lists(h, P, KT, d_counts))) {
         return rc;
       }
@@ -4466,7 +4474,7 @@ int yoda_shard_phase1_witness(yoda_t* h, uint64_t* d_maxima, uint32_t* d_counts,
     return fail(h, YODA_ERR_STATE, "witness phase 1 needs a fast record path (N32 or F64)");
   if (!d_maxima || !d_counts || !d_wit) return fail(h, YODA_ERR_INVALID_ARG, "NULL buffer");
   try {
-    if ((rc = order_pods(h, YODA_MODE_SCV))) return rc;
+    if ((rc = order_pods(h, YODA_MODE_SCV, true))) return rc;
     if ((rc = phase1_witness(h, d_maxima, d_counts, d_wit, h->node_offset))) return rc;
     h->phase1_done = true;
     h->phase1_wit = true;

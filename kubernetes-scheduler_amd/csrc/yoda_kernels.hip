@@ -1135,13 +1135,15 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WIT ? 4 
       a_free = max(a_free, mrf1 - (mrf1 != 0u ? 1u : 0u));
       a_pw = max(a_pw, pw);
       a_tot = max(a_tot, tot);
-      if constexpr (WIT) {  // nodes in increasing order per lane: the first witness is lowest
+      if constexpr (WIT) {
+        // (not in id order per lane: a chunk's whole-block folds below, lane = block, come
+        // before the nodes of its undecided blocks, so an equal value takes the lower id)
         const uint32_t v[6] = {bw, ck, core, mrf1 - (mrf1 != 0u ? 1u : 0u), pw, tot};
 #pragma unroll
         for (int f = 0; f < 6; ++f) {
           const bool gt = v[f] > aw[f], eq = v[f] == aw[f];
           ac[f] = gt ? 1u : ac[f] + (eq ? 1u : 0u);
-          al[f] = gt ? nb + lane : al[f];
+          al[f] = gt ? nb + lane : (eq ? min(al[f], nb + lane) : al[f]);
           aw[f] = gt ? v[f] : aw[f];
         }
       }

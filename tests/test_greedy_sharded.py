@@ -15,6 +15,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 import oracle
+import witness_cases
 from yoda_amd import synth
 from yoda_amd.capi import merge_shard_lists, topk_k, topk_k_capacity
 from yoda_amd.dist import Reducer, ShardBuffers, merge_topk, shard_bounds, sharded_greedy
@@ -96,29 +97,9 @@ class OracleShard:
         qualifying cards (collection.go:46) reach the shard's maximum, and the lowest one."""
         b = self.phase1()
         b.ensure_witness()
-        n, nd = self.pods.n_pods, self.nodes
-        mx = b.maxima.numpy().view(np.uint64).reshape(6, n)
-        wc = np.zeros((6, n), np.uint32)
-        wn = np.full((6, n), 0xFFFFFFFF, np.uint32)
-        K = nd.card_free_memory.shape[1]
-        for p in range(n):
-            f, _ = self._detail(p)
-            if f.size == 0:
-                continue
-            m = int(self.pods.memory[p]) if self.pods.has_memory[p] else 0
-            c = int(self.pods.clock[p]) if self.pods.has_clock[p] else 0
-            real = np.arange(K)[None, :] < nd.card_count[f][:, None]
-            q = real & (nd.card_free_memory[f] >= m) & (nd.card_clock[f] >= c)
-            anyq = q.any(axis=1)
-            fields = (nd.card_bandwidth, nd.card_clock, nd.card_core, nd.card_free_memory,
-                      nd.card_power, nd.card_total_memory)  # MaxValue order
-            for fi, arr in enumerate(fields):
-                contrib = np.where(q, arr[f], 0).max(axis=1)
-                hit = anyq & (contrib == mx[fi, p])
-                wc[fi, p] = hit.sum()
-                if hit.any():
-                    wn[fi, p] = f[hit].min()
-        b.wit.copy_(torch.from_numpy(np.concatenate([wc, wn]).reshape(-1).view(np.int32)))
+        ref = witness_cases.reference(self.nodes, self.pods, self.lo, self.hi)
+        wit = np.concatenate([ref["wit_count"], ref["wit_node"]])
+        b.wit.copy_(torch.from_numpy(wit.reshape(-1).view(np.int32)))
         return b
 
     def witness_prepare(self, b):
