@@ -203,6 +203,31 @@ int yoda_update_alloc(yoda_t* h, const uint64_t* alloc_memory);
  * yoda_upload_pods + yoda_run + yoda_download. */
 int yoda_eval(yoda_t* h, const yoda_pod_soa* pods, int mode, yoda_eval_out* out);
 
+/* selectHost: when enabled, a pod whose cycle ends YODA_STATUS_OK with n_ties >= 2 gets as its
+ * pick the node of its tie set (the set n_ties counts) with the smallest draw word
+ * yoda_tie_hash(seed, pod_base + p, node), p = the pod's index in the uploaded batch (the
+ * CALLER's order), node = its GLOBAL id (node_offset + upload-order index).  Every other output
+ * (status, n_feasible, n_ties, top_score, maxima) and every other pod's pick are unchanged.
+ * Default: disabled (the lowest node of the set).  Takes effect from the next yoda_run/yoda_eval.
+ *
+ * The draw word, with mix64 the splitmix64 finalizer (x ^= x>>30; x *= 0xBF58476D1CE4E5B9;
+ * x ^= x>>27; x *= 0x94D049BB133111EB; x ^= x>>31) and fmix32 the murmur3 32-bit finalizer
+ * (h ^= h>>16; h *= 0x85EBCA6B; h ^= h>>13; h *= 0xC2B2AE35; h ^= h>>16):
+ *   s = mix64(seed + 0x9E3779B97F4A7C15 * (pod + 1))              (mod 2^64, once per pod)
+ *   yoda_tie_hash = fmix32(fmix32(node ^ lo32(s)) + hi32(s))      (mod 2^32)
+ * and the pick is the argmin of (hash << 32) | node over the tie set: a plain 64-bit MIN.  The
+ * word depends on (seed, pod, node) alone -- not on the chunking, the pod order, the
+ * block-grouped node order or the record path.  A caller that slices a batch across processes
+ * passes its slice's first index as pod_base (the slices' picks are then the unsliced batch's);
+ * one that wants fresh draws per batch changes the seed.  On the U64 record path the pods that
+ * go through the exact normalize draw over the nodes of the top NORMALIZED score.
+ * Only yoda_run / yoda_eval draw: yoda_shard_*, yoda_comm_*, yoda_greedy* and yoda_score_rows*
+ * keep the lowest-node rule whether or not the draw is enabled.
+ * YODA_ERR_INVALID_ARG on a NULL handle. */
+int yoda_set_tie_draw(yoda_t* h, int enable, uint64_t seed, uint64_t pod_base);
+/* Host only.  For fixed (seed, pod) a bijection of the 32-bit node ids: no two nodes share a word. */
+uint32_t yoda_tie_hash(uint64_t seed, uint64_t pod, uint32_t node);
+
 /* ---- split evaluation (device-resident timing, multi-GPU) --------------------------- */
 int yoda_upload_pods(yoda_t* h, const yoda_pod_soa* pods);
 /* Run filter+prescore+score+normalize+select for the uploaded pods; results stay on the

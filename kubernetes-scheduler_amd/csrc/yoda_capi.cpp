@@ -196,6 +196,12 @@ hipError_t launch_unpack_key(const uint64_t* key, uint32_t n_pods, uint32_t ib, 
                              uint32_t* idx, uint32_t* ties, int64_t* low, hipStream_t s);
 hipError_t launch_max_multi(const PtrList& src, uint32_t k, uint64_t n, uint64_t* dst,
                             hipStream_t s);
+hipError_t launch_draw(int K, Path path, int mode_diskio, const unsigned char* nodes,
+                       const NodeRecB* nodes_b, uint32_t n_nodes, const PodParams& pp,
+                       const double* rcp, const uint64_t* maxima, const int64_t* low,
+                       const uint64_t* bm, uint32_t bm_stride, const BlockMask* bs,
+                       uint32_t bs_stride, const uint64_t* blk, uint32_t blk_stride,
+                       const DrawArgs& a, hipStream_t s);
 size_t order_scratch_bytes(uint32_t n_pods);
 hipError_t launch_order_pods(const uint64_t* number, const uint64_t* m_u, const uint64_t* c_u,
                              const uint32_t* need_mem, uint32_t n_pods, const uint32_t key_bits[3],
@@ -535,6 +541,11 @@ struct yoda_handle {
   bool k1_rec_ok = false;  // k1_rec holds this run's records (written with the order)
   DevBuf k1_w, k1_order, k1_rec;  // (k1_rec: the waves' K1WaveRec records, beside k1_w)
   uint32_t C2 = 1, chunk2 = 32;  // K2 / K3 node chunking
+  // selectHost draw (yoda_set_tie_draw): yoda_run / yoda_eval draw each tied pod's pick after
+  // finalize (draw_pass); the listed sorted positions, their MIN keys, the list's length
+  bool tie_draw = false;
+  uint64_t tie_seed = 0, tie_pod_base = 0;
+  DevBuf draw_list, draw_keys, draw_n;
   int cap[2][3][2] = {};         // resident workgroups per (kernel, path, mode), cached
   int last_mode = -1;
   bool ran = false;
@@ -2957,7 +2968,48 @@ static void seed_report(yoda_t* h) {
                gap / std::max<uint32_t>(1, act_w - zero));
 }
 
-int yoda_run(yoda_t* h, int mode, uint32_t flags) {
+// The selectHost draw of a private run (yoda_set_tie_draw), after finalize: every per-pod output
+// is in the caller's order by now, while the pod arrays, the reciprocals, the masks and the
+// lowest scores are still in the run's sorted order (n_work positions, h->perm).
+static int draw_pass(yoda_t* h, int mode) {
+  const uint32_t W = h->n_work;
+  if (W == 0 || h->n_pods == 0 || h->n_nodes == 0) return YODA_OK;
+  HIP_TRY(h, h->draw_list.ensure((size_t)W * 4));
+  HIP_TRY(h, h->draw_keys.ensure((size_t)W * 8));
+  HIP_TRY(h, h->draw_n.ensure(16));
+  DrawArgs a{};
+  a.perm = h->ordered ? h->perm.as<uint32_t>() : nullptr;
+  a.n_work = W;
+  a.n_pods = h->n_pods;
+  a.status = h->status.as<int32_t>();
+  a.ties = h->ties_out.as<uint32_t>();
+  a.best = h->best.as<int64_t>();
+  a.pick = h->pick.as<int32_t>();
+  a.list = h->draw_list.as<uint32_t>();
+  a.n_list = h->draw_n.as<uint32_t>();
+  a.keys = h->draw_keys.as<unsigned long long>();
+  a.seed = h->tie_seed;
+  a.pod_base = h->tie_pod_base;
+  a.node_offset = h->node_offset;
+  const bool diskio = mode == YODA_MODE_DISKIO;
+  // (the U64 path's finalize scattered the maxima to the caller's order: unpermute_outputs)
+  if (!diskio && h->generic && h->maxima_sorted)
+    return fail(h, YODA_ERR_STATE, "draw pass: generic maxima still in sorted order");
+  HIP_TRY(h, launch_draw(h->K, h->path, diskio ? 1 : 0, h->nodes.as<unsigned char>(),
+                         h->nodes_b.as<NodeRecB>(), h->n_nodes, pod_params(h),
+                         h->rcp.as<double>(), h->maxima.as<uint64_t>(), h->lowest.as<int64_t>(),
+                         h->bitmask.as<uint64_t>(), bm_row(h->n_nodes), h->bs_ptr(),
+                         bs_row(h->n_nodes), h->blk_ptr(), blk_row(h->n_nodes), a, h->stream));
+  return YODA_OK;
+}
+
+// yoda_run; draw: the selectHost draw when the handle has it enabled (the greedy batch's own
+// runs pass false: it keeps the lowest-node rule).
+static int run_private(yoda_t* h, int mode, uint32_t flags, bool draw);
+
+int yoda_run(yoda_t* h, int mode, uint32_t flags) { return run_private(h, mode, flags, true); }
+
+static int run_private(yoda_t* h, int mode, uint32_t flags, bool draw) {
   if (!h) return YODA_ERR_INVALID_ARG;
   // a private run on the block kernels in the counting order reads only the pod arrays the
   // upload copied first; the rest of the batch goes to the device after its kernels
@@ -2994,6 +3046,7 @@ int yoda_run(yoda_t* h, int mode, uint32_t flags) {
     h->core_only = false;
     if (defer && side && h->copy_stream && (rc = pods_complete_async(h))) return rc;
     if (defer && (rc = pods_complete(h))) return rc;
+    if (draw && h->tie_draw && (rc = draw_pass(h, mode))) return rc;
     h->ran = true;
     h->ran_bitmask = mode == YODA_MODE_SCV && (flags & YODA_RUN_BITMASK);
     h->last_mode = mode;
@@ -3167,6 +3220,18 @@ int yoda_eval(yoda_t* h, const yoda_pod_soa* pods, int mode, yoda_eval_out* out)
   if (rc) return rc;
   if ((rc = yoda_run(h, mode, 0))) return rc;
   return yoda_download(h, out);
+}
+
+int yoda_set_tie_draw(yoda_t* h, int enable, uint64_t seed, uint64_t pod_base) {
+  if (!h) return YODA_ERR_INVALID_ARG;
+  h->tie_draw = enable != 0;
+  h->tie_seed = seed;
+  h->tie_pod_base = pod_base;
+  return YODA_OK;
+}
+
+uint32_t yoda_tie_hash(uint64_t seed, uint64_t pod, uint32_t node) {
+  return tie_word(tie_pod_state(seed, pod), node);
 }
 
 // ---- sharded entry points -------------------------------------------------------------
@@ -3578,7 +3643,7 @@ int greedy_eval_one(GreedyState& g, const yoda_pod_soa* pods, uint32_t p, int mo
   PodGather one;
   one.build(pods, &p, 1);
   if ((rc = yoda_upload_pods(h, &one.soa))) return rc;
-  if ((rc = yoda_run(h, mode, 0))) return rc;
+  if ((rc = run_private(h, mode, 0, false))) return rc;
   HIP_TRY(h, h->pick_stage.ensure(16));
   HIP_TRY(h, hipMemcpyAsync(h->pick_stage.p, h->pick.p, 4, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -3671,7 +3736,8 @@ int yoda_greedy(yoda_t* h, const yoda_pod_soa* pods, int mode, uint32_t flags, i
     if (mode == YODA_MODE_DISKIO) {  // Mode B reads no assumed-pod state: independent cycles
       PodGather all;
       all.build(pods, order.data(), P);
-      if ((rc = yoda_upload_pods(h, &all.soa)) || (rc = yoda_run(h, mode, 0))) return rc;
+      if ((rc = yoda_upload_pods(h, &all.soa)) || (rc = run_private(h, mode, 0, false)))
+        return rc;
       std::vector<int32_t> pk(P);
       // the handle's stream may be non-blocking: copy and wait on it, not on the null stream
       HIP_TRY(h, hipMemcpyAsync(pk.data(), h->pick.p, P * 4ull, hipMemcpyDeviceToHost, h->stream));

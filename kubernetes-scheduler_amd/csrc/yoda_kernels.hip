@@ -13,6 +13,8 @@
 //                          argmax/ties/min for NormalizeScore + selectHost
 //   K2B k2_diskio          algorithm.go:99-119 (live Mode B)
 //   K3  k3_exact_normalize scheduler.go:176-179 with int64 wrap (generic path only)
+//       k_draw_*           k8s selectHost as a seeded draw over each tied pod's tie set (a
+//                          post-pass with LANE = NODE, only with yoda_set_tie_draw enabled)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <algorithm>
@@ -6267,6 +6269,221 @@ hipError_t launch_max_multi(const PtrList& src, uint32_t k, uint64_t n, uint64_t
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_max_multi, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
                      src, k, n, dst);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
+// The selectHost draw (include/yoda.h yoda_set_tie_draw; DESIGN.md §2 "Tie-break"): a post-pass
+// of a private run, after finalize.  k_draw_list compacts the sorted positions whose pod ended
+// OK with >= 2 ties; a draw kernel rescans each listed pod's feasible nodes with the run's exact
+// per-pair scorer, LANE = NODE, and folds the MIN key (tie_key: draw word << 32 | global node)
+// of the nodes whose score equals the pod's best into keys[slot]; k_draw_write puts the key's
+// node into pick at the pod's caller-order slot.  A padded order lists both copies of a pod:
+// they hash the same caller index, so both write the same node.
+__global__ __launch_bounds__(kBlock) void k_draw_list(DrawArgs a) {
+  const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+  if (p >= a.n_work) return;
+  const uint32_t o = a.perm ? a.perm[p] : p;
+  if (o >= a.n_pods || a.status[o] != 0 || a.ties[o] < 2u) return;
+  const uint32_t i = atomicAdd(a.n_list, 1u);
+  a.list[i] = p;
+  a.keys[i] = ~0ull;
+}
+
+// Filter result of (sorted position p = 64 w + l, node position pos) from either mask form.
+__device__ __forceinline__ bool draw_feasible(const MaskSrc& m, uint32_t w, uint32_t l,
+                                              uint32_t pos) {
+  if (m.bs) {
+    if (!blk_listed(m.blk, m.blk_stride, w, pos >> 6)) return false;
+    const BlockMask b = m.bs[(size_t)w * m.bs_stride + (pos >> 6)];
+    const uint32_t j = pos & 63u;
+    if ((b.full >> j) & 1ull) return true;  // every live pod of the wave
+    if (!((b.nz >> j) & 1ull)) return false;
+  }
+  return (m.bm[(size_t)w * m.bm_stride + pos] >> l) & 1ull;
+}
+
+// The block's MIN key into keys[slot]: waves through shuffles, one atomic per wave with a key.
+__device__ __forceinline__ void draw_fold(unsigned long long* keys, uint32_t slot, uint64_t key) {
+#pragma unroll
+  for (int o = kWave / 2; o > 0; o >>= 1) {
+    const uint64_t other = __shfl_xor(key, o, kWave);
+    key = other < key ? other : key;
+  }
+  if (lane_id() == 0 && key != ~0ull) atomicMin(keys + slot, (unsigned long long)key);
+}
+
+// Fast record paths (N32 / F64): workgroup = (a stride of the list, node chunk blockIdx.y).
+// ids: the local node id of each position in the block-grouped order (nullptr: identity).
+template <int K, Path PATH>
+__global__ __launch_bounds__(kBlock) void k_draw_fast(const unsigned char* __restrict__ nodes,
+                                                      uint32_t n_nodes, uint32_t chunk_nodes,
+                                                      ScoreArgs sa, const MaskSrc ms, DrawArgs a) {
+  const uint32_t nl = min(*a.n_list, a.n_work);
+  const uint32_t n0 = blockIdx.y * chunk_nodes;
+  const uint32_t n1 = min(n0 + chunk_nodes, n_nodes);
+  constexpr uint32_t stride = PATH == Path::N32 ? n32_stride(K) : node_stride(K);
+  for (uint32_t i = blockIdx.x; i < nl; i += gridDim.x) {
+    const uint32_t p = a.list[i];
+    const uint32_t o = a.perm ? a.perm[p] : p;
+    const double best = (double)a.best[o];
+    const uint64_t st = tie_pod_state(a.seed, a.pod_base + o);
+    Scorer<PATH> sc;
+    sc.load(sa, p, a.n_work);
+    uint64_t key = ~0ull;
+    for (uint32_t pos = n0 + threadIdx.x; pos < n1; pos += kBlock) {
+      if (!draw_feasible(ms, p >> 6, p & 63u, pos)) continue;
+      const uint32_t n = sa.ids ? sa.ids[pos] : pos;
+      const double raw = sc.template raw<K>(nodes + (size_t)n * stride);
+      if (raw == best) {
+        const uint64_t k = tie_key(st, a.node_offset + n);
+        key = k < key ? k : key;
+      }
+    }
+    draw_fold(a.keys, i, key);
+  }
+}
+
+// U64 record path: one workgroup per listed pod over all nodes.  A pod finalize sent through the
+// exact normalize (the same test as k_finalize's) draws over the nodes of the top NORMALIZED
+// score, as k3_exact_normalize counts them: one sweep for that score, one for the keys.
+// maxima / best: caller order [6][n_pods] / [n_pods]; low: the run's sorted order.
+template <int K>
+__global__ __launch_bounds__(kBlock) void k_draw_generic(
+    const unsigned char* __restrict__ nodes, uint32_t n_nodes, const uint64_t* __restrict__ m_u,
+    const uint64_t* __restrict__ c_u, const uint64_t* __restrict__ maxima,
+    const int64_t* __restrict__ low, const MaskSrc ms, DrawArgs a) {
+  __shared__ int64_t s_norm[kBlock / kWave];
+  const uint32_t nl = min(*a.n_list, a.n_work);
+  for (uint32_t i = blockIdx.x; i < nl; i += gridDim.x) {
+    const uint32_t p = a.list[i];
+    const uint32_t o = a.perm ? a.perm[p] : p;
+    const uint64_t m = m_u[p], c = c_u[p];
+    uint64_t M[6];
+#pragma unroll
+    for (int f = 0; f < 6; ++f) M[f] = maxima[(size_t)f * a.n_pods + o];
+    const int64_t h = a.best[o];
+    int64_t l = low[p];
+    if (h == l) --l;  // scheduler.go:173-175
+    const int64_t d = h - l;
+    const bool exact = (uint64_t)d > (uint64_t)(kI64Max / 100);
+    const uint64_t st = tie_pod_state(a.seed, a.pod_base + o);
+    int64_t top = h;
+    if (exact) {  // the top normalized score (block-uniform branch: i is)
+      int64_t bn = -1;
+      for (uint32_t n = threadIdx.x; n < n_nodes; n += kBlock) {
+        if (!draw_feasible(ms, p >> 6, p & 63u, n)) continue;
+        const int64_t s = raw_score_u64<K>(nodes + (size_t)n * node_stride(K), m, c, M);
+        const int64_t norm = (int64_t)((uint64_t)(s - l) * 100u) / d;  // scheduler.go:178
+        bn = norm > bn ? norm : bn;
+      }
+#pragma unroll
+      for (int x = kWave / 2; x > 0; x >>= 1) {
+        const int64_t other = __shfl_xor(bn, x, kWave);
+        bn = other > bn ? other : bn;
+      }
+      if (lane_id() == 0) s_norm[threadIdx.x >> 6] = bn;
+      __syncthreads();
+      top = s_norm[0];
+      for (int k = 1; k < kBlock / kWave; ++k) top = s_norm[k] > top ? s_norm[k] : top;
+      __syncthreads();
+    }
+    uint64_t key = ~0ull;
+    for (uint32_t n = threadIdx.x; n < n_nodes; n += kBlock) {
+      if (!draw_feasible(ms, p >> 6, p & 63u, n)) continue;
+      const int64_t s = raw_score_u64<K>(nodes + (size_t)n * node_stride(K), m, c, M);
+      const int64_t v = exact ? (int64_t)((uint64_t)(s - l) * 100u) / d : s;
+      if (v == top) {
+        const uint64_t k = tie_key(st, a.node_offset + n);
+        key = k < key ? k : key;
+      }
+    }
+    draw_fold(a.keys, i, key);
+  }
+}
+
+// Mode B: every node is feasible; the score of k2_diskio (algorithm.go:109-111, no FMA).
+__global__ __launch_bounds__(kBlock) void k_draw_diskio(const NodeRecB* __restrict__ nodes,
+                                                        uint32_t n_nodes, uint32_t chunk_nodes,
+                                                        const double* __restrict__ alpha_in,
+                                                        const double* __restrict__ beta_in,
+                                                        DrawArgs a) {
+#pragma clang fp contract(off)
+  const uint32_t nl = min(*a.n_list, a.n_work);
+  const uint32_t n0 = blockIdx.y * chunk_nodes;
+  const uint32_t n1 = min(n0 + chunk_nodes, n_nodes);
+  for (uint32_t i = blockIdx.x; i < nl; i += gridDim.x) {
+    const uint32_t p = a.list[i];
+    const uint32_t o = a.perm ? a.perm[p] : p;
+    const double best = (double)a.best[o];
+    const double alpha = alpha_in[p], beta = beta_in[p];
+    const uint64_t st = tie_pod_state(a.seed, a.pod_base + o);
+    uint64_t key = ~0ull;
+    for (uint32_t n = n0 + threadIdx.x; n < n1; n += kBlock) {
+      const NodeRecB r = nodes[n];
+      const double x = alpha * r.v;
+      const double y = beta * r.u;
+      const double l = fabs(x - y);  // :110
+      const double t = 10.0 * l;
+      const double s = 10.0 - t;     // :111
+      const double score = (s >= 1.0) ? __builtin_trunc(s) : 0.0;
+      if (score == best) {
+        const uint64_t k = tie_key(st, a.node_offset + n);
+        key = k < key ? k : key;
+      }
+    }
+    draw_fold(a.keys, i, key);
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void k_draw_write(DrawArgs a) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= min(*a.n_list, a.n_work)) return;
+  const uint32_t p = a.list[i];
+  const uint32_t o = a.perm ? a.perm[p] : p;
+  const uint64_t k = a.keys[i];
+  if (k != ~0ull) a.pick[o] = (int32_t)(uint32_t)k;
+}
+
+// Nodes per draw chunk (a multiple of the workgroup) and the most list strides of a launch: the
+// list's length stays on the device (no host round trip), so the grid cannot be sized by it --
+// at most this many workgroups a chunk stride over the list, and with a short list (the usual
+// case: few pods tie) the others return at once.
+constexpr uint32_t kDrawChunk = 8 * kBlock;
+constexpr uint32_t kDrawMaxStrides = 256;
+
+hipError_t launch_draw(int K, Path path, int mode_diskio, const unsigned char* nodes,
+                       const NodeRecB* nodes_b, uint32_t n_nodes, const PodParams& pp,
+                       const double* rcp, const uint64_t* maxima, const int64_t* low,
+                       const uint64_t* bm, uint32_t bm_stride, const BlockMask* bs,
+                       uint32_t bs_stride, const uint64_t* blk, uint32_t blk_stride,
+                       const DrawArgs& a, hipStream_t s) {
+  if (a.n_work == 0 || n_nodes == 0) return hipSuccess;
+  if (bs && !blk) return hipErrorInvalidValue;  // sparse masks are read through their block list
+  hipError_t e = hipMemsetAsync(a.n_list, 0, 4, s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_draw_list, pod_grid(a.n_work), dim3(kBlock), 0, s, a);
+  const uint32_t gx = std::min(a.n_work, kDrawMaxStrides);
+  const uint32_t C = (n_nodes + kDrawChunk - 1) / kDrawChunk;
+  const MaskSrc ms{bm, bs, bm_stride, bs_stride, blk, blk_stride};
+  if (mode_diskio) {
+    hipLaunchKernelGGL(k_draw_diskio, dim3(gx, C), dim3(kBlock), 0, s, nodes_b, n_nodes,
+                       kDrawChunk, pp.alpha, pp.beta, a);
+  } else if (path == Path::U64) {
+    YODA_K_SWITCH(K, hipLaunchKernelGGL((k_draw_generic<KK>), dim3(gx), dim3(kBlock), 0, s, nodes,
+                                        n_nodes, pp.m_u, pp.c_u, maxima, low, ms, a));
+  } else {
+    ScoreArgs sa{pp.m_f, pp.c_f, pp.m_32, pp.c_32, rcp};
+    sa.ids = pp.ids;
+    if (path == Path::N32) {
+      YODA_K_SWITCH(K, hipLaunchKernelGGL((k_draw_fast<KK, Path::N32>), dim3(gx, C), dim3(kBlock),
+                                          0, s, nodes, n_nodes, kDrawChunk, sa, ms, a));
+    } else {
+      YODA_K_SWITCH(K, hipLaunchKernelGGL((k_draw_fast<KK, Path::F64>), dim3(gx, C), dim3(kBlock),
+                                          0, s, nodes, n_nodes, kDrawChunk, sa, ms, a));
+    }
+  }
+  hipLaunchKernelGGL(k_draw_write, pod_grid(a.n_work), dim3(kBlock), 0, s, a);
   return hipGetLastError();
 }
 

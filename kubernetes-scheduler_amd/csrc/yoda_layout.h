@@ -541,4 +541,55 @@ struct PermTable {
   uint32_t n;
 };
 
+// selectHost draw (include/yoda.h yoda_set_tie_draw): the draw word of (seed, pod, node) and the
+// 64-bit key (word << 32 | node) whose MIN over a pod's tie set is its pick.  mix64: the
+// splitmix64 finalizer; fmix32: the murmur3 32-bit finalizer (a bijection of the u32, so for
+// one pod no two nodes share a word).  The host (yoda_tie_hash) and the draw kernels both
+// compute it from here.
+__host__ __device__ inline uint64_t tie_mix64(uint64_t x) {
+  x ^= x >> 30;
+  x *= 0xBF58476D1CE4E5B9ull;
+  x ^= x >> 27;
+  x *= 0x94D049BB133111EBull;
+  x ^= x >> 31;
+  return x;
+}
+__host__ __device__ inline uint32_t tie_fmix32(uint32_t h) {
+  h ^= h >> 16;
+  h *= 0x85EBCA6Bu;
+  h ^= h >> 13;
+  h *= 0xC2B2AE35u;
+  h ^= h >> 16;
+  return h;
+}
+// once per pod: the pod's 64-bit state s
+__host__ __device__ inline uint64_t tie_pod_state(uint64_t seed, uint64_t pod) {
+  return tie_mix64(seed + 0x9E3779B97F4A7C15ull * (pod + 1ull));
+}
+__host__ __device__ inline uint32_t tie_word(uint64_t s, uint32_t node) {
+  return tie_fmix32(tie_fmix32(node ^ (uint32_t)s) + (uint32_t)(s >> 32));
+}
+__host__ __device__ inline uint64_t tie_key(uint64_t s, uint32_t node) {
+  return ((uint64_t)tie_word(s, node) << 32) | node;
+}
+
+// The draw pass of a private run (yoda_run with the draw enabled), after finalize.  The run's
+// pods are its n_work sorted positions (perm[p] = the caller's index of position p; nullptr:
+// the run was not ordered); status / ties / best / pick are the finalized outputs in the
+// CALLER's order.  list [n_work] gets the positions that draw (status OK, ties >= 2), keys
+// [n_work] their running MIN key by list slot.
+struct DrawArgs {
+  const uint32_t* perm;
+  uint32_t n_work, n_pods;
+  const int32_t* status;
+  const uint32_t* ties;
+  const int64_t* best;
+  int32_t* pick;
+  uint32_t* list;
+  uint32_t* n_list;
+  unsigned long long* keys;
+  uint64_t seed, pod_base;
+  uint32_t node_offset;
+};
+
 }  // namespace yoda

@@ -410,6 +410,27 @@ func (g *Handle) Batch(pods []*v1.Pod, mode Mode) (picks []int32, statuses []int
 	return append([]int32(nil), pk...), append([]int32(nil), st...), nil
 }
 
+// SetTieDraw turns the seeded selectHost draw of Batch on or off (yoda_set_tie_draw): when
+// enabled, a pod that ends StatusOK with two or more top-scored nodes is placed on the one with
+// the smallest TieHash(seed, podBase+p, node) -- p its index in the batch, node the global node
+// id -- instead of the lowest.  podBase: the global index of the batch's first pod when the
+// caller slices a larger batch.  ScoreRow, Greedy and the sharded entry points keep the
+// lowest node either way.  Takes effect from the next Batch.
+func (g *Handle) SetTieDraw(enable bool, seed, podBase uint64) error {
+	on := C.int(0)
+	if enable {
+		on = 1
+	}
+	return check(g.h, C.yoda_set_tie_draw(g.h, on, C.uint64_t(seed), C.uint64_t(podBase)),
+		"yoda_set_tie_draw")
+}
+
+// TieHash is the draw word of (seed, pod, node) (yoda_tie_hash; host only): for one pod a
+// bijection of the 32-bit node ids.
+func TieHash(seed, pod uint64, node uint32) uint32 {
+	return uint32(C.yoda_tie_hash(C.uint64_t(seed), C.uint64_t(pod), C.uint32_t(node)))
+}
+
 // Greedy schedules the pods one after another in sort.Less order, each pick updating the
 // node's Allocate score (config 5); cardCapacity also decrements CardNumber.
 func (g *Handle) Greedy(pods []*v1.Pod, mode Mode, cardCapacity bool) ([]int32, error) {

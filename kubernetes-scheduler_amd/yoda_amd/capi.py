@@ -45,6 +45,8 @@ _SIGS = {
     "yoda_score_bound": ([_vp], C.c_uint64),
     "yoda_update_alloc": ([_vp, C.POINTER(C.c_uint64)], C.c_int),
     "yoda_eval": ([_vp, C.POINTER(CPodSoA), C.c_int, C.POINTER(CEvalOut)], C.c_int),
+    "yoda_set_tie_draw": ([_vp, C.c_int, C.c_uint64, C.c_uint64], C.c_int),
+    "yoda_tie_hash": ([C.c_uint64, C.c_uint64, _u32], C.c_uint32),
     "yoda_upload_pods": ([_vp, C.POINTER(CPodSoA)], C.c_int),
     "yoda_run": ([_vp, C.c_int, _u32], C.c_int),
     "yoda_download": ([_vp, C.POINTER(CEvalOut)], C.c_int),
@@ -253,6 +255,16 @@ class Yoda:
         self.n_pods = self._pods.n_pods
 
     # ---- evaluation --------------------------------------------------------------------
+    def set_tie_draw(self, seed: Optional[int], pod_base: int = 0):
+        """selectHost (yoda_set_tie_draw): with a seed, run() / eval() draw each tied pod's pick
+        among its top-scored nodes -- the node with the smallest tie_hash(seed, pod_base + p,
+        node) -- instead of taking the lowest one; None turns the draw off.  pod_base: the
+        global index of this batch's first pod (a slice of a larger batch)."""
+        on = seed is not None
+        self._check(lib().yoda_set_tie_draw(self._h, 1 if on else 0,
+                                            int(seed) & (2**64 - 1) if on else 0,
+                                            int(pod_base) & (2**64 - 1)), "yoda_set_tie_draw")
+
     def run(self, mode: int = 0, bitmask: bool = False):
         self._check(lib().yoda_run(self._h, mode, 1 if bitmask else 0), "yoda_run")
 
@@ -771,6 +783,12 @@ class GreedySession:
         self._check(lib().yoda_gs_picks(self._g, _np_ptr(pick), C.byref(r), C.byref(a)),
                     "yoda_gs_picks")
         return pick[:self.n_pods], r.value, a.value
+
+
+def tie_hash(seed: int, pod: int, node: int) -> int:
+    """The selectHost draw word of (seed, pod, node) (yoda_tie_hash; host only, no GPU)."""
+    return int(lib().yoda_tie_hash(int(seed) & (2**64 - 1), int(pod) & (2**64 - 1),
+                                   int(node) & 0xFFFFFFFF))
 
 
 def header_symbols(path: str = HEADER_PATH):
