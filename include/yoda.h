@@ -355,7 +355,7 @@ int yoda_set_pod_order(yoda_t* h, int enable);
 int yoda_order_info(const yoda_t* h, uint32_t* out);
 /* The node snapshot's order in private runs (diagnostic): *grouped = 1 when its one-model nodes
  * are dealt into 64-node blocks of one clock for yoda_run (copies of the summaries in that
- * order; YODA_NODE_PERM=0 disables), 0 when the upload order is used. */
+ * order), 0 when the upload order is used. */
 int yoda_node_order(const yoda_t* h, uint32_t* grouped);
 
 /* ---- kernel timing ----------------------------------------------------------------- */

@@ -27,194 +27,9 @@
 
 #include "../../include/yoda.h"
 #include "yoda_layout.h"
+#include "yoda_launch.h"
 #include "yoda_node_pack.h"
 
-namespace yoda {
-// launchers (yoda_kernels.hip)
-hipError_t launch_k1(int K, Path path, const unsigned char* nodes, const unsigned char* sum,
-                     const unsigned char* sum2, const unsigned char* mix,
-                     uint32_t n_nodes, uint32_t chunk_nodes, uint32_t C, const PodParams& pp,
-                     uint32_t n_pods, const Partials& part, uint64_t* bm, uint32_t bm_stride,
-                     BlockMask* bs, uint32_t bs_stride, uint64_t* blk, uint32_t blk_stride,
-                     unsigned long long* stats, hipStream_t s, uint32_t sub);
-hipError_t launch_reduce1(const Partials& part, uint32_t C, uint32_t n_pods, uint32_t nw,
-                          uint64_t* maxima, uint32_t* counts, double* rcp,
-                          const MemTab& mt, hipStream_t s,
-                          uint32_t* lpt_w = nullptr, uint32_t* lpt_order = nullptr,
-                          const uint64_t* cmask = nullptr);
-hipError_t launch_k1_order(int K, const PodParams& pp, uint32_t n_pods, uint32_t n_nodes,
-                           uint32_t* wts, uint32_t* order, K1WaveRec* rec, hipStream_t s);
-hipError_t launch_mem_rank(const uint64_t* m_u, uint32_t n_pods, const MemTab& mt, uint32_t* m32,
-                           hipStream_t s);
-hipError_t launch_prep2(const uint64_t* maxima, uint32_t n_pods, double* rcp,
-                        hipStream_t s);
-hipError_t launch_window_out(const uint32_t* counts, const uint64_t* maxima, const uint32_t* wit,
-                             const double* tk_s, const uint32_t* tk_i, const uint32_t* perm,
-                             uint32_t wn, uint32_t kt, bool lists_row_major, unsigned char* out,
-                             uint32_t* inv_scratch, hipStream_t s);
-hipError_t launch_k2(int K, Path path, const unsigned char* nodes, const unsigned char* sum2,
-                     const uint64_t* blk, uint32_t blk_stride, uint32_t n_nodes,
-                     uint32_t chunk_nodes, uint32_t C, const PodParams& pp, const uint64_t* maxima,
-                     const double* rcp, uint32_t n_pods,
-                     const uint64_t* bm, uint32_t bm_stride, const BlockMask* bs,
-                     uint32_t bs_stride, const Partials& part, int64_t* rows,
-                     unsigned long long* stats, const uint32_t* counts, hipStream_t s);
-hipError_t launch_k2b_rows(const NodeRecB* nodes, uint32_t n_nodes, const PodParams& pp,
-                           uint32_t n_pods, const Partials& part, int64_t* rows, hipStream_t s);
-hipError_t launch_k2_diskio(const NodeRecB* nodes, uint32_t n_nodes, uint32_t chunk_nodes,
-                            uint32_t C, const PodParams& pp, uint32_t n_pods, const Partials& part,
-                            int64_t* rows, hipStream_t s);
-DiskPlan diskio_plan(uint32_t n_nodes, uint32_t n_cls);
-hipError_t launch_k2b(const NodeRecB* nodes, uint32_t n_nodes, const double* cab,
-                      uint32_t n_cls, const DiskLevels& lv, const DiskPlan& pl, uint32_t* plc,
-                      uint32_t* pidx, hipStream_t s);
-hipError_t launch_reduce2b(const uint32_t* plc, const uint32_t* pidx, uint32_t C, uint32_t n_cls,
-                           const uint32_t* cls, uint32_t n_pods, uint32_t node_offset,
-                           int64_t* best, uint32_t* idx, uint32_t* ties, int64_t* low,
-                           hipStream_t s);
-hipError_t launch_rows_transpose(const int64_t* in, uint32_t n_nodes, uint32_t n_pods,
-                                 const uint32_t* perm,
-                                 int64_t* out, hipStream_t s);
-hipError_t launch_reduce2(const Partials& part, uint32_t C, uint32_t n_pods, bool is_f64,
-                          uint32_t node_offset, int64_t* best, uint32_t* idx, uint32_t* ties,
-                          int64_t* low, hipStream_t s, const uint64_t* cmask = nullptr);
-hipError_t launch_merge_prepare(const int64_t* best_global, const int64_t* best_local,
-                                uint32_t n_pods, uint32_t* idx, uint32_t* ties, hipStream_t s);
-hipError_t launch_fill_diskio_state(uint32_t n_pods, uint32_t n_nodes, uint64_t* maxima,
-                                    uint32_t* counts, hipStream_t s);
-hipError_t launch_finalize(const uint32_t* counts, const int64_t* best, const uint32_t* idx,
-                           const uint32_t* ties_in, const int64_t* lowest, uint32_t n_pods,
-                           bool generic, int32_t* pick, int32_t* status, uint32_t* ties_out,
-                           uint32_t* flagged, uint32_t* n_flagged, const FinalScatter& sc,
-                           hipStream_t s);
-hipError_t launch_k3(int K, const unsigned char* nodes, uint32_t n_nodes, uint32_t chunk_nodes,
-                     uint32_t C, const PodParams& pp, const uint64_t* maxima, uint32_t n_pods,
-                     const uint64_t* bm, uint32_t bm_stride, const uint32_t* flagged,
-                     const uint32_t* n_flagged,
-                     const int64_t* best, const int64_t* low, const Partials& part,
-                     uint32_t max_flagged, hipStream_t s);
-hipError_t launch_reduce3_rec(const Partials& part, uint32_t C, const uint32_t* flagged,
-                              const uint32_t* n_flagged, uint32_t max_flagged,
-                              uint32_t node_offset, ShardRec* rec, hipStream_t s);
-hipError_t launch_merge3(const ShardRec* all, uint32_t n_pods, uint32_t world,
-                         const uint32_t* flagged, const uint32_t* n_flagged, uint32_t max_flagged,
-                         int32_t* pick, int32_t* status, uint32_t* ties, hipStream_t s);
-hipError_t launch_reduce3(const Partials& part, uint32_t C, const uint32_t* flagged,
-                          const uint32_t* n_flagged, uint32_t max_flagged, uint32_t node_offset,
-                          int32_t* pick, int32_t* status, uint32_t* ties, hipStream_t s);
-hipError_t launch_bitmask_transpose(const uint64_t* bm, uint32_t bm_stride, const BlockMask* bs,
-                                    uint32_t bs_stride, const uint64_t* blk, uint32_t blk_stride,
-                                    uint32_t n_nodes,
-                                    uint32_t W, uint32_t n_pods, const uint32_t* perm,
-                                    uint32_t* out, hipStream_t s);
-int kernel_capacity(int K, Path path, int which, int mode_diskio);
-hipError_t launch_k2_topk(int K, Path path, const unsigned char* nodes, uint32_t n_nodes,
-                          uint32_t chunk_nodes, uint32_t C, const PodParams& pp,
-                          const double* rcp, uint32_t n_pods,
-                          const uint64_t* bm, uint32_t bm_stride, const BlockMask* bs,
-                          uint32_t bs_stride, const uint64_t* blk, uint32_t blk_stride,
-                          const Partials& part, double* tk_s, uint32_t* tk_i, int tk,
-                          hipStream_t s);
-hipError_t launch_topk_merge(const double* tk_s, const uint32_t* tk_i, uint32_t C,
-                             uint32_t n_pods, uint32_t node_offset, double* out_s,
-                             uint32_t* out_i, int tk, hipStream_t s);
-hipError_t launch_k2_topk_block(int K, const unsigned char* nodes, const unsigned char* sum2,
-                                const uint64_t* blk, uint32_t blk_stride, uint32_t n_nodes,
-                                uint32_t chunk_nodes, uint32_t C, const PodParams& pp,
-                                const double* rcp, uint32_t n_pods,
-                                const uint64_t* bm, uint32_t bm_stride, const BlockMask* bs,
-                                uint32_t bs_stride, const uint32_t* counts, uint64_t* keys,
-                                uint32_t ib, int tk, hipStream_t s);
-hipError_t launch_topk_merge_deep(const uint64_t* keys, uint32_t C, uint32_t n_pods, uint32_t ib,
-                                  uint32_t node_offset, double* out_s, uint32_t* out_i, int tk,
-                                  int ko, hipStream_t s);
-hipError_t launch_topk_merge_keys(const uint64_t* keys, uint32_t C, uint32_t n_pods, uint32_t ib,
-                                  uint32_t node_offset, double* out_s, uint32_t* out_i, int tk,
-                                  hipStream_t s);
-hipError_t launch_set_static(unsigned char* nodes, uint32_t stride, const uint32_t* node,
-                             const uint64_t* value, const uint64_t* card_number, uint32_t count,
-                             unsigned char* sum, uint32_t sum_stride, unsigned char* sum2,
-                             uint32_t sum2_stride, const PermCopy& pc, hipStream_t s);
-hipError_t launch_bsum_cn(const unsigned char* sum, uint32_t sum_stride, uint32_t n_nodes,
-                          uint32_t* bsum, uint32_t bsw, hipStream_t s);
-hipError_t launch_set_cards(unsigned char* nodes, uint32_t stride, const uint32_t* node,
-                            const uint32_t* rows, uint32_t row_words, uint32_t count, int K,
-                            uint32_t* sum, uint32_t* sum2, uint32_t* mix, uint32_t* x1,
-                            const PermCopy& pc, hipStream_t s);
-hipError_t launch_bsum_build(int K, const uint32_t* sum, const uint32_t* sum2, const uint32_t* x1,
-                             const uint32_t* mix, uint32_t n_nodes, uint32_t* bsum,
-                             hipStream_t s);
-hipError_t launch_block_ub(int K, const uint32_t* sum2, const uint32_t* tab, uint32_t n_nodes,
-                           uint32_t* out, const uint32_t* levels, hipStream_t s);
-hipError_t launch_block_dec(int K, const uint32_t* sum2, const uint32_t* mix, uint32_t n_nodes,
-                            uint32_t* out, const uint32_t* levels, MemTab mt, hipStream_t s);
-hipError_t launch_gtable(int K, const uint32_t* sum2, const uint32_t* mix, uint32_t n_nodes,
-                         const uint64_t* g_max,
-                         uint32_t* tab, uint32_t* rcp_out, MemTab mt, hipStream_t s);
-int topk_k();
-int topk_k_capacity();
-uint32_t greedy_one_blocks();
-hipError_t launch_greedy_one(int K, Path path, const unsigned char* nodes,
-                             const unsigned char* sum2, uint32_t n_nodes,
-                             const PodParams& pp, const double* rcp,
-                             uint32_t n_pods, uint32_t s, const uint64_t* bm, uint32_t bm_stride,
-                             const BlockMask* bs, uint32_t bs_stride, const uint64_t* blk,
-                             uint32_t blk_stride, double* part_s, uint32_t* part_i, uint32_t* done, uint32_t* out,
-                             hipStream_t st);
-hipError_t launch_k1_witness(int K, Path path, const unsigned char* nodes, uint32_t n_nodes,
-                             uint32_t chunk_nodes, uint32_t C, const PodParams& pp,
-                             uint32_t n_pods, uint64_t* pmax, uint32_t* pwit, uint32_t* pcnt,
-                             uint64_t* bm, uint32_t bm_stride, hipStream_t s);
-hipError_t launch_k1_block_witness(int K, const unsigned char* nodes, const unsigned char* sum,
-                                   const unsigned char* sum2, const unsigned char* mix,
-                                   uint32_t n_nodes, uint32_t chunk_nodes, uint32_t C,
-                                   const PodParams& pp, uint32_t n_pods, uint64_t* pmax,
-                                   uint32_t* pwit, uint32_t* pcnt, uint64_t* bm,
-                                   uint32_t bm_stride, BlockMask* bs, uint32_t bs_stride,
-                                   uint64_t* blk, uint32_t blk_stride, hipStream_t s);
-hipError_t launch_reduce_wit(const uint64_t* pmax, const uint32_t* pwit, const uint32_t* pcnt,
-                             uint32_t C, uint32_t n_pods, uint32_t node_offset, uint64_t* maxima,
-                             uint32_t* counts, uint32_t* wcount, uint32_t* wnode, const MemTab& mt, hipStream_t s);
-hipError_t launch_wit_prepare(const uint64_t* gmax, const uint64_t* lmax, uint32_t n_pods,
-                              uint32_t* wit, hipStream_t s);
-uint32_t one_blocks();
-hipError_t launch_one(int K, Path path, const unsigned char* nodes, uint32_t n_nodes,
-                      const OnePod& pod, uint64_t* feas, void* part, uint32_t* done,
-                      OneOut* out, const MemTab& mt, hipStream_t s);
-hipError_t launch_norm_rows(const int64_t* rows, uint32_t n_nodes, uint32_t n_pods,
-                            const int64_t* best, const int64_t* lowest, int64_t* norm,
-                            hipStream_t s);
-hipError_t launch_pack_rec(const int64_t* best, const uint32_t* idx, const uint32_t* ties,
-                           const int64_t* low, uint32_t n_pods, ShardRec* rec, hipStream_t s);
-hipError_t launch_merge_rec(const ShardRec* all, uint32_t n_pods, uint32_t world, int64_t* best,
-                            uint32_t* idx, uint32_t* ties, int64_t* low, hipStream_t s);
-hipError_t launch_sum_multi_u32(const PtrList& src, uint32_t k, uint64_t n, uint32_t* dst,
-                                hipStream_t s);
-hipError_t launch_pack_key(const int64_t* best, const uint32_t* idx, uint32_t n_pods, uint32_t ib,
-                           uint64_t* key, hipStream_t s);
-hipError_t launch_unpack_key(const uint64_t* key, uint32_t n_pods, uint32_t ib, int64_t* best,
-                             uint32_t* idx, uint32_t* ties, int64_t* low, hipStream_t s);
-hipError_t launch_max_multi(const PtrList& src, uint32_t k, uint64_t n, uint64_t* dst,
-                            hipStream_t s);
-hipError_t launch_draw(int K, Path path, int mode_diskio, const unsigned char* nodes,
-                       const NodeRecB* nodes_b, uint32_t n_nodes, const PodParams& pp,
-                       const double* rcp, const uint64_t* maxima, const int64_t* low,
-                       const uint64_t* bm, uint32_t bm_stride, const BlockMask* bs,
-                       uint32_t bs_stride, const uint64_t* blk, uint32_t blk_stride,
-                       const DrawArgs& a, hipStream_t s);
-size_t order_scratch_bytes(uint32_t n_pods);
-hipError_t launch_order_pods(const uint64_t* number, const uint64_t* m_u, const uint64_t* c_u,
-                             const uint32_t* need_mem, uint32_t n_pods, const uint32_t key_bits[3],
-                             const uint64_t* groups, uint32_t n_groups, void* scratch,
-                             size_t scratch_bytes, uint32_t* perm, const uint32_t* m32, hipStream_t s);
-hipError_t launch_order_count(const OrderMeta& o, const uint64_t* number, const uint32_t* m32,
-                              const uint32_t* c32, const uint32_t* need_mem, uint32_t n_pods,
-                              uint32_t* hist, uint32_t* bstart, uint32_t* slot, uint32_t* bkt,
-                              const PermTable& t, const uint32_t* pad, uint32_t n_pad,
-                              uint64_t* zero, uint32_t n_zero, uint32_t* perm, hipStream_t s);
-hipError_t launch_permute(const PermTable& t, const uint32_t* perm, uint32_t n_pods, bool scatter,
-                          hipStream_t s);
-}  // namespace yoda
 
 using namespace yoda;
 
@@ -527,14 +342,13 @@ struct yoda_handle {
                               // window gather + pod upload + order launches
   DevBuf p_max_u, p_cnt, p_best_f, p_best_i, p_idx, p_ties, p_low_f, p_low_i, p_err;
   uint32_t C1 = 1, chunk1 = 32;  // K1 node chunking (partial chunks; chunk1: nodes per K1 wave)
-  uint32_t k1_sub = 1;
   bool pack16 = true;            // N32: the small card fields fit 16 bits (packed K1 partials)
   bool q32 = true;               // ... and <= kF32SmallMax (the block K2's f32 quotients)
   uint64_t small_max = 0;        // the largest bandwidth / clock / core / power (any path)
   // heaviest-first pod blocks for the argmax block K2 (k_lpt_order): this run uses them,
   // the per-wave weights K1 adds to (zero between runs), the order (valid once sorted)
   bool lpt_active = false, lpt_sorted = false;
-  DevBuf lpt_w, lpt_order;           // K1 waves per chunk (4: k1_block_n32's SUB, chunk1 = a quarter)
+  DevBuf lpt_w, lpt_order;
   // the block K1's own heaviest-first order (k1_probe's weights, ranked before the K1): valid
   // for this run once k1_sorted
   bool k1_sorted = false;
@@ -839,21 +653,6 @@ void plan_chunks(yoda_t* h, int mode, uint32_t n_pods, uint32_t n_nodes) {
       h->C1 = (h->C1 + 7) / 8 * 8;
     }
   }
-  // YODA_K1_SUB=4 (A/B knob, off): the block K1 with SUB = 4 -- the same (pod wave, node range)
-  // tasks, the four waves of a workgroup on quarters of one chunk merging their partials in
-  // LDS: a quarter of the partial bytes, but K1 0.284-0.289 against 0.230-0.235 ms (the four
-  // waves no longer share the node tiles in L1).  C1 becomes the chunk count, chunk1 the quarter.
-  static const bool k1_split = YODA_KNOB("YODA_K1_SUB", 1) == 4;
-  h->k1_sub = 1;
-  if (k1_split && h->path == Path::N32 && h->has_k1sum && mode != YODA_MODE_DISKIO &&
-      h->C1 >= 4) {
-    uint32_t C = (h->C1 + 3) / 4;
-    if (C >= 8) C = (C + 7) / 8 * 8;
-    const uint32_t q = (n_nodes + 4 * C - 1) / (4 * C);
-    h->chunk1 = std::max<uint32_t>(kChunkAlign, (q + kChunkAlign - 1) / kChunkAlign * kChunkAlign);
-    h->C1 = C >= 8 ? C : std::max<uint32_t>(1, (n_nodes + 4 * h->chunk1 - 1) / (4 * h->chunk1));
-    h->k1_sub = 4;
-  }
   plan_chunks_for((uint32_t)capacity(h, 2, mode), r2, n_pods, n_nodes, &h->C2, &h->chunk2);
 }
 
@@ -864,7 +663,7 @@ size_t blk_words(const yoda_t* h, uint32_t P) {
 }
 
 int ensure_state(yoda_t* h, uint32_t P) {
-  const size_t CP = (size_t)std::max(h->C1 * h->k1_sub, h->C2) * P;
+  const size_t CP = (size_t)std::max(h->C1, h->C2) * P;
   HIP_TRY(h, h->maxima.ensure(6 * (size_t)P * 8));
   HIP_TRY(h, h->counts.ensure(2 * (size_t)P * 4));
   HIP_TRY(h, h->rcp.ensure(5 * (size_t)P * 8));
@@ -931,8 +730,7 @@ PodParams pod_params(yoda_t* h) {
   if (ub_ok && h->kb_levels_ok && lv_env) pp.kb_levels = h->kb_levels.as<uint32_t>();
   // the K2 pruning seeds live after the block list (cleared with it); the block K1 of this run
   // writes them, the argmax K2 of the same run reads them
-  // (A/B knobs: YODA_KB_DEC=0 / YODA_GBEST=0 turn the non-G bounds / the shared best off)
-  static const bool dec_env = YODA_KNOB("YODA_KB_DEC", 1) != 0;
+  // (A/B knob: YODA_GBEST=0 turns the shared best off)
   static const bool gbest_env = YODA_KNOB("YODA_GBEST", 1) != 0;
   // (the non-G bounds pay on one-model snapshots at K <= 8: config 3's K2 0.32 -> 0.21 ms;
   // on mixed-model nodes and at K = 16 their per-block cost exceeds what they prune -- mixed50
@@ -940,9 +738,9 @@ PodParams pod_params(yoda_t* h) {
   // (YODA_KB_DEC_GROUPED, A/B knob: 1 = also on mixed fleets in the block-grouped order, whose
   // one-model blocks are whole again; 2 = there at K = 16 too)
   static const uint32_t dec_grouped = YODA_KNOB("YODA_KB_DEC_GROUPED", 1);
-  const bool dec_ok = dec_env && (h->all_one_model ? h->K <= 8
-                                                    : h->perm_run() && dec_grouped != 0 &&
-                                                          (h->K <= 8 || dec_grouped == 2));
+  const bool dec_ok = h->all_one_model ? h->K <= 8
+                                        : h->perm_run() && dec_grouped != 0 &&
+                                              (h->K <= 8 || dec_grouped == 2);
   if (ub_ok && dec_ok && h->kbdec.p) pp.kbdec = h->kbdec.as<uint32_t>();
   {
     const size_t nw = (h->n_work + 63) / 64;
@@ -950,11 +748,10 @@ PodParams pod_params(yoda_t* h) {
     if (seeds_env && ub_ok && h->seeds_valid && h->blk_valid && h->bm_sparse && pp.g.tab)
       pp.seed = sd;
     if (gbest_env && ub_ok && h->blk_fresh) pp.gbest = sd + nw;  // [n_work] after the seeds
-    // the chunk masks after the shared best (A/B knob YODA_CMASK=0: every chunk writes)
-    static const bool cmask_env = YODA_KNOB("YODA_CMASK", 1) != 0;
+    // the chunk masks after the shared best
     uint64_t* cm = sd + nw + h->n_work;
-    if (cmask_env && h->blk_fresh && h->path == Path::N32) {
-      if (h->has_k1sum && h->C1 <= kPlainReduceChunks && h->k1_sub == 1) pp.cmask1 = cm;
+    if (h->blk_fresh && h->path == Path::N32) {
+      if (h->has_k1sum && h->C1 <= kPlainReduceChunks) pp.cmask1 = cm;
       if (h->has_k2sum && h->C2 <= kPlainReduceChunks) pp.cmask2 = cm + nw;
     }
   }
@@ -1497,10 +1294,9 @@ int phase1(yoda_t* h, int mode, uint64_t* maxima, uint32_t* counts,
     HIP_TRY(h, build_block_ub(h));
   if (h->blksum_loose && !h->greedy_active) HIP_TRY(h, tighten_block_sums(h));
   // the block K1 visits its pod blocks heaviest first too (k1_probe: the per-node work its
-  // whole-block decisions leave each wave on a sample of blocks; YODA_K1_LPT=0: launch order)
-  static const bool k1_lpt_env = YODA_KNOB("YODA_K1_LPT", 1) != 0;
+  // whole-block decisions leave each wave on a sample of blocks)
   h->k1_sorted = h->k1_rec_ok = false;
-  if (k1_lpt_env && h->lpt_active && h->k1_sub == 1u && mode == YODA_MODE_SCV) {
+  if (h->lpt_active && mode == YODA_MODE_SCV) {
     const PodParams pp0 = pod_params(h);
     if (pp0.bsum != nullptr) {
       const uint32_t n_pb = (P + kBlock - 1) / kBlock;
@@ -1508,10 +1304,8 @@ int phase1(yoda_t* h, int mode, uint64_t* maxima, uint32_t* counts,
       HIP_TRY(h, h->k1_order.ensure((size_t)n_pb * 4));
       // (a private run -- yoda_run, the only caller with final maxima: the probe leaves each
       // wave's bounds for the block K1 of this run.  The row, shard and greedy entry points pass
-      // no record, and their K1 computes its set-up per chunk task; so does every run under the
-      // A/B knob YODA_K1_REC=0)
-      static const bool k1_rec_knob = YODA_KNOB("YODA_K1_REC", 1) != 0;
-      const bool k1_rec_env = k1_rec_knob && final_maxima;
+      // no record, and their K1 computes its set-up per chunk task)
+      const bool k1_rec_env = final_maxima;
       if (k1_rec_env) HIP_TRY(h, h->k1_rec.ensure((size_t)((P + 63) / 64) * sizeof(K1WaveRec)));
       HIP_TRY(h, launch_k1_order(h->K, pp0, P, h->n_nodes, h->k1_w.as<uint32_t>(),
                                  h->k1_order.as<uint32_t>(),
@@ -1528,8 +1322,7 @@ int phase1(yoda_t* h, int mode, uint64_t* maxima, uint32_t* counts,
                        (pr ? h->kmix_p : h->kmix).as<unsigned char>(), h->n_nodes,
                        h->chunk1, h->C1, pod_params(h), P, part, h->bitmask.as<uint64_t>(),
                        bm_row(h->n_nodes), h->bsum.as<BlockMask>(), bs_row(h->n_nodes),
-                       h->blk.as<uint64_t>(), blk_row(h->n_nodes), h->stats_ptr(), h->stream,
-                       h->k1_sub));
+                       h->blk.as<uint64_t>(), blk_row(h->n_nodes), h->stats_ptr(), h->stream));
   if (h->class_stats && h->has_k1sum) h->stats_pairs1 += (uint64_t)(P + 63) / 64 * h->n_nodes;
   if (e1) {
     HIP_TRY(h, hipEventRecord(e1, h->stream));
@@ -1570,12 +1363,10 @@ int phase1_witness(yoda_t* h, uint64_t* maxima, uint32_t* counts, uint32_t* wit,
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return YODA_OK;
   }
-  // (the witness K1s run one wave per node range: chunk1 nodes each, C1 * k1_sub of them)
-  uint32_t C = h->C1 * h->k1_sub;
+  uint32_t C = h->C1;
   HIP_TRY(h, h->p_wit.ensure(12 * (size_t)C * P * 4));
   Partials part = partials(h);
-  static const bool block_wit = YODA_KNOB("YODA_BLOCK_WITNESS", 1) != 0;
-  if (block_wit && h->path == Path::N32 && h->has_k1sum && h->has_k2sum && h->all_one_model) {
+  if (h->path == Path::N32 && h->has_k1sum && h->has_k2sum && h->all_one_model) {
     // block-classified, like phase 1's K1: sparse masks and the block list for the window's K2.
     // Its per-(wave, chunk) epilogue (18 wave reductions, 104 B of partials a pod) is the
     // cost that grows with the chunk count: chunks of >= YODA_WIT_CHUNK_NODES nodes
@@ -1818,18 +1609,11 @@ int topk_lists(yoda_t* h, uint32_t P, uint32_t KT, const uint32_t* d_counts, uin
       if (Ct >= 8) Ct = (Ct + 7) / 8 * 8;
     }
     HIP_TRY(h, h->tk_s_part.ensure((size_t)Ct * P * KT * 8));
-    // the chunks' shared k-th keys start empty at every list pass (a mid-window refresh scores
-    // a later node state, whose keys are lower: the last pass's would be too high)
     PodParams pp = pod_params(h);
-    // (A/B knobs: YODA_TOPK_GBEST=0 / YODA_TOPK_DEC=0 -- the shared k-th keys / the non-G
-    // bounds in the list passes)
-    // (both off by default: the capacity windows ran 1.51 s without them, 1.58 s with them,
-    // profiles/r05/g)
-    static const bool tk_gbest = YODA_KNOB("YODA_TOPK_GBEST", 0) != 0;
-    static const bool tk_dec = YODA_KNOB("YODA_TOPK_DEC", 0) != 0;
-    if (!tk_gbest) pp.gbest = nullptr;
-    if (!tk_dec) pp.kbdec = nullptr;
-    if (pp.gbest) HIP_TRY(h, hipMemsetAsync(pp.gbest, 0, (size_t)P * 8, h->stream));
+    // the list passes take neither the shared k-th keys nor the non-G bounds (the capacity
+    // windows ran 1.51 s without them, 1.58 s with them, profiles/r05/g)
+    pp.gbest = nullptr;
+    pp.kbdec = nullptr;
     HIP_TRY(h, launch_k2_topk_block(h->K, h->nodes.as<unsigned char>(),
                                     h->k2sum.as<unsigned char>(),
                                     h->blk_valid ? h->blk.as<uint64_t>() : nullptr, blk_row(N), N,
@@ -2159,16 +1943,12 @@ PackedRows pack_rows(const yoda_node_soa* nd, const UploadFormat& f, const MemCo
 // `sum`: the node-major K1 summaries of an N32 snapshot.  Returns the node of each position,
 // empty when the snapshot keeps its own order.
 std::vector<uint32_t> grouped_node_order(const std::vector<uint32_t>& sum, uint32_t N, int K,
-                                         bool ranks, bool all_one_model, uint32_t flags) {
-  static const bool perm_env = YODA_KNOB("YODA_NODE_PERM", 1) != 0;
+                                         bool ranks, uint32_t flags) {
   std::vector<uint32_t> nperm;
   // Mixed-model nodes (cards of several GPU models) form a group of their own, so that
   // the one-model nodes still fill one-model blocks, which the block summaries decide
-  // whole (50 % mixed-model nodes: every block mixed without it).  YODA_NODE_PERM_MIXED=0
-  // (A/B knob): one-model snapshots only, as in round 5.
-  static const bool perm_mixed = YODA_KNOB("YODA_NODE_PERM_MIXED", 1) != 0;
-  if (!(perm_env && (all_one_model || perm_mixed) && N >= 4096 &&
-        !(flags & YODA_UPLOAD_PER_NODE_K1) && !(flags & YODA_UPLOAD_PER_NODE_K2)))
+  // whole (50 % mixed-model nodes: every block mixed without it).
+  if (N < 4096 || (flags & YODA_UPLOAD_PER_NODE_K1) || (flags & YODA_UPLOAD_PER_NODE_K2))
     return nperm;
   const uint32_t SW = k1sum_stride(K) / 4u;
   std::vector<uint32_t> keys;
@@ -2197,10 +1977,7 @@ std::vector<uint32_t> grouped_node_order(const std::vector<uint32_t>& sum, uint3
   // samples every free level (the chunks stay even).
   // Not with memory ranks: there the rank-space K2 ran slower on the sorted blocks
   // (memory in bytes: 1.91 vs 1.80 ms, profiles/r05/y/ab.txt).
-  static const bool zorder_env = YODA_KNOB("YODA_NODE_ZORDER", 1) != 0;  // A/B knob
-  // (YODA_ZORDER_RANKS=1, A/B knob: with memory ranks too)
-  static const bool zorder_ranks = YODA_KNOB("YODA_ZORDER_RANKS", 0) != 0;
-  if (ok && zorder_env && (!ranks || zorder_ranks)) {
+  if (ok && !ranks) {
     std::vector<uint32_t> hix;
     for (uint32_t t = 1; t <= (uint32_t)K; t <<= 1) hix.push_back(t - 1);
     const uint32_t nc = (uint32_t)hix.size(), bits = 64 / nc > 16 ? 16 : 64 / nc;
@@ -2516,7 +2293,7 @@ int yoda_upload_nodes(yoda_t* h, const yoda_node_soa* nd, uint32_t node_offset, 
     std::vector<uint32_t> nperm;
     std::vector<std::vector<uint32_t>> staged;  // (host sides of the copies in flight)
     if (want_sum) {
-      nperm = grouped_node_order(rows.sum, N, K, fmt.ranks, rows.n_one_model == N, flags);
+      nperm = grouped_node_order(rows.sum, N, K, fmt.ranks, flags);
       h->perm_on = !nperm.empty();
       int rc = upload_sum_tables(h, rows, nperm, staged);
       if (!rc) rc = upload_block_sums(h);
@@ -2537,11 +2314,10 @@ int yoda_upload_nodes(yoda_t* h, const yoda_node_soa* nd, uint32_t node_offset, 
     }
     h->has_k1sum = want_sum && !(flags & YODA_UPLOAD_PER_NODE_K1);
     h->has_k2sum = want_sum && !(flags & YODA_UPLOAD_PER_NODE_K2);
-    static const bool no_gtab = YODA_KNOB("YODA_NO_GTAB", 0) != 0;  // A/B knob
     // The upload's one wait, for every copy and table kernel above; with a G table in use its
     // reciprocals come back in the same wait.
     h->g = GTab{};
-    if (h->has_k2sum && N > 0 && !no_gtab && !(flags & YODA_UPLOAD_NO_GTAB)) {
+    if (h->has_k2sum && N > 0 && !(flags & YODA_UPLOAD_NO_GTAB)) {
       h->g.tab = h->gtab.as<uint32_t>();
       if (int rc = read_g_reciprocals(h)) return rc;
     } else {
@@ -2913,17 +2689,15 @@ static int prepare_run(yoda_t* h, int mode, bool pad = false) {
   // a private run takes the counting sort, padded when that adds at most 1/8 of the batch
   // (many small groups would otherwise multiply the work)
   h->count_order = pad && ordering && h->og_ok;
-  const bool padded = h->count_order && h->order_pad && YODA_KNOB("YODA_ORDER_PAD", 1) &&
+  const bool padded = h->count_order && h->order_pad &&
                       (uint64_t)h->n_pad * 8 <= (uint64_t)h->n_pods * 9;
   h->n_work = padded ? h->n_pad : h->n_pods;
   plan_chunks(h, mode, h->n_work, h->n_nodes);
   // a run on the block kernels (argmax, or the greedy windows' top-k) visits its pod blocks
-  // heaviest first (a block's weight: its heaviest wave's PART nodes in K1; YODA_LPT=0: launch
-  // order)
-  static const bool lpt_env = YODA_KNOB("YODA_LPT", 1) != 0;
+  // heaviest first (a block's weight: its heaviest wave's PART nodes in K1)
   const uint32_t n_pb = (h->n_work + kBlock - 1) / kBlock;
   h->lpt_sorted = false;
-  h->lpt_active = lpt_env && mode == YODA_MODE_SCV && h->path == Path::N32 &&
+  h->lpt_active = mode == YODA_MODE_SCV && h->path == Path::N32 &&
                   h->has_k1sum && h->has_k2sum && n_pb >= 8 && n_pb <= 4096;
   if (h->lpt_active) {
     const size_t had = h->lpt_w.bytes;
@@ -3021,8 +2795,6 @@ static int run_private(yoda_t* h, int mode, uint32_t flags, bool draw) {
   if (rc) return rc;
   const bool defer = fast && h->count_order;
   if (!defer && (rc = pods_complete(h))) return rc;
-  // (YODA_SIDE_COPY=0, A/B knob: the deferred copy on the run's stream after its kernels)
-  static const bool side = YODA_KNOB("YODA_SIDE_COPY", 1) != 0;
   h->core_only = defer;
   try {
     struct Clear {
@@ -3044,7 +2816,7 @@ static int run_private(yoda_t* h, int mode, uint32_t flags, bool draw) {
     // the deferred arrays: packed on the host while the kernels run, copied on the side stream
     // (from the upload's core copy on, so alongside the kernels), joined into the stream
     h->core_only = false;
-    if (defer && side && h->copy_stream && (rc = pods_complete_async(h))) return rc;
+    if (defer && h->copy_stream && (rc = pods_complete_async(h))) return rc;
     if (defer && (rc = pods_complete(h))) return rc;
     if (draw && h->tie_draw && (rc = draw_pass(h, mode))) return rc;
     h->ran = true;
@@ -3886,8 +3658,6 @@ int yoda_greedy(yoda_t* h, const yoda_pod_soa* pods, int mode, uint32_t flags, i
         // is stored as  score + old static - current static  of its node, so the certificate
         // above yields its current score from then on; the threshold is the refresh-time
         // score (unlisted nodes scored at most that then and only dropped since).
-        // YODA_GREEDY_REFRESH=0: off (A/B knob).
-        static const bool refresh_on = YODA_KNOB("YODA_GREEDY_REFRESH", 1) != 0;
         // (YODA_GREEDY_REFRESH_EVERY / _MIN: A/B knobs for the check period and the bar)
         static const uint32_t kFbCheck =
             std::max<uint32_t>(1, YODA_KNOB("YODA_GREEDY_REFRESH_EVERY", 8));
@@ -3895,7 +3665,7 @@ int yoda_greedy(yoda_t* h, const yoda_pod_soa* pods, int mode, uint32_t flags, i
         constexpr uint32_t kScan = 256;
         uint32_t fb_since = 0;
         auto maybe_refresh = [&](uint32_t i) -> int {
-          if (!refresh_on || wrapped || N == 0 || ++fb_since < kFbCheck || wn - i < 2 * kScan)
+          if (wrapped || N == 0 || ++fb_since < kFbCheck || wn - i < 2 * kScan)
             return YODA_OK;
           fb_since = 0;
           uint32_t unc = 0, bj;
@@ -5195,18 +4965,11 @@ uint32_t yoda_greedy_next_window(uint32_t progress, uint32_t wmax) {
   // the next window holds 130 % of this one's progress, in whole waves: small windows cost
   // less (K1 / K2 time grows with the pods) and most restart near where the last one did;
   // profiles/r03/greedy_capacity/grow_ab.txt (1.81-1.91 s with the earlier power of two >=
-  // twice the progress, 1.57-1.64 s at 130 %).  YODA_GREEDY_GROW_PCT: A/B knob (0: that
-  // power of two)
+  // twice the progress, 1.57-1.64 s at 130 %).  YODA_GREEDY_GROW_PCT: A/B knob
   static const uint32_t grow = YODA_KNOB("YODA_GREEDY_GROW_PCT", 130);
   wmax = std::max<uint32_t>(wmax, 1);
-  uint32_t w2 = 64;
-  if (grow) {
-    const uint64_t t = (uint64_t)progress * grow / 100;
-    w2 = (uint32_t)std::min<uint64_t>(wmax, std::max<uint64_t>(64, (t + 63) / 64 * 64));
-  } else {
-    while (w2 < 2 * progress && w2 < wmax) w2 <<= 1;
-  }
-  return std::min(w2, wmax);
+  const uint64_t t = (uint64_t)progress * grow / 100;
+  return (uint32_t)std::min<uint64_t>(wmax, std::max<uint64_t>(64, (t + 63) / 64 * 64));
 }
 
 int yoda_gs_uncertified(const yoda_gs_t* g, uint32_t from, uint32_t scan, uint32_t* count) {
@@ -5381,11 +5144,8 @@ static int greedy_capacity(yoda_t* h, const yoda_pod_soa* pods, int32_t* pick) {
   };
   // the chunks' list depth: 8 where the lists are merged deeper (k_topk_merge_deep: the same
   // 64-deep lists as from 16, and a cheaper K2 -- 1.00-1.02 vs 1.07-1.09 s,
-  // profiles/r05/pqr/tk_ab.txt), else 16; YODA_GREEDY_CAP_TOPK=16 (A/B knob): 16 always
-  static const uint32_t kt_knob = YODA_KNOB("YODA_GREEDY_CAP_TOPK", 0);
-  const uint32_t kt_cap = kt_knob == (uint32_t)topk_k_capacity() || !topk_block_ok(h)
-                              ? (uint32_t)topk_k_capacity()
-                              : (uint32_t)topk_k();
+  // profiles/r05/pqr/tk_ab.txt), else 16
+  const uint32_t kt_cap = !topk_block_ok(h) ? (uint32_t)topk_k_capacity() : (uint32_t)topk_k();
   const uint32_t P = pods->n_pods, N = h->n_nodes, KT = kt_cap;
   yoda_node_soa nv{};
   nv.n_nodes = N;
@@ -5611,8 +5371,7 @@ static int greedy_capacity(yoda_t* h, const yoda_pod_soa* pods, int32_t* pick) {
       // the next window holds 130 % of this one's progress, in whole waves: small windows cost
       // less (K1 / K2 time grows with the pods) and most restart near where the last one did;
       // profiles/r03/greedy_capacity/grow_ab.txt (1.81-1.91 s with the earlier power of two >=
-      // twice the progress, 1.57-1.64 s at 130 %).  YODA_GREEDY_GROW_PCT: A/B knob (0: that
-      // power of two)
+      // twice the progress, 1.57-1.64 s at 130 %).  YODA_GREEDY_GROW_PCT: A/B knob
       W = yoda_greedy_next_window(next, Wmax);
       ws += next;
     } else {

@@ -22,6 +22,7 @@
 #include <cstdlib>
 
 #include "yoda_layout.h"
+#include "yoda_launch.h"
 
 // The YODA_ABL_* ablations remove work whose results the path needs (written masks, summaries,
 // whole classes): counter and timing builds only.  They compile only beside the A/B knobs
@@ -179,44 +180,6 @@ __device__ __forceinline__ bool k1_node(const unsigned char* rec, typename Rec<P
         mx[kMaxFree] = fmax_t(mx[kMaxFree], fr.v[j]);
         mx[kMaxPower] = fmax_t(mx[kMaxPower], pw.v[j]);
         mx[kMaxTotal] = fmax_t(mx[kMaxTotal], to.v[j]);
-      }
-    }
-  }
-  return feas;
-}
-
-// k1_node for the block-classified N32 K1's undecided MIXED-model nodes (one-model nodes are
-// decided from the node summary there): the same predicates and maxima, but the maxima
-// fields are read one card at a time, so the rare path holds ~2K + 6 SGPRs instead of 6K
-// and does not push the whole kernel into SGPR spills.
-template <int K>
-__device__ __forceinline__ bool k1_node_lean(const unsigned char* rec, uint32_t m, uint32_t c,
-                                             uint64_t number, uint32_t need_mem,
-                                             uint32_t need_clk, uint32_t (&mx)[6], uint32_t& nf,
-                                             uint32_t& nz) {
-  const NodeHdrG hd = *reinterpret_cast<const NodeHdrG*>(rec);
-  const uint32_t* g = reinterpret_cast<const uint32_t*>(rec + n32_u32_off(0, K));
-  uint32_t cm = 0, cc = 0;
-#pragma unroll 1
-  for (int j = 0; j < K; ++j) {
-    const uint32_t hj = (hd.healthy_mask >> j) & 1u, fj = g[kFree * K + j], cj = g[kClock * K + j];
-    cm += (uint32_t)(fj >= m) & hj;   // CardFitsMemory (filter.go:52-54)
-    cc += (uint32_t)(cj == c) & hj;   // CardFitsClock (filter.go:56-58)
-  }
-  const bool feas = (number <= hd.card_number) & (cm >= need_mem) & (cc >= need_clk);
-  if (feas) {
-    ++nf;
-    nz += hd.zero_total;
-#pragma unroll 1
-    for (int j = 0; j < K; ++j) {
-      const uint32_t fj = g[kFree * K + j], cj = g[kClock * K + j];
-      if ((fj >= m) & (cj >= c)) {  // collection.go:46: no health check, >= clock
-        mx[kMaxBw] = max(mx[kMaxBw], g[kBandwidth * K + j]);
-        mx[kMaxClock] = max(mx[kMaxClock], cj);
-        mx[kMaxCore] = max(mx[kMaxCore], g[kCore * K + j]);
-        mx[kMaxFree] = max(mx[kMaxFree], fj);
-        mx[kMaxPower] = max(mx[kMaxPower], g[kPower * K + j]);
-        mx[kMaxTotal] = max(mx[kMaxTotal], g[kTotal * K + j]);
       }
     }
   }
@@ -654,10 +617,6 @@ __device__ __forceinline__ uint32_t narrow_floor(int w, uint32_t nw) {  // floor
   return (nw == kNarrowWords && w < 2) ? 0x00010001u : 1u;
 }
 
-// SUB = 4 (the argmax runs): the workgroup's four waves hold the SAME 64 pods, each over its own
-// quarter of the chunk (chunk_nodes = the quarter), and merge their partials in LDS at the end:
-// a quarter of the partial bytes (and of k_reduce1's reads) for the same (wave, node-range)
-// tasks -- 24 B per (pod, chunk) written once per chunk instead of once per quarter.
 // The wave bounds K1's whole-block decisions compare against (k1_block_class), from the wave's
 // pods: scv/number, scv/memory (m, the need in cards), scv/clock (c, the need in cards).
 struct K1Wave {
@@ -729,15 +688,12 @@ __device__ __forceinline__ K1BlockClass k1_block_class(const uint32_t* B, bool b
   const bool noq = (ckmax < w.c_min) | (mrf_max <= w.m_min);
   // (other blocks: no clock-only noq -- the seed's level bound assumes every card passes)
   ball &= (r.allq | (one ? noq : mrf_max <= w.m_min)) & !bnone & (one | mix_all);
-#ifdef YODA_AB_NO_MIXALL  // (A/B build: whole-block ALL for one-model blocks only, as round 5)
-  ball &= one;
-#endif
   r.none = bnone & bv & (r.nreal > 0u);
   r.all = ball & bv & (r.nreal > 0u);
   return r;
 }
 
-template <int K, bool STATS, bool MIX = true, bool WIT = false, int SUB = 1>
+template <int K, bool STATS, bool MIX = true, bool WIT = false>
 #ifndef YODA_K1_WAVES
 #define YODA_K1_WAVES 6  // (7: 9 VGPRs spilled, ~90 MB of scratch writes per launch; r05j)
 #endif
@@ -767,9 +723,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WIT ? 4 
     const uint32_t* __restrict__ pb_order = nullptr,
     const K1WaveRec* __restrict__ wrec = nullptr) {
   static_assert(!(WIT && MIX), "the witness K1 serves one-model snapshots");
-  static_assert(SUB == 1 || (SUB == kBlock / kWave && !WIT), "SUB: 1, or one pod wave per workgroup");
   constexpr uint32_t SS = k1sum_stride(K);
-  constexpr uint32_t NS = n32_stride(K);
   constexpr uint32_t S2 = k2sum_stride(K), MS = mix_stride(K), XS = x1_stride(K);
   constexpr uint32_t HW = K + 1;  // LDS words per node: hfs[0..K-1], 0
   // + a 10-word record per one-model PART node (below): the per-pod pass reads it from LDS
@@ -778,17 +732,16 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WIT ? 4 
   uint32_t* lds = lds_all[threadIdx.x >> 6];
   const uint32_t lane = lane_id();
   const Tile tl = tile();
-  const uint32_t sub = SUB > 1 ? threadIdx.x >> 6 : 0u;
   // pb_order: the pod blocks heaviest first (k1_probe + k_lpt_order), so the long tasks do not
-  // start last (SUB = 1)
-  const uint32_t pbk = (SUB == 1 && pb_order != nullptr) ? pb_order[tl.pb] : tl.pb;
-  const uint32_t p = SUB > 1 ? tl.pb * kWave + lane : pbk * kBlock + threadIdx.x;
+  // start last
+  const uint32_t pbk = pb_order != nullptr ? pb_order[tl.pb] : tl.pb;
+  const uint32_t p = pbk * kBlock + threadIdx.x;
   const uint32_t chunk = tl.chunk, C = gridDim.y;
-  const uint32_t n0 = (chunk * SUB + sub) * chunk_nodes;
+  const uint32_t n0 = chunk * chunk_nodes;
   const uint32_t n1 = min(n0 + chunk_nodes, n_nodes);
   const bool live = p < n_pods;
   const uint64_t live_mask = ballot(live);
-  // a wave past the batch: no bitmask row, no partials (SUB: the whole workgroup, together)
+  // a wave past the batch: no bitmask row, no partials
   if (live_mask == 0) return;
   uint64_t* bmw = bm + (size_t)uniform_u32(p >> 6) * bm_stride;
   BlockMask* bsw = bs + (size_t)uniform_u32(p >> 6) * bs_stride;
@@ -811,7 +764,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WIT ? 4 
   uint32_t lev = 0u;
   if (levels != nullptr) lev = levels[lane & (kKbLevels - 1u)];
   // ---- wave bounds (pm: pods with the scv/memory label, pc: with scv/clock) ----
-  // wrec (yoda_run's K1, SUB = 1; nullptr from every other entry point): k1_probe computed
+  // wrec (yoda_run's K1; nullptr from every other entry point): k1_probe computed
   // them once for the wave; each of its chunk tasks reads the record in the load round of the
   // pod arrays instead of reducing them again, and the per-lane values above are first waited
   // for in the per-pod pass.
@@ -822,7 +775,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WIT ? 4 
   // v_readlane reloads cost issue slots in every block; profiles/r02/final/k1_occupancy_ab.txt)
   uint32_t mpm_max, mpm_min, m_max, m_min, c_max, c_min;
   uint32_t l_hi_rec = kKbLevels - 1u;
-  if (SUB == 1 && wrec != nullptr) {
+  if (wrec != nullptr) {
     const K1WaveRec* rv = wrec + (p >> 6);                // (per-lane address: VGPR values)
     const K1WaveRec* rs = wrec + uniform_u32(p >> 6);     // (uniform address: scalar values)
     mpm_min = rv->mpm_min;
@@ -904,12 +857,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WIT ? 4 
       atomicOr(reinterpret_cast<unsigned long long*>(blkw + blk_wi), (unsigned long long)blk_bits);
   };
 
-#ifndef YODA_K1_PF
-#define YODA_K1_PF 0
-#endif
-  // the summary words a block's classification reads (YODA_K1_PF = 1: the next block
-  // node_block visits is loaded while this one is classified; off: the extra live registers
-  // spill, K1 0.211-0.219 ms without against 0.230-0.235 with, same box)
+  // the summary words a block's classification reads
   uint4 pf0 = make_uint4(0u, 0u, 0u, 0u), pf1 = pf0;
   uint32_t pf_pw = 0, pf_ta = 0, pf_tn = 0;
   auto load_sum = [&](uint32_t nb) {
@@ -932,8 +880,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WIT ? 4 
   // scores for all of them under the G maxima -- static + B_G[q], q = the cards that qualify
   // for the wave's largest scv/memory (so for every pod: B_G is non-decreasing in q), one-model
   // nodes only (a feasible one has the pods' scv/clock, so every card passes the clock test).
-  // Taken over the ALL blocks (lane = block, kbub's lv[] at the wave's largest scv/memory);
-  // YODA_K1_NODE_SEEDS (A/B) adds the ALL nodes of the blocks classified node by node.
+  // Taken over the ALL blocks (lane = block, kbub's lv[] at the wave's largest scv/memory).
 #ifdef YODA_K1_NOSEED  // (A/B build: the seed code compiled out)
   const bool seeding = false;
 #else
@@ -953,18 +900,15 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WIT ? 4 
                   hfs_all_ok, hfs_none_ok};
   // per-node classification of one 64-node block (below: only the blocks the block summaries
   // leave undecided)
-  // (nxt: the block node_block visits next, whose summary words are loaded here -- the
-  // caller loaded nb's before the first call; ~0u: none)
-  auto node_block = [&](uint32_t nb, uint32_t nxt) {
+  auto node_block = [&](uint32_t nb) {
     if (STATS) ++nblk;
     const uint32_t n = nb + lane;
     const bool valid = n < n1;
     // this block's tile of summaries (nb is a multiple of 64): word w at s[64 w]
     const uint32_t* s = reinterpret_cast<const uint32_t*>(sum) + sum_index(nb, 0, SS) + lane;
-    if (!YODA_K1_PF) load_sum(nb);
+    load_sum(nb);
     const uint4 w0 = pf0, w1 = pf1;
     const uint32_t pw0 = pf_pw, t_all = pf_ta, t_none = pf_tn;
-    if (YODA_K1_PF && nxt != ~0u) load_sum(nxt);
     if (!need_uni) {  // the node's healthy frees for the per-pod pass: lds[node][need - 1] (slot K: 0)
       // (all K loads in flight before the first LDS write: one round trip, not K / 2)
       uint32_t hv[K];
@@ -1104,21 +1048,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WIT ? 4 
     }
     const bool is_none = valid && feas_none;
     const bool is_all = valid && !feas_none && feas_all && same;
-#ifdef YODA_K1_NODE_SEEDS  // (A/B: per-node seeds too -- +35 % K1 time for little K2 gain)
-    if (seeding) {
-      const bool sdl = valid && feas_all && !feas_none && uni4;
-      if (ballot(sdl) != 0ull && sdl) {
-        uint32_t q = 0;  // healthy cards with free >= the largest m (<= the qualifying cards)
-#pragma unroll
-        for (int t = 0; t < K; ++t) q += s[64 * (kSumHfs + t)] > m_max ? 1u : 0u;
-        const uint32_t* s2 = sum2w + sum_index(nb, 0, k2sum_stride(K)) + lane;
-        const double st = __longlong_as_double(
-            (long long)((uint64_t)s2[64 * kS2Static] | ((uint64_t)s2[64 * (kS2Static + 1)] << 32)));
-        const uint32_t bq = q > 0u ? gtab[sum_index(nb + lane, q - 1u, gtab_stride(K))] : 0u;
-        atomicMax(sdw, (unsigned long long)((uint64_t)st + (uint64_t)bq));
-      }
-    }
-#endif
     const uint64_t all_b = ballot(is_all), none_b = ballot(is_none);
     uint64_t part_b = ballot(valid) & ~all_b & ~none_b;
     if (STATS && !trace) {  // class counts of (wave, node) pairs: ALL, NONE; whole blocks
@@ -1229,11 +1158,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WIT ? 4 
       }
     }
     part_b &= ~rec_b;
-#ifndef YODA_K1_LEAN_GLOBAL
     // Other PART nodes (several GPU models, or several TotalMemory values): their cards staged
     // in LDS, lane = node, from the block's tiles (K2 summary frees / totals in free order,
     // K1MixWord cards, the health bits) -- one memory round trip per batch of nodes -- then
-    // read by the per-pod pass with broadcast ds_read_b128s.  (Before: k1_node_lean's per-card
+    // read by the per-pod pass with broadcast ds_read_b128s.  (Before: a per-card
     // loop over the node record, ~2K dependent scalar loads per node: mixed50 K1 0.88 ms.)
     // The area is the rows / records above, free again here.  Per node: {CardNumber lo, hi,
     // health bits | zero-total << 31, 0}, then per card {free, clock | bw << 16, total,
@@ -1303,18 +1231,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WIT ? 4 
         }
       }
     }
-#else
-    while (MIX && part_b) {  // mixed-model nodes: the exact per-card predicates from the record
-      const int j = __builtin_ctzll(part_b);
-      part_b &= part_b - 1;
-      // (the record by the node's local id: a block-grouped run reads positions, ids)
-      const uint32_t rid = ids ? ids[nb + (uint32_t)j] : nb + (uint32_t)j;
-      const bool f = k1_node_lean<K>(nodes + (size_t)rid * NS, m, c, number,
-                                     need_mem, need_clk, mx, nf, nz) && live;
-      const uint64_t b = ballot(f);
-      set_lane(lo, hi, b, (uint32_t)j);
-    }
-#endif
     // sparse masks: the block's (nz, full) words always, a node's own mask only when it is
     // neither empty nor the wave's live mask (the ALL / NONE nodes cost no mask traffic)
     const uint64_t mine = ((uint64_t)hi << 32) | lo;
@@ -1434,16 +1350,14 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WIT ? 4 
         }
       }
       uint64_t und = ballot(bv && nreal > 0u) & ~(none_m | all_m);
-      if (YODA_K1_PF && und) load_sum((g + (uint32_t)__builtin_ctzll(und)) << 6);
       while (und) {
         const uint32_t j = (uint32_t)__builtin_ctzll(und);
         und &= und - 1;
-        node_block((g + j) << 6, und ? (g + (uint32_t)__builtin_ctzll(und)) << 6 : ~0u);
+        node_block((g + j) << 6);
       }
     }
   } else {
-    if (YODA_K1_PF && n0 < n1) load_sum(n0);
-    for (uint32_t nb = n0; nb < n1; nb += kWave) node_block(nb, nb + kWave < n1 ? nb + kWave : ~0u);
+    for (uint32_t nb = n0; nb < n1; nb += kWave) node_block(nb);
   }
   const uint64_t t_pass = STATS ? wall_clock64() : 0ull;
   g_nf = wave_sum_u32(g_nf);
@@ -1463,7 +1377,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WIT ? 4 
     const uint32_t wgt = npart + g_nu;
     if (lane == 0 && wgt != 0u) atomicAdd(wts + (p >> 6), wgt);
   }
-  const size_t slot1 = ((size_t)(p >> 6) * C + chunk) * SUB + sub;
+  const size_t slot1 = (size_t)(p >> 6) * C + chunk;
   if (trace && lane == 0 && slot1 < (size_t)(stats[15] >> 8)) {
     unsigned long long* tr = stats + 16 + 4 * slot1;
     tr[0] = t_start;
@@ -1511,13 +1425,13 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WIT ? 4 
   a_free = wave_max_u32(a_free);
   a_pw = wave_max_u32(a_pw);
   a_tot = wave_max_u32(a_tot);
-  if (SUB == 1 && cmask != nullptr) {
+  if (cmask != nullptr) {
     // no pod of the wave has a feasible node in the chunk: its partials are the identity
     // (maxima at the floor, counts 0) -- nothing written, and k_reduce1 skips the chunk
     if (ballot(live && nf + nf_all != 0u) == 0ull) return;
     if (lane == 0) atomicOr(cmask + (p >> 6), 1ull << chunk);
   }
-  if (SUB == 1 && !live) return;  // (lane 0 is live: the live lanes are a prefix)
+  if (!live) return;  // (lane 0 is live: the live lanes are a prefix)
   mx[kMaxBw] = max(mx[kMaxBw], a_bw);
   mx[kMaxClock] = max(mx[kMaxClock], a_ck);
   mx[kMaxCore] = max(mx[kMaxCore], a_core);
@@ -1540,26 +1454,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WIT ? 4 
   } else {
 #pragma unroll
     for (int f = 0; f < kWideWords; ++f) pw4[f] = mx[f];
-  }
-  if constexpr (SUB > 1) {
-    // the quarters' partials through LDS (each wave's own region, free after its loop);
-    // wave 0 folds them and writes the chunk's
-    static_assert(RECS + kWave * REC >= (kWideWords + 2) * kWave, "LDS merge area");
-#pragma unroll
-    for (int f = 0; f < kWideWords; ++f) lds[f * kWave + lane] = pw4[f];
-    lds[kWideWords * kWave + lane] = nf;
-    lds[(kWideWords + 1) * kWave + lane] = nz;
-    __syncthreads();
-    if (sub != 0u || !live) return;
-#pragma unroll
-    for (int w = 1; w < SUB; ++w) {
-      const uint32_t* o = lds_all[w];
-#pragma unroll
-      for (int f = 0; f < kWideWords; ++f)
-        pw4[f] = narrow_max(pw4[f], o[f * kWave + lane], f, nwords);
-      nf += o[kWideWords * kWave + lane];
-      nz += o[(kWideWords + 1) * kWave + lane];
-    }
   }
 #ifdef YODA_ABL_K1_NOPART  // (write-traffic ablation: no partial stores)
   return;
@@ -2186,8 +2080,6 @@ hipError_t launch_lpt_order(uint32_t* wts, uint32_t n_pods, uint32_t* order, hip
   return hipGetLastError();
 }
 
-// The block K1's heaviest-first pod-block order: k1_probe's per-wave weights into wts, ranked by
-// k_lpt_order into order (n_pb entries); rec (optional): the waves' K1WaveRec records.
 hipError_t launch_k1_order(int K, const PodParams& pp, uint32_t n_pods, uint32_t n_nodes,
                            uint32_t* wts, uint32_t* order, K1WaveRec* rec, hipStream_t s) {
   const uint32_t n_pb = (n_pods + kBlock - 1) / kBlock;
@@ -3361,14 +3253,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(K <= 8 ?
     if (args.gbest != nullptr && act) {  // (score + 1; 0: none yet)
       const unsigned long long mine = lb >= 0.0 ? (unsigned long long)lb + 1ull : 0ull;
       // (published once per value: the load may see a stale line, not this lane's own atomic)
-#ifndef YODA_GBEST_REPUB
       if (mine > g && mine > gpub) {
         atomicMax(args.gbest + p, mine);
         gpub = mine;
       }
-#else
-      if (mine > g) atomicMax(args.gbest + p, mine);
-#endif
       lb = fmax(lb, (double)g - 1.0);
     }
     lb = wave_allreduce(lb, OpMinF64{});
@@ -5046,24 +4934,28 @@ __global__ __launch_bounds__(kBlock) void k_bitmask_transpose(const MaskSrc ms,
     case 16: { constexpr int KK = 16; __VA_ARGS__; } break; \
     default: return hipErrorInvalidValue;           \
   }
+// (the launchers that refuse K = 16 before their switch)
+#define YODA_K8_SWITCH(K, ...)                      \
+  switch (K) {                                      \
+    case 1: { constexpr int KK = 1; __VA_ARGS__; } break;  \
+    case 2: { constexpr int KK = 2; __VA_ARGS__; } break;  \
+    case 4: { constexpr int KK = 4; __VA_ARGS__; } break;  \
+    case 8: { constexpr int KK = 8; __VA_ARGS__; } break;  \
+    default: return hipErrorInvalidValue;           \
+  }
 
 
-
-// sub (block K1 only): 1, or 4 = one pod wave per workgroup over four quarters of each
-// chunk, chunk_nodes then being the quarter (k1_block_n32's SUB).
 hipError_t launch_k1(int K, Path path, const unsigned char* nodes, const unsigned char* sum,
                      const unsigned char* sum2, const unsigned char* mix, uint32_t n_nodes, uint32_t chunk_nodes, uint32_t C, const PodParams& pp,
                      uint32_t n_pods, const Partials& part, uint64_t* bm, uint32_t bm_stride,
                      BlockMask* bs, uint32_t bs_stride, uint64_t* blk, uint32_t blk_stride,
-                     unsigned long long* stats, hipStream_t s, uint32_t sub) {
+                     unsigned long long* stats, hipStream_t s) {
   dim3 grid((n_pods + kBlock - 1) / kBlock, C);
   switch (path) {
     case Path::N32:
       if (sum) {
-        if (sub != 1u && sub != (uint32_t)(kBlock / kWave)) return hipErrorInvalidValue;
-        const dim3 g1 = sub == 1u ? grid : dim3((n_pods + kWave - 1) / kWave, C);
 #define YODA_K1B(...)                                                                          \
-  YODA_K_SWITCH(K, hipLaunchKernelGGL((k1_block_n32<__VA_ARGS__>), g1, dim3(kBlock), 0, s, nodes, \
+  YODA_K_SWITCH(K, hipLaunchKernelGGL((k1_block_n32<__VA_ARGS__>), grid, dim3(kBlock), 0, s, nodes, \
                                       sum, reinterpret_cast<const uint32_t*>(sum2),            \
                                       reinterpret_cast<const uint32_t*>(mix), pp.x1, n_nodes,  \
                                       chunk_nodes, pp.m_32, pp.c_32, pp.number, pp.need_mem,   \
@@ -5073,16 +4965,10 @@ hipError_t launch_k1(int K, Path path, const unsigned char* nodes, const unsigne
                                       pp.kbub_exact ? pp.kbub : nullptr, pp.kb_levels,           \
                                       reinterpret_cast<unsigned long long*>(pp.seed),          \
                                       reinterpret_cast<unsigned long long*>(pp.cmask1), pp.ids, \
-                                      pp.k1_order, sub == 1u ? pp.k1_rec : nullptr))
-        if (sub == 1u) {
-          if (stats) YODA_K1B(KK, true)
-          else if (pp.one_model) YODA_K1B(KK, false, false)
-          else YODA_K1B(KK, false)
-        } else {
-          if (stats) YODA_K1B(KK, true, true, false, kBlock / kWave)
-          else if (pp.one_model) YODA_K1B(KK, false, false, false, kBlock / kWave)
-          else YODA_K1B(KK, false, true, false, kBlock / kWave)
-        }
+                                      pp.k1_order, pp.k1_rec))
+        if (stats) YODA_K1B(KK, true)
+        else if (pp.one_model) YODA_K1B(KK, false, false)
+        else YODA_K1B(KK, false)
 #undef YODA_K1B
       } else {
         YODA_K_SWITCH(K, hipLaunchKernelGGL((k1_filter_maxima<KK, Path::N32>), grid, dim3(kBlock),
@@ -5107,8 +4993,6 @@ hipError_t launch_k1(int K, Path path, const unsigned char* nodes, const unsigne
   return hipGetLastError();
 }
 
-// Resident 256-thread workgroups of one K1 / K2 instantiation on the whole device (occupancy
-// API x CUs), for grid sizing.  which: 1 = K1, 2 = K2.
 int kernel_capacity(int K, Path path, int which, int mode_diskio) {
   int dev = 0, cus = 0, nb = 0;
   if (hipGetDevice(&dev) != hipSuccess) return 0;
@@ -5143,14 +5027,6 @@ int kernel_capacity(int K, Path path, int which, int mode_diskio) {
 // chunks, one wave per pod (strided over chunks) when there are many.
 constexpr uint32_t kWaveReduceChunks = 48;
 
-hipError_t launch_prep2(const uint64_t* maxima, uint32_t n_pods, double* rcp,
-                        hipStream_t s);
-
-// rcp non-null: also the reciprocals (k_prep2 fused; the wave variant runs it after)
-// nw: the block K1's partial words (kNarrowWords / kWideWords), 0: u64 partials [6][C][P]
-// lpt_w / lpt_order non-null: also the block K2's heaviest-first pod-block order (k_lpt_order;
-// in k_reduce1's grid as one extra workgroup where that kernel runs)
-hipError_t launch_lpt_order(uint32_t* wts, uint32_t n_pods, uint32_t* order, hipStream_t s);
 hipError_t launch_reduce1(const Partials& part, uint32_t C, uint32_t n_pods, uint32_t nw,
                           uint64_t* maxima, uint32_t* counts, double* rcp,
                           const MemTab& mt, hipStream_t s, uint32_t* lpt_w,
@@ -5328,9 +5204,6 @@ hipError_t launch_k2_topk(int K, Path path, const unsigned char* nodes, uint32_t
   return hipGetLastError();
 }
 
-// The block K2's packed-key top-k (N32 path with node summaries; DESIGN.md §5 greedy):
-// keys [C][P][tk], merged by launch_topk_merge_keys.  counts: the pods' feasible-node counts
-// (a pod with none takes no part in the wave's bounds).
 hipError_t launch_k2_topk_block(int K, const unsigned char* nodes, const unsigned char* sum2,
                                 const uint64_t* blk, uint32_t blk_stride, uint32_t n_nodes,
                                 uint32_t chunk_nodes, uint32_t C, const PodParams& pp,
@@ -5346,7 +5219,7 @@ hipError_t launch_k2_topk_block(int K, const unsigned char* nodes, const unsigne
                     pp.kbub ? pp.kb_levels : nullptr, pp.kbub ? pp.kbdec : nullptr,
                     reinterpret_cast<unsigned long long*>(pp.gbest)};
 #define YODA_TOPKB(TKV, RKV, MIXV, Q32V)                                                        \
-  YODA_K_SWITCH(K, hipLaunchKernelGGL((k2_block_n32<KK, false, TKV, RKV, MIXV, Q32V>), grid,      \
+  YODA_K8_SWITCH(K, hipLaunchKernelGGL((k2_block_n32<KK, false, TKV, RKV, MIXV, Q32V>), grid,     \
                                       dim3(kBlock), 0, s, nodes, sum2, n_nodes, chunk_nodes, a,   \
                                       n_pods, bm, bm_stride, bs, bs_stride, blk, blk_stride,      \
                                       nullptr, nullptr, nullptr, nullptr, nullptr, keys, ib))
@@ -5372,7 +5245,6 @@ hipError_t launch_k2_topk_block(int K, const unsigned char* nodes, const unsigne
   return hipGetLastError();
 }
 
-// The 16-deep chunk lists merged into ko-deep exact-prefix lists (k_topk_merge_deep).
 hipError_t launch_topk_merge_deep(const uint64_t* keys, uint32_t C, uint32_t n_pods, uint32_t ib,
                                   uint32_t node_offset, double* out_s, uint32_t* out_i, int tk,
                                   int ko, hipStream_t s) {
@@ -5919,7 +5791,6 @@ hipError_t launch_bitmask_transpose(const uint64_t* bm, uint32_t bm_stride, cons
   return hipGetLastError();
 }
 
-// The block K1 with witnesses (one-model N32 snapshots with summaries): sparse masks, blk.
 hipError_t launch_k1_block_witness(int K, const unsigned char* nodes, const unsigned char* sum,
                                    const unsigned char* sum2, const unsigned char* mix,
                                    uint32_t n_nodes, uint32_t chunk_nodes, uint32_t C,

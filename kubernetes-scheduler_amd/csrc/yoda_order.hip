@@ -15,6 +15,7 @@
 #include <cstdint>
 
 #include "yoda_layout.h"
+#include "yoda_launch.h"
 
 namespace yoda {
 
@@ -108,7 +109,6 @@ __global__ __launch_bounds__(kBlock) void k_permute(PermTable t, const uint32_t*
     static_cast<uint32_t*>(t.dst[a])[d] = static_cast<const uint32_t*>(t.src[a])[s];
 }
 
-// Scratch for the sort: keys[2][P] u64, idx[2][P] u32, then hipcub's temp storage.
 size_t order_scratch_bytes(uint32_t n_pods) {
   size_t temp = 0, temp32 = 0;
   (void)hipcub::DeviceRadixSort::SortPairs(nullptr, temp, (const uint64_t*)nullptr,
@@ -120,7 +120,6 @@ size_t order_scratch_bytes(uint32_t n_pods) {
   return 16ull * n_pods + 8ull * n_pods + 256 + (temp > temp32 ? temp : temp32);
 }
 
-// perm[i] = the original index of the i-th pod in sorted order.
 hipError_t launch_order_pods(const uint64_t* number, const uint64_t* m_u, const uint64_t* c_u,
                              const uint32_t* need_mem, uint32_t n_pods, const uint32_t key_bits[3],
                              const uint64_t* groups, uint32_t n_groups, void* scratch,
@@ -302,7 +301,6 @@ __global__ __launch_bounds__(kBlock) void k_order_scatter(PermTable t,
   }
 }
 
-// t: the pod arrays (src = caller order, dst = sorted order); scratch: slot, bkt [P] u32.
 hipError_t launch_order_count(const OrderMeta& o, const uint64_t* number, const uint32_t* m32,
                               const uint32_t* c32, const uint32_t* need_mem, uint32_t n_pods,
                               uint32_t* hist, uint32_t* bstart, uint32_t* slot, uint32_t* bkt,

@@ -56,12 +56,23 @@ def test_struct_layouts_match_header():
 # Policy knobs of the A/B harness: read from the environment only by libyoda_ab.so
 # (`make -C kubernetes-scheduler_amd/csrc ab`, -DYODA_AB_KNOBS).  The release library must
 # ignore them -- a scheduler inherits its environment -- so their names are not even in it.
-AB_KNOBS = ("YODA_NODE_PERM", "YODA_ORDER_PAD", "YODA_NO_GTAB", "YODA_CHUNK_ROUNDS",
-            "YODA_MIN_CHUNK_NODES", "YODA_K1_MAX_CHUNKS", "YODA_BLOCK_WITNESS",
-            "YODA_TOPK_PER_PAIR", "YODA_TOPK_ROUNDS", "YODA_UPLOAD_THREADS",
-            "YODA_GREEDY_WINDOW", "YODA_GREEDY_TOPK", "YODA_GREEDY_REFRESH",
-            "YODA_GREEDY_GROW_PCT", "YODA_GREEDY_CAP_TOPK", "YODA_GREEDY_CAP_SCAN",
-            "YODA_GREEDY_FAIL_DIV")
+AB_KNOBS = (
+    # the tuners libyoda_ab.so reads
+    "YODA_CHUNK_ROUNDS", "YODA_CHUNK_ROUNDS1", "YODA_CHUNK_ROUNDS2", "YODA_MIN_CHUNK_NODES",
+    "YODA_K1_MAX_CHUNKS", "YODA_WIT_CHUNK_NODES", "YODA_TOPK_ROUNDS", "YODA_TOPK_MIN_CHUNK",
+    "YODA_UPLOAD_THREADS", "YODA_UPLOAD_MIN_RANGE", "YODA_POOL_SPIN_US", "YODA_GREEDY_WINDOW",
+    "YODA_GREEDY_TOPK", "YODA_GREEDY_REFRESH_EVERY", "YODA_GREEDY_REFRESH_MIN",
+    "YODA_GREEDY_CAP_DEPTH", "YODA_GREEDY_CAP_SCAN", "YODA_GREEDY_CAP_SCAN_MAX",
+    "YODA_GREEDY_GROW_PCT",
+    # the path selectors it still reads (no measurement on record settles them)
+    "YODA_KB_LEVELS", "YODA_SEEDS", "YODA_GBEST", "YODA_KB_DEC_GROUPED", "YODA_TOPK_PER_PAIR",
+    "YODA_WIN_DMA", "YODA_GREEDY_FAIL_DIV",
+    # retired selectors (DESIGN.md "Tried and dropped"): no build reads them any more
+    "YODA_K1_SUB", "YODA_KB_DEC", "YODA_CMASK", "YODA_K1_LPT", "YODA_K1_REC",
+    "YODA_BLOCK_WITNESS", "YODA_TOPK_GBEST", "YODA_TOPK_DEC", "YODA_NODE_PERM",
+    "YODA_NODE_PERM_MIXED", "YODA_NODE_ZORDER", "YODA_ZORDER_RANKS", "YODA_NO_GTAB",
+    "YODA_ORDER_PAD", "YODA_LPT", "YODA_SIDE_COPY", "YODA_GREEDY_REFRESH",
+    "YODA_GREEDY_CAP_TOPK")
 
 
 def test_release_library_ignores_ab_knobs():

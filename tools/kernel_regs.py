@@ -15,14 +15,21 @@ OBJ = os.environ.get("OBJ") or os.path.join(os.path.dirname(os.path.abspath(__fi
                                              "yoda_kernels.o")
 
 
-def notes(obj):
+def code_object(obj, co):
+    """The gfx950 code object of a host object's fat binary, written to `co`."""
     with tempfile.TemporaryDirectory() as t:
-        fat, co = os.path.join(t, "fat.bin"), os.path.join(t, "k.co")
+        fat = os.path.join(t, "fat.bin")
         subprocess.run([f"{L}/llvm-objcopy", f"--dump-section=.hip_fatbin={fat}", obj,
                         os.devnull], check=True)
         subprocess.run([f"{L}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={fat}",
                         "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"],
                        check=True)
+
+
+def notes(obj):
+    with tempfile.TemporaryDirectory() as t:
+        co = os.path.join(t, "k.co")
+        code_object(obj, co)
         return subprocess.run([f"{L}/llvm-readelf", "--notes", co], check=True,
                               capture_output=True, text=True).stdout
 
