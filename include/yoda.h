@@ -221,8 +221,10 @@ int yoda_eval(yoda_t* h, const yoda_pod_soa* pods, int mode, yoda_eval_out* out)
  * passes its slice's first index as pod_base (the slices' picks are then the unsliced batch's);
  * one that wants fresh draws per batch changes the seed.  On the U64 record path the pods that
  * go through the exact normalize draw over the nodes of the top NORMALIZED score.
- * Only yoda_run / yoda_eval draw: yoda_shard_*, yoda_comm_*, yoda_greedy* and yoda_score_rows*
- * keep the lowest-node rule whether or not the draw is enabled.
+ * yoda_run / yoda_eval draw; the node-sharded evaluation step (yoda_comm_run*, yoda_shard_*)
+ * draws once yoda_shard_tie_draw turns it on as well (below), with picks bit-identical to one
+ * handle holding the whole snapshot.  yoda_greedy*, yoda_comm_greedy*, the greedy-window entry
+ * points and yoda_score_rows* keep the lowest-node rule whether or not a draw is enabled.
  * YODA_ERR_INVALID_ARG on a NULL handle. */
 int yoda_set_tie_draw(yoda_t* h, int enable, uint64_t seed, uint64_t pod_base);
 /* Host only.  For fixed (seed, pod) a bijection of the 32-bit node ids: no two nodes share a word. */
@@ -289,6 +291,30 @@ int yoda_shard_overflow_count(yoda_t* h, uint32_t* n_pods);
 int yoda_shard_exact_records(yoda_t* h, void* d_rec);
 int yoda_shard_exact_merge(yoda_t* h, const void* d_all, int world);
 
+/* Node shards draw too.  Default 0.  With it on AND yoda_set_tie_draw enabled on the handle,
+ * the sharded evaluation step ends in the draw: yoda_comm_run / yoda_comm_run_local do it
+ * themselves; a caller driving yoda_shard_* adds the exchange below.  Every shard of a batch
+ * must use the same (enable, seed, pod_base).  The greedy-window entry points, yoda_comm_greedy*
+ * and yoda_score_rows* keep the lowest node regardless.  With it off (or yoda_set_tie_draw
+ * off) the sharded step launches what it always did. */
+int yoda_shard_tie_draw(yoda_t* h, int enable);
+/* After yoda_shard_finalize.  When yoda_shard_overflow_count reports pods, after
+ * yoda_shard_exact_merge instead.  Writes d_keys [P] u64 (device), ALWAYS in the caller's pod
+ * order whatever yoda_shard_exchange_order says.  A pod that ended YODA_STATUS_OK with GLOBAL
+ * n_ties >= 2 gets the MIN of (yoda_tie_hash << 32 | global node) over THIS shard's nodes
+ * that are feasible and score the pod's GLOBAL best.  On the U64 path a pod sent through the
+ * exact normalize uses the global top NORMALIZED score instead.  ~0 when this shard holds no
+ * such node or the pod does not draw. */
+int yoda_shard_draw_keys(yoda_t* h, int mode, uint64_t* d_keys);
+/* The caller all-reduces d_keys with an unsigned 64-bit MIN over the ranks (8 P bytes per
+ * rank), then: pick <- the key's low 32 bits where key != ~0.  Only pick changes: status,
+ * n_feasible, n_ties, top_score and maxima stay what the step gave.
+ * Both calls: YODA_ERR_INVALID_ARG for a NULL handle or buffer; YODA_ERR_STATE, the picks left
+ * as they were, before a sharded finalize, while exact-normalize pods are pending, after a
+ * private yoda_run, with the shard draw or the handle's draw disabled, and for
+ * yoda_shard_draw_apply without this step's yoda_shard_draw_keys before it. */
+int yoda_shard_draw_apply(yoda_t* h, const uint64_t* d_keys);
+
 /* ---- multi-GPU without a host framework: RCCL inside libyoda ------------------------
  * For callers that have no torch.distributed (the Go plugin through cgo, C).  One handle per
  * GPU holds a node shard (yoda_upload_nodes with its node_offset) and the same pod batch.
@@ -299,7 +325,10 @@ int yoda_shard_exact_merge(yoda_t* h, const void* d_all, int world);
  * on the fast record paths the packed-key merge: all-reduce(MAX) of each shard's
  * (best << ib | 2^ib - 1 - node) key, then all-reduce(SUM) of the winners' tie counts (the
  * U64 path in Mode A all-gathers (best, index, ties, lowest) records instead); finalize --
- * and leaves the picks for yoda_download, like yoda_run.  All shards must run the same
+ * then, only with yoda_shard_tie_draw on, the draw: all-reduce(MIN) of the shards' draw keys
+ * [P] u64 -- and leaves the picks for yoda_download, like yoda_run.  The first all-reduce also
+ * carries a digest of the draw settings and its complement: shards that disagree on them all
+ * fail with YODA_ERR_STATE (the handles stay usable).  All shards must run the same
  * record path.  librccl.so.1 is opened at the first call (not a link dependency).
  * yoda_comm_run_local runs the same step for `world` shard handles of ONE process on one
  * device, with device copies as the transport (tests, single-process use). */

@@ -360,7 +360,16 @@ struct yoda_handle {
   bool tie_draw = false;
   uint64_t tie_seed = 0, tie_pod_base = 0;
   DevBuf draw_list, draw_keys, draw_n;
-  int cap[2][3][2] = {};         // resident workgroups per (kernel, path, mode), cached
+  // The draw of a node-sharded step (yoda_shard_tie_draw; it draws only beside tie_draw).
+  // draw_stage: 0 no sharded outcome to draw on, 1 a sharded finalize completed (its exact
+  // merge may still be pending: k3_pending), 2 yoda_shard_draw_keys emitted that step's keys.
+  // xkeys: comm_step's key buffer [P]; norm_top: the exact merge's GLOBAL top normalized
+  // scores by sorted position (k_merge3_top)
+  bool shard_draw = false;
+  int draw_stage = 0;
+  DevBuf xkeys, norm_top;
+  bool shard_draws() const { return shard_draw && tie_draw; }
+  int cap[2][3][2] = {};        // resident workgroups per (kernel, path, mode), cached
   int last_mode = -1;
   bool ran = false;
   bool ran_bitmask = false;
@@ -2684,6 +2693,7 @@ static int prepare_run(yoda_t* h, int mode, bool pad = false) {
   int rc = check_ready(h, mode);
   if (rc) return rc;
   h->topk_ready = false;  // this run overwrites the bitmask and reciprocals
+  h->draw_stage = 0;      // ... and the outcome a sharded draw would read
   const bool ordering = h->order_enabled && mode == YODA_MODE_SCV &&
                         h->n_pods >= kOrderMinPods && h->n_nodes > 0;
   // a private run takes the counting sort, padded when that adds at most 1/8 of the batch
@@ -3006,6 +3016,101 @@ uint32_t yoda_tie_hash(uint64_t seed, uint64_t pod, uint32_t node) {
   return tie_word(tie_pod_state(seed, pod), node);
 }
 
+// ---- the draw of a node-sharded step ----------------------------------------------------
+int yoda_shard_tie_draw(yoda_t* h, int enable) {
+  if (!h) return YODA_ERR_INVALID_ARG;
+  h->shard_draw = enable != 0;
+  return YODA_OK;
+}
+
+// The state both passes need: a completed sharded step of this mode, with the draw enabled.
+static int shard_draw_ready(yoda_t* h, const char* what) {
+  const std::string w(what);
+  if (!h->shard_draws())
+    return fail(h, YODA_ERR_STATE, w + ": the draw is disabled (yoda_set_tie_draw and "
+                                       "yoda_shard_tie_draw enable it)");
+  if (!h->has_nodes || !h->has_pods || !h->ran || h->draw_stage == 0)
+    return fail(h, YODA_ERR_STATE, w + " needs a completed yoda_shard_finalize / yoda_comm_run "
+                                       "of this batch");
+  if (h->k3_pending)
+    return fail(h, YODA_ERR_STATE,
+                w + ": exact normalize pending: run yoda_shard_exact_records / "
+                    "yoda_shard_exact_merge first");
+  return YODA_OK;
+}
+
+// The finalized outcome is in the caller's order by now and GLOBAL; the pod arrays, reciprocals,
+// masks and lowest scores are in the step's sorted order, as draw_pass finds them.
+static DrawArgs shard_draw_args(yoda_t* h) {
+  DrawArgs a{};
+  a.perm = h->ordered ? h->perm.as<uint32_t>() : nullptr;
+  a.n_work = h->n_work;
+  a.n_pods = h->n_pods;
+  a.status = h->status.as<int32_t>();
+  a.ties = h->ties_out.as<uint32_t>();
+  a.best = h->best.as<int64_t>();
+  a.pick = h->pick.as<int32_t>();
+  a.list = h->draw_list.as<uint32_t>();
+  a.n_list = h->draw_n.as<uint32_t>();
+  a.seed = h->tie_seed;
+  a.pod_base = h->tie_pod_base;
+  a.node_offset = h->node_offset;
+  a.norm_top = h->norm_top.as<int64_t>();
+  return a;
+}
+
+int yoda_shard_draw_keys(yoda_t* h, int mode, uint64_t* d_keys) {
+  if (!h) return YODA_ERR_INVALID_ARG;
+  if (!d_keys) return fail(h, YODA_ERR_INVALID_ARG, "NULL key buffer");
+  if (mode != YODA_MODE_SCV && mode != YODA_MODE_DISKIO)
+    return fail(h, YODA_ERR_INVALID_ARG, "mode must be YODA_MODE_SCV or YODA_MODE_DISKIO");
+  int rc = shard_draw_ready(h, "yoda_shard_draw_keys");
+  if (rc) return rc;
+  if (mode != h->last_mode)
+    return fail(h, YODA_ERR_STATE, "yoda_shard_draw_keys: the step ran in the other mode");
+  try {
+    HIP_TRY(h, hipSetDevice(h->device));
+    const uint32_t W = h->n_work;
+    if (W == 0 || h->n_pods == 0) {
+      h->draw_stage = 2;
+      return YODA_OK;
+    }
+    const bool diskio = mode == YODA_MODE_DISKIO;
+    if (!diskio && h->generic && h->maxima_sorted)
+      return fail(h, YODA_ERR_STATE, "draw keys: generic maxima still in sorted order");
+    HIP_TRY(h, h->draw_list.ensure((size_t)W * 4));
+    HIP_TRY(h, h->draw_n.ensure(16));
+    // (k_merge3_top filled it for the pods the exact merge handled; the key kernel reads no
+    // other entry)
+    if (!diskio && h->generic) HIP_TRY(h, h->norm_top.ensure((size_t)W * 8));
+    DrawArgs a = shard_draw_args(h);
+    a.keys = reinterpret_cast<unsigned long long*>(d_keys);
+    HIP_TRY(h, launch_shard_draw_keys(
+                   h->K, h->path, diskio ? 1 : 0, h->nodes.as<unsigned char>(),
+                   h->nodes_b.as<NodeRecB>(), h->n_nodes, pod_params(h), h->rcp.as<double>(),
+                   h->maxima.as<uint64_t>(), h->lowest.as<int64_t>(), h->bitmask.as<uint64_t>(),
+                   bm_row(h->n_nodes), h->bs_ptr(), bs_row(h->n_nodes), h->blk_ptr(),
+                   blk_row(h->n_nodes), a, h->stream));
+    h->draw_stage = 2;
+    return YODA_OK;
+  } catch (...) {
+    return fail(h, YODA_ERR_INVALID_ARG, "unexpected exception");
+  }
+}
+
+int yoda_shard_draw_apply(yoda_t* h, const uint64_t* d_keys) {
+  if (!h) return YODA_ERR_INVALID_ARG;
+  if (!d_keys) return fail(h, YODA_ERR_INVALID_ARG, "NULL key buffer");
+  int rc = shard_draw_ready(h, "yoda_shard_draw_apply");
+  if (rc) return rc;
+  if (h->draw_stage != 2)
+    return fail(h, YODA_ERR_STATE, "yoda_shard_draw_apply before this step's yoda_shard_draw_keys");
+  HIP_TRY(h, hipSetDevice(h->device));
+  HIP_TRY(h, launch_shard_draw_apply(shard_draw_args(h), d_keys, h->stream));
+  h->draw_stage = 1;  // applied: another apply needs another key pass
+  return YODA_OK;
+}
+
 // ---- sharded entry points -------------------------------------------------------------
 int yoda_shard_exchange_order(yoda_t* h, int caller_order) {
   if (!h || (caller_order != 0 && caller_order != 1)) return YODA_ERR_INVALID_ARG;
@@ -3104,6 +3209,10 @@ int yoda_shard_finalize(yoda_t* h, int mode, const uint32_t* d_counts, const int
         HIP_TRY(h, hipMemcpyAsync(h->counts.p, d_counts, 2ull * P * 4, hipMemcpyDeviceToDevice,
                                   h->stream));
         HIP_TRY(h, hipMemcpyAsync(h->best.p, d_best, P * 8ull, hipMemcpyDeviceToDevice, h->stream));
+        // the sharded draw's U64 key pass repeats finalize's normalize test on the GLOBAL lowest
+        if (h->shard_draws() && h->generic && d_lowest != h->lowest.p)
+          HIP_TRY(h, hipMemcpyAsync(h->lowest.p, d_lowest, P * 8ull, hipMemcpyDeviceToDevice,
+                                    h->stream));
       }
       if ((rc = finalize(h, mode, h->counts.as<uint32_t>(), h->best.as<int64_t>(), d_idx, d_ties,
                          d_lowest, true)))
@@ -3112,6 +3221,7 @@ int yoda_shard_finalize(yoda_t* h, int mode, const uint32_t* d_counts, const int
     h->ran = true;
     h->ran_bitmask = false;
     h->last_mode = mode;
+    h->draw_stage = 1;
     return YODA_OK;
   } catch (...) {
     return fail(h, YODA_ERR_INVALID_ARG, "unexpected exception");
@@ -3136,6 +3246,12 @@ int yoda_shard_exact_merge(yoda_t* h, const void* d_all, int world) {
                              h->flagged.as<uint32_t>(), h->n_flagged.as<uint32_t>(), h->k3_nfl,
                              h->pick.as<int32_t>(), h->status.as<int32_t>(),
                              h->ties_out.as<uint32_t>(), h->stream));
+    if (h->shard_draws()) {  // the draw's key pass compares against the GLOBAL top normalized
+      HIP_TRY(h, h->norm_top.ensure((size_t)h->n_work * 8));
+      HIP_TRY(h, launch_merge3_top(static_cast<const ShardRec*>(d_all), h->n_work, (uint32_t)world,
+                                   h->flagged.as<uint32_t>(), h->n_flagged.as<uint32_t>(),
+                                   h->k3_nfl, h->norm_top.as<int64_t>(), h->stream));
+    }
     h->k3_pending = false;
     return unpermute_outputs(h);
   } catch (...) {
@@ -5416,7 +5532,10 @@ static int greedy_capacity(yoda_t* h, const yoda_pod_soa* pods, int32_t* pick) {
 //      lowest node reaching it) as one u64 key, all-reduce(MAX) [P], then the winners' tie
 //      counts all-reduce(SUM) [P] (k_pack_key / k_unpack_key); the U64 path in Mode A, whose
 //      normalize check needs the lowest score too, all-gathers each shard's ShardRec [P]
-//      (best, lowest index reaching it, ties, lowest) and folds them (k_merge_rec).
+//      (best, lowest index reaching it, ties, lowest) and folds them (k_merge_rec);
+//   3. (rare) the U64 path's exact-normalize records, all-gathered and merged;
+//   4. only when the shards draw (yoda_shard_tie_draw beside yoda_set_tie_draw, yoda_comm_run*
+//      only): each shard's MIN draw key per tied pod, all-reduce(MIN) [P] u64, then the apply.
 // `hs` are the shards this process drives: one handle with an RCCL communicator
 // (yoda_comm_run), or every shard of the batch on one device with device copies as the
 // transport (yoda_comm_run_local, for tests and single-process use).
@@ -5435,10 +5554,21 @@ static uint32_t bit_length(uint64_t v) {
 //       f32 shard is exact only while the global small-field max is <= kF32SmallMax too;
 //       otherwise the shards must re-upload with YODA_UPLOAD_F64_QUOTIENTS (dist.agree_on_path
 //       does) -- quotient_disagreement names that instead of returning inexact scores.
-constexpr int kAgreeWords = 4;
+//   [4] a digest of the shard's draw settings (enable, seed, pod_base; 0: no draw in this step)
+//       and [5] its bitwise complement: after the MAX the two are complements of each other iff
+//       every shard sent the same digest (max d == min d), so every rank sees a disagreement.
+constexpr int kAgreeWords = 6;
 constexpr size_t kAgreeBytes = 8 * kAgreeWords;
 
-static void agreement_words(const yoda_t* h, int mode, uint64_t* w) {
+static uint64_t draw_digest(const yoda_t* h) {
+  if (!h->shard_draws()) return 0;
+  return tie_mix64(tie_mix64(h->tie_seed) ^ (h->tie_pod_base + 0x9E3779B97F4A7C15ull)) | 1ull;
+}
+
+// draw: a step that may end in the draw (yoda_comm_run*; the greedy's steps never do)
+static void agreement_words(const yoda_t* h, int mode, uint64_t* w, bool draw = false) {
+  w[4] = draw ? draw_digest(h) : 0;
+  w[5] = ~w[4];
   w[0] = h->generic && mode == YODA_MODE_SCV ? 64u : bit_length(h->score_bound);
   w[1] = bit_length((uint64_t)h->node_offset + h->n_nodes + 1);
   const bool f32q = mode == YODA_MODE_SCV && h->path == Path::N32 && h->q32;
@@ -5455,7 +5585,7 @@ static const char* quotient_disagreement(uint64_t global_small_max, uint64_t any
   return nullptr;
 }
 
-static int comm_step(yoda_t* const* hs, int n, int world, int mode, bool local) {
+static int comm_step(yoda_t* const* hs, int n, int world, int mode, bool local, bool draw) {
   yoda_t* h0 = hs[0];
   const uint32_t P = h0->n_pods;
   const size_t n1 = 6 * (size_t)P + kAgreeWords;  // maxima | agreement words
@@ -5485,7 +5615,7 @@ static int comm_step(yoda_t* const* hs, int n, int world, int mode, bool local) 
     // agreement words (pinned staging, one slot per shard; the previous step's copies
     // finished before its read-back below)
     uint64_t agree[kAgreeWords];
-    agreement_words(h, mode, agree);
+    agreement_words(h, mode, agree, draw);
     HIP_TRY(h0, h0->win_stage.ensure(kAgreeBytes * ((size_t)n + 1)));
     unsigned char* slot =
         static_cast<unsigned char*>(h0->win_stage.p) + kAgreeBytes * ((size_t)i + 1);
@@ -5533,7 +5663,7 @@ static int comm_step(yoda_t* const* hs, int n, int world, int mode, bool local) 
       return fail(h0, YODA_ERR_HIP, std::string("ncclAllReduce: ") + rccl().error_string(r));
   }
   // the agreed phase-2 form (every shard reads the same reduced words; one host wait per step)
-  uint64_t agreed[kAgreeWords] = {64, 64, 0, 0};
+  uint64_t agreed[kAgreeWords] = {64, 64, 0, 0, 0, ~0ull};
   HIP_TRY(h0, hipMemcpyAsync(h0->win_stage.p, h0->ex1.as<uint64_t>() + 6 * (size_t)P,
                              kAgreeBytes, hipMemcpyDeviceToHost, h0->stream));
   HIP_TRY(h0, hipStreamSynchronize(h0->stream));
@@ -5541,6 +5671,14 @@ static int comm_step(yoda_t* const* hs, int n, int world, int mode, bool local) 
   // every rank reads the same reduced words, so every rank fails here together
   if (const char* why = quotient_disagreement(agreed[2], agreed[3]))
     return fail(h0, YODA_ERR_STATE, why);
+  if (agreed[4] != ~agreed[5]) {
+    for (int i = 0; i < n; ++i)
+      fail(hs[i], YODA_ERR_STATE,
+           "shards disagree on the draw settings: yoda_set_tie_draw (enable, seed, pod_base) and "
+           "yoda_shard_tie_draw must be the same on every shard of a batch");
+    return YODA_ERR_STATE;
+  }
+  const bool drawing = agreed[4] != 0;  // (so every shard of the batch has it enabled)
   const uint32_t ib = (uint32_t)std::max<uint64_t>(1, agreed[1]);
   const bool packed = agreed[0] + ib <= 63 && ib <= 40;
   for (int i = 0; i < n; ++i) {
@@ -5631,6 +5769,7 @@ static int comm_step(yoda_t* const* hs, int n, int world, int mode, bool local) 
     h->ran = true;
     h->ran_bitmask = false;
     h->last_mode = mode;
+    h->draw_stage = 1;
   }
   // exchange 3 (rare: U64 pods whose NormalizeScore can overflow int64, scheduler.go:176-179):
   // every shard's exact-normalize records to every shard, then the merge (all shards flag the
@@ -5651,6 +5790,33 @@ static int comm_step(yoda_t* const* hs, int n, int world, int mode, bool local) 
     }
     for (int i = 0; i < n; ++i) {
       int rc = yoda_shard_exact_merge(hs[i], hs[i]->k3all.p, world);
+      if (rc) return rc;
+    }
+  }
+  // exchange 4 (only with the shard draw on): every shard's MIN draw key per tied pod over its
+  // own top-scored nodes, all-reduce(MIN) [P] u64, then every shard takes the winner's node
+  if (drawing) {
+    for (int i = 0; i < n; ++i) {
+      yoda_t* h = hs[i];
+      HIP_TRY(h, h->xkeys.ensure((size_t)P * 8));
+      int rc = yoda_shard_draw_keys(h, mode, h->xkeys.as<uint64_t>());
+      if (rc) return rc;
+    }
+    if (local) {
+      PtrList l{};
+      for (int i = 0; i < n; ++i) l.p[i] = hs[i]->xkeys.p;
+      HIP_TRY(h0, launch_min_multi(l, (uint32_t)n, P, h0->rec_all.as<uint64_t>(), h0->stream));
+      for (int i = 0; i < n; ++i)
+        HIP_TRY(h0, hipMemcpyAsync(hs[i]->xkeys.p, h0->rec_all.p, (size_t)P * 8,
+                                   hipMemcpyDeviceToDevice, h0->stream));
+    } else {
+      const ncclResult_t r = rccl().all_reduce(h0->xkeys.p, h0->xkeys.p, P, ncclUint64, ncclMin,
+                                               h0->comm, h0->stream);
+      if (r != ncclSuccess)
+        return fail(h0, YODA_ERR_HIP, std::string("ncclAllReduce: ") + rccl().error_string(r));
+    }
+    for (int i = 0; i < n; ++i) {
+      int rc = yoda_shard_draw_apply(hs[i], hs[i]->xkeys.as<uint64_t>());
       if (rc) return rc;
     }
   }
@@ -5756,7 +5922,8 @@ struct Coll {
   }
 };
 
-static int comm_step(yoda_t* const* hs, int n, int world, int mode, bool local);
+static int comm_step(yoda_t* const* hs, int n, int world, int mode, bool local,
+                     bool draw = false);
 
 // The sharded greedy's list merge (window exchange 2), shared by comm_greedy and the caller-
 // driven protocol (yoda_merge_shard_lists, dist.sharded_greedy): shard rk's list of window pod
@@ -6228,7 +6395,7 @@ int yoda_comm_run(yoda_t* h, int mode) {
   if (!h->comm) return fail(h, YODA_ERR_STATE, "yoda_comm_run before yoda_comm_init");
   try {
     yoda_t* hs[1] = {h};
-    return comm_step(hs, 1, h->comm_world, mode, false);
+    return comm_step(hs, 1, h->comm_world, mode, false, true);
   } catch (...) {
     return fail(h, YODA_ERR_INVALID_ARG, "unexpected exception");
   }
@@ -6301,7 +6468,7 @@ int yoda_comm_run_local(yoda_t* const* hs, int world, int mode) {
   }
   int rc;
   try {
-    rc = comm_step(hs, world, world, mode, true);
+    rc = comm_step(hs, world, world, mode, true, true);
   } catch (...) {
     rc = fail(hs[0], YODA_ERR_INVALID_ARG, "unexpected exception");
   }

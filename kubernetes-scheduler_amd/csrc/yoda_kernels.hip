@@ -15,6 +15,8 @@
 //   K3  k3_exact_normalize scheduler.go:176-179 with int64 wrap (generic path only)
 //       k_draw_*           k8s selectHost as a seeded draw over each tied pod's tie set (a
 //                          post-pass with LANE = NODE, only with yoda_set_tie_draw enabled)
+//       k_shard_draw_*     the same draw over node shards: MIN keys per caller pod, reduced
+//                          across the shards (only with yoda_shard_tie_draw enabled as well)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <algorithm>
@@ -6186,7 +6188,9 @@ __device__ __forceinline__ void draw_fold(unsigned long long* keys, uint32_t slo
 
 // Fast record paths (N32 / F64): workgroup = (a stride of the list, node chunk blockIdx.y).
 // ids: the local node id of each position in the block-grouped order (nullptr: identity).
-template <int K, Path PATH>
+// SHARD (every key kernel): the sharded step's key-emit pass -- the key goes to the pod's CALLER
+// slot of the dense [n_pods] buffer a.keys instead of the list slot (k_shard_draw_list).
+template <int K, Path PATH, bool SHARD>
 __global__ __launch_bounds__(kBlock) void k_draw_fast(const unsigned char* __restrict__ nodes,
                                                       uint32_t n_nodes, uint32_t chunk_nodes,
                                                       ScoreArgs sa, const MaskSrc ms, DrawArgs a) {
@@ -6211,7 +6215,7 @@ __global__ __launch_bounds__(kBlock) void k_draw_fast(const unsigned char* __res
         key = k < key ? k : key;
       }
     }
-    draw_fold(a.keys, i, key);
+    draw_fold(a.keys, SHARD ? o : i, key);
   }
 }
 
@@ -6219,7 +6223,10 @@ __global__ __launch_bounds__(kBlock) void k_draw_fast(const unsigned char* __res
 // exact normalize (the same test as k_finalize's) draws over the nodes of the top NORMALIZED
 // score, as k3_exact_normalize counts them: one sweep for that score, one for the keys.
 // maxima / best: caller order [6][n_pods] / [n_pods]; low: the run's sorted order.
-template <int K>
+// SHARD: best / low / maxima are the reduced GLOBAL ones, and the top normalized score of an
+// exact pod is the global one the exact merge left in a.norm_top (k_merge3_top), not a sweep
+// over this shard's nodes.
+template <int K, bool SHARD>
 __global__ __launch_bounds__(kBlock) void k_draw_generic(
     const unsigned char* __restrict__ nodes, uint32_t n_nodes, const uint64_t* __restrict__ m_u,
     const uint64_t* __restrict__ c_u, const uint64_t* __restrict__ maxima,
@@ -6240,7 +6247,9 @@ __global__ __launch_bounds__(kBlock) void k_draw_generic(
     const bool exact = (uint64_t)d > (uint64_t)(kI64Max / 100);
     const uint64_t st = tie_pod_state(a.seed, a.pod_base + o);
     int64_t top = h;
-    if (exact) {  // the top normalized score (block-uniform branch: i is)
+    if (SHARD) {
+      if (exact) top = a.norm_top[p];
+    } else if (exact) {  // the top normalized score (block-uniform branch: i is)
       int64_t bn = -1;
       for (uint32_t n = threadIdx.x; n < n_nodes; n += kBlock) {
         if (!draw_feasible(ms, p >> 6, p & 63u, n)) continue;
@@ -6269,11 +6278,12 @@ __global__ __launch_bounds__(kBlock) void k_draw_generic(
         key = k < key ? k : key;
       }
     }
-    draw_fold(a.keys, i, key);
+    draw_fold(a.keys, SHARD ? o : i, key);
   }
 }
 
 // Mode B: every node is feasible; the score of k2_diskio (algorithm.go:109-111, no FMA).
+template <bool SHARD>
 __global__ __launch_bounds__(kBlock) void k_draw_diskio(const NodeRecB* __restrict__ nodes,
                                                         uint32_t n_nodes, uint32_t chunk_nodes,
                                                         const double* __restrict__ alpha_in,
@@ -6303,7 +6313,7 @@ __global__ __launch_bounds__(kBlock) void k_draw_diskio(const NodeRecB* __restri
         key = k < key ? k : key;
       }
     }
-    draw_fold(a.keys, i, key);
+    draw_fold(a.keys, SHARD ? o : i, key);
   }
 }
 
@@ -6323,6 +6333,36 @@ __global__ __launch_bounds__(kBlock) void k_draw_write(DrawArgs a) {
 constexpr uint32_t kDrawChunk = 8 * kBlock;
 constexpr uint32_t kDrawMaxStrides = 256;
 
+// The key kernel of the run's record path over the listed pods (SHARD: see k_draw_fast).
+template <bool SHARD>
+static hipError_t launch_draw_keys(int K, Path path, int mode_diskio, const unsigned char* nodes,
+                             const NodeRecB* nodes_b, uint32_t n_nodes, const PodParams& pp,
+                             const double* rcp, const uint64_t* maxima, const int64_t* low,
+                             const MaskSrc& ms, const DrawArgs& a, hipStream_t s) {
+  const uint32_t gx = std::min(a.n_work, kDrawMaxStrides);
+  const uint32_t C = (n_nodes + kDrawChunk - 1) / kDrawChunk;
+  if (mode_diskio) {
+    hipLaunchKernelGGL(k_draw_diskio<SHARD>, dim3(gx, C), dim3(kBlock), 0, s, nodes_b, n_nodes,
+                       kDrawChunk, pp.alpha, pp.beta, a);
+  } else if (path == Path::U64) {
+    YODA_K_SWITCH(K, hipLaunchKernelGGL((k_draw_generic<KK, SHARD>), dim3(gx), dim3(kBlock), 0, s,
+                                        nodes, n_nodes, pp.m_u, pp.c_u, maxima, low, ms, a));
+  } else {
+    ScoreArgs sa{pp.m_f, pp.c_f, pp.m_32, pp.c_32, rcp};
+    sa.ids = pp.ids;
+    if (path == Path::N32) {
+      YODA_K_SWITCH(K, hipLaunchKernelGGL((k_draw_fast<KK, Path::N32, SHARD>), dim3(gx, C),
+                                          dim3(kBlock), 0, s, nodes, n_nodes, kDrawChunk, sa, ms,
+                                          a));
+    } else {
+      YODA_K_SWITCH(K, hipLaunchKernelGGL((k_draw_fast<KK, Path::F64, SHARD>), dim3(gx, C),
+                                          dim3(kBlock), 0, s, nodes, n_nodes, kDrawChunk, sa, ms,
+                                          a));
+    }
+  }
+  return hipSuccess;
+}
+
 hipError_t launch_draw(int K, Path path, int mode_diskio, const unsigned char* nodes,
                        const NodeRecB* nodes_b, uint32_t n_nodes, const PodParams& pp,
                        const double* rcp, const uint64_t* maxima, const int64_t* low,
@@ -6334,27 +6374,114 @@ hipError_t launch_draw(int K, Path path, int mode_diskio, const unsigned char* n
   hipError_t e = hipMemsetAsync(a.n_list, 0, 4, s);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_draw_list, pod_grid(a.n_work), dim3(kBlock), 0, s, a);
-  const uint32_t gx = std::min(a.n_work, kDrawMaxStrides);
-  const uint32_t C = (n_nodes + kDrawChunk - 1) / kDrawChunk;
   const MaskSrc ms{bm, bs, bm_stride, bs_stride, blk, blk_stride};
-  if (mode_diskio) {
-    hipLaunchKernelGGL(k_draw_diskio, dim3(gx, C), dim3(kBlock), 0, s, nodes_b, n_nodes,
-                       kDrawChunk, pp.alpha, pp.beta, a);
-  } else if (path == Path::U64) {
-    YODA_K_SWITCH(K, hipLaunchKernelGGL((k_draw_generic<KK>), dim3(gx), dim3(kBlock), 0, s, nodes,
-                                        n_nodes, pp.m_u, pp.c_u, maxima, low, ms, a));
-  } else {
-    ScoreArgs sa{pp.m_f, pp.c_f, pp.m_32, pp.c_32, rcp};
-    sa.ids = pp.ids;
-    if (path == Path::N32) {
-      YODA_K_SWITCH(K, hipLaunchKernelGGL((k_draw_fast<KK, Path::N32>), dim3(gx, C), dim3(kBlock),
-                                          0, s, nodes, n_nodes, kDrawChunk, sa, ms, a));
-    } else {
-      YODA_K_SWITCH(K, hipLaunchKernelGGL((k_draw_fast<KK, Path::F64>), dim3(gx, C), dim3(kBlock),
-                                          0, s, nodes, n_nodes, kDrawChunk, sa, ms, a));
-    }
-  }
+  e = launch_draw_keys<false>(K, path, mode_diskio, nodes, nodes_b, n_nodes, pp, rcp, maxima, low,
+                              ms, a, s);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_draw_write, pod_grid(a.n_work), dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
+// The draw of a node-sharded step (include/yoda.h yoda_shard_tie_draw), after
+// the sharded finalize (and the exact merge): status / ties / best are the GLOBAL outcome in
+// the caller's order.  Key-emit pass: k_shard_draw_list fills the dense caller-order key buffer
+// with ~0 and lists the run's positions whose pod draws; the SHARD key kernels fold each listed
+// pod's MIN key over THIS shard's top-scored nodes into keys[caller index] (padded copies of a
+// pod hash the same index and land in the same slot).  The caller MIN-reduces the keys over the
+// shards; k_shard_draw_apply then writes the winning node into pick.
+__global__ __launch_bounds__(kBlock) void k_shard_draw_list(DrawArgs a) {
+  const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+  if (p >= a.n_work) return;
+  const uint32_t o = a.perm ? a.perm[p] : p;
+  if (o >= a.n_pods) return;
+  a.keys[o] = ~0ull;  // (every caller slot is some position's; copies write the same)
+  if (a.status[o] != 0 || a.ties[o] < 2u) return;
+  a.list[atomicAdd(a.n_list, 1u)] = p;
+}
+
+__global__ __launch_bounds__(kBlock) void k_shard_draw_apply(
+    DrawArgs a, const unsigned long long* __restrict__ keys) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= min(*a.n_list, a.n_work)) return;
+  const uint32_t p = a.list[i];
+  const uint32_t o = a.perm ? a.perm[p] : p;
+  const uint64_t k = keys[o];
+  if (k != ~0ull) a.pick[o] = (int32_t)(uint32_t)k;
+}
+
+hipError_t launch_shard_draw_keys(int K, Path path, int mode_diskio, const unsigned char* nodes,
+                                  const NodeRecB* nodes_b, uint32_t n_nodes, const PodParams& pp,
+                                  const double* rcp, const uint64_t* maxima, const int64_t* low,
+                                  const uint64_t* bm, uint32_t bm_stride, const BlockMask* bs,
+                                  uint32_t bs_stride, const uint64_t* blk, uint32_t blk_stride,
+                                  const DrawArgs& a, hipStream_t s) {
+  if (a.n_work == 0 || a.n_pods == 0) return hipSuccess;
+  if (bs && !blk) return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(a.n_list, 0, 4, s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_shard_draw_list, pod_grid(a.n_work), dim3(kBlock), 0, s, a);
+  if (n_nodes == 0) return hipGetLastError();  // a shard without nodes: every key stays ~0
+  const MaskSrc ms{bm, bs, bm_stride, bs_stride, blk, blk_stride};
+  e = launch_draw_keys<true>(K, path, mode_diskio, nodes, nodes_b, n_nodes, pp, rcp, maxima, low,
+                             ms, a, s);
+  if (e != hipSuccess) return e;
+  return hipGetLastError();
+}
+
+hipError_t launch_shard_draw_apply(const DrawArgs& a, const uint64_t* keys, hipStream_t s) {
+  if (a.n_work == 0 || a.n_pods == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_shard_draw_apply, pod_grid(a.n_work), dim3(kBlock), 0, s, a,
+                     reinterpret_cast<const unsigned long long*>(keys));
+  return hipGetLastError();
+}
+
+// The exact merge's GLOBAL top normalized score of each flagged pod (the MAX of the shards'
+// records, as k_merge3 folds it), kept per sorted position for the sharded draw.
+__global__ __launch_bounds__(kBlock) void k_merge3_top(const ShardRec* __restrict__ all,
+                                                       uint32_t n_pods, uint32_t world,
+                                                       const uint32_t* __restrict__ flagged,
+                                                       const uint32_t* __restrict__ n_flagged_p,
+                                                       uint32_t max_flagged,
+                                                       int64_t* __restrict__ norm_top) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= min(*n_flagged_p, max_flagged)) return;
+  const uint32_t p = flagged[i];
+  int64_t best = -1;
+  for (uint32_t r = 0; r < world; ++r) {
+    const int64_t b = all[(size_t)r * n_pods + p].best;
+    best = b > best ? b : best;
+  }
+  norm_top[p] = best;
+}
+
+hipError_t launch_merge3_top(const ShardRec* all, uint32_t n_pods, uint32_t world,
+                             const uint32_t* flagged, const uint32_t* n_flagged,
+                             uint32_t max_flagged, int64_t* norm_top, hipStream_t s) {
+  if (max_flagged == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_merge3_top, pod_grid(max_flagged), dim3(kBlock), 0, s, all, n_pods, world,
+                     flagged, n_flagged, max_flagged, norm_top);
+  return hipGetLastError();
+}
+
+// In-process exchange: elementwise MIN of n u64 over the handles' buffers into dst.
+__global__ __launch_bounds__(kBlock) void k_min_multi(PtrList src, uint32_t k, uint64_t n,
+                                                      uint64_t* __restrict__ dst) {
+  const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (t >= n) return;
+  uint64_t m = ~0ull;
+  for (uint32_t j = 0; j < k; ++j) {
+    const uint64_t v = static_cast<const uint64_t*>(src.p[j])[t];
+    m = v < m ? v : m;
+  }
+  dst[t] = m;
+}
+
+hipError_t launch_min_multi(const PtrList& src, uint32_t k, uint64_t n, uint64_t* dst,
+                            hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_min_multi, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
+                     src, k, n, dst);
   return hipGetLastError();
 }
 

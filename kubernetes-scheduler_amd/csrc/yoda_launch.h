@@ -197,6 +197,20 @@ hipError_t launch_draw(int K, Path path, int mode_diskio, const unsigned char* n
                        const uint64_t* bm, uint32_t bm_stride, const BlockMask* bs,
                        uint32_t bs_stride, const uint64_t* blk, uint32_t blk_stride,
                        const DrawArgs& a, hipStream_t s);
+// The sharded draw (yoda_shard_draw_keys / _apply): a.keys is the dense caller-order [n_pods]
+// key buffer; a.best / a.status / a.ties the GLOBAL outcome; a.norm_top the exact merge's.
+hipError_t launch_shard_draw_keys(int K, Path path, int mode_diskio, const unsigned char* nodes,
+                                  const NodeRecB* nodes_b, uint32_t n_nodes, const PodParams& pp,
+                                  const double* rcp, const uint64_t* maxima, const int64_t* low,
+                                  const uint64_t* bm, uint32_t bm_stride, const BlockMask* bs,
+                                  uint32_t bs_stride, const uint64_t* blk, uint32_t blk_stride,
+                                  const DrawArgs& a, hipStream_t s);
+hipError_t launch_shard_draw_apply(const DrawArgs& a, const uint64_t* keys, hipStream_t s);
+hipError_t launch_merge3_top(const ShardRec* all, uint32_t n_pods, uint32_t world,
+                             const uint32_t* flagged, const uint32_t* n_flagged,
+                             uint32_t max_flagged, int64_t* norm_top, hipStream_t s);
+hipError_t launch_min_multi(const PtrList& src, uint32_t k, uint64_t n, uint64_t* dst,
+                            hipStream_t s);
 
 // ---- yoda_order.hip ----
 // Scratch for the sort: keys[2][P] u64, idx[2][P] u32, then hipcub's temp storage.

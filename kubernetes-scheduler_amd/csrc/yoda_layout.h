@@ -577,7 +577,8 @@ __host__ __device__ inline uint64_t tie_key(uint64_t s, uint32_t node) {
 // pods are its n_work sorted positions (perm[p] = the caller's index of position p; nullptr:
 // the run was not ordered); status / ties / best / pick are the finalized outputs in the
 // CALLER's order.  list [n_work] gets the positions that draw (status OK, ties >= 2), keys
-// [n_work] their running MIN key by list slot.
+// [n_work] their running MIN key by list slot.  The sharded draw (launch_shard_draw_keys) keeps
+// its keys in a dense [n_pods] buffer in the caller's order instead.
 struct DrawArgs {
   const uint32_t* perm;
   uint32_t n_work, n_pods;
@@ -590,6 +591,9 @@ struct DrawArgs {
   unsigned long long* keys;
   uint64_t seed, pod_base;
   uint32_t node_offset;
+  // the sharded draw's U64 exact-normalize pods: the GLOBAL top normalized score by sorted
+  // position (k_merge3_top); unused by a private run
+  const int64_t* norm_top = nullptr;
 };
 
 }  // namespace yoda

@@ -414,8 +414,9 @@ func (g *Handle) Batch(pods []*v1.Pod, mode Mode) (picks []int32, statuses []int
 // enabled, a pod that ends StatusOK with two or more top-scored nodes is placed on the one with
 // the smallest TieHash(seed, podBase+p, node) -- p its index in the batch, node the global node
 // id -- instead of the lowest.  podBase: the global index of the batch's first pod when the
-// caller slices a larger batch.  ScoreRow, Greedy and the sharded entry points keep the
-// lowest node either way.  Takes effect from the next Batch.
+// caller slices a larger batch.  ScoreRow and Greedy keep the lowest node either way; the
+// node-sharded step (CommRun) draws only once ShardTieDraw is on as well.  Takes effect from
+// the next Batch.
 func (g *Handle) SetTieDraw(enable bool, seed, podBase uint64) error {
 	on := C.int(0)
 	if enable {
@@ -423,6 +424,34 @@ func (g *Handle) SetTieDraw(enable bool, seed, podBase uint64) error {
 	}
 	return check(g.h, C.yoda_set_tie_draw(g.h, on, C.uint64_t(seed), C.uint64_t(podBase)),
 		"yoda_set_tie_draw")
+}
+
+// ShardTieDraw lets the node-sharded evaluation step draw too (yoda_shard_tie_draw): with it
+// on AND SetTieDraw enabled, CommRun ends in the draw -- one more all-reduce (MIN, 8 bytes a
+// pod) -- and the picks are those of one handle holding the whole snapshot.  Every shard of a
+// batch must use the same (enable, seed, podBase); CommRun fails on every rank otherwise.
+// Like the rest of this file, not compiled in this repository (no Go toolchain in the image).
+func (g *Handle) ShardTieDraw(enable bool) error {
+	on := C.int(0)
+	if enable {
+		on = 1
+	}
+	return check(g.h, C.yoda_shard_tie_draw(g.h, on), "yoda_shard_tie_draw")
+}
+
+// ShardDrawKeys and ShardDrawApply are the draw's two passes for a caller that drives the
+// yoda_shard_* calls with its own collectives: after the sharded finalize (and the exact
+// merge), ShardDrawKeys writes this shard's MIN draw key of every tied pod into dKeys -- DEVICE
+// memory, [P] uint64 in the caller's pod order, ^0 where it has none; the caller all-reduces
+// the keys over the ranks with an unsigned 64-bit MIN; ShardDrawApply then takes each key's
+// low 32 bits as the pod's pick.
+func (g *Handle) ShardDrawKeys(mode Mode, dKeys unsafe.Pointer) error {
+	return check(g.h, C.yoda_shard_draw_keys(g.h, C.int(mode), (*C.uint64_t)(dKeys)),
+		"yoda_shard_draw_keys")
+}
+
+func (g *Handle) ShardDrawApply(dKeys unsafe.Pointer) error {
+	return check(g.h, C.yoda_shard_draw_apply(g.h, (*C.uint64_t)(dKeys)), "yoda_shard_draw_apply")
 }
 
 // TieHash is the draw word of (seed, pod, node) (yoda_tie_hash; host only): for one pod a

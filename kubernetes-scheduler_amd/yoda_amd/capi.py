@@ -63,6 +63,9 @@ _SIGS = {
     "yoda_shard_overflow_count": ([_vp, C.POINTER(C.c_uint32)], C.c_int),
     "yoda_shard_exact_records": ([_vp, _vp], C.c_int),
     "yoda_shard_exact_merge": ([_vp, _vp, C.c_int], C.c_int),
+    "yoda_shard_tie_draw": ([_vp, C.c_int], C.c_int),
+    "yoda_shard_draw_keys": ([_vp, C.c_int, _vp], C.c_int),
+    "yoda_shard_draw_apply": ([_vp, _vp], C.c_int),
     "yoda_comm_greedy": ([_vp, C.POINTER(CNodeSoA), C.POINTER(CPodSoA), C.c_int, _u32,
                           C.POINTER(C.c_int32)], C.c_int),
     "yoda_comm_greedy_local": ([_vp, C.c_int, C.POINTER(CNodeSoA), C.POINTER(CPodSoA), C.c_int,
@@ -560,6 +563,23 @@ class Yoda:
     def shard_exact_merge(self, d_all: int, world: int):
         self._check(lib().yoda_shard_exact_merge(self._h, _vp(d_all), world),
                     "yoda_shard_exact_merge")
+
+    def shard_tie_draw(self, enable: bool):
+        """Node shards draw too (yoda_shard_tie_draw): with set_tie_draw enabled as well, comm_run
+        / comm_run_local end in the draw, and shard_draw_keys / shard_draw_apply serve a caller
+        driving the shard_* calls.  Every shard of a batch: the same setting, seed, pod_base."""
+        self._check(lib().yoda_shard_tie_draw(self._h, 1 if enable else 0), "yoda_shard_tie_draw")
+
+    def shard_draw_keys(self, mode: int, d_keys: int):
+        """After shard_finalize (and shard_exact_merge when pods overflowed): this shard's MIN
+        draw key of every tied pod into d_keys, [P] u64 on the device, caller's pod order (~0:
+        none).  The caller MIN-reduces them over the ranks, unsigned (dist.merge_draw_keys)."""
+        self._check(lib().yoda_shard_draw_keys(self._h, mode, _vp(d_keys)),
+                    "yoda_shard_draw_keys")
+
+    def shard_draw_apply(self, d_keys: int):
+        """pick <- the reduced key's node where a key was drawn (yoda_shard_draw_apply)."""
+        self._check(lib().yoda_shard_draw_apply(self._h, _vp(d_keys)), "yoda_shard_draw_apply")
 
     def comm_greedy(self, all_nodes, pods, mode: int = 0, flags: int = 0) -> np.ndarray:
         """yoda_comm_greedy: the greedy batch over the ranks' node shards (collective)."""

@@ -51,6 +51,8 @@ class ShardBuffers:
         # [lowest i64 | idx widened to i64]: both merge by MIN, so one all-reduce serves both
         self.mins = torch.empty(2 * P, dtype=torch.int64, device=device)
         self.lowest = self.mins[:P]
+        # the shard draw's MIN keys, u64 [P], caller's pod order (yoda_shard_draw_keys)
+        self.keys = torch.empty(P, dtype=torch.int64, device=device)
         # maxima need the sign flip only when a field can exceed 2^63 (U64 path); the fast
         # record paths bound every field by 2^44
         self.unsigned_maxima = True
@@ -196,6 +198,28 @@ def merge_phase2_packed(reduce: Reducer, bufs: List[ShardBuffers], ib: int):
     reduce([b.ties for b in bufs], "sum")
 
 
+def merge_draw_keys(reduce: Reducer, bufs: List[ShardBuffers]):
+    """The shard draw's exchange: the unsigned 64-bit MIN of the shards' keys (hash << 32 |
+    global node, ~0: none) -- through the signed view with the sign bit flipped, as the
+    unsigned maxima of merge_phase1.  8 P bytes per rank."""
+    for b in bufs:
+        _flip(b.keys, I64_SIGN)
+    reduce([b.keys for b in bufs], "min")
+    for b in bufs:
+        _flip(b.keys, I64_SIGN)
+
+
+def _draw_digest(tie_draw) -> int:
+    """A 62-bit digest of (seed, pod_base), 0 for no draw: equal settings, equal digests."""
+    if tie_draw is None:
+        return 0
+    import hashlib
+    seed, base = (int(v) & (2**64 - 1) for v in tie_draw)
+    d = hashlib.blake2b(seed.to_bytes(8, "little") + base.to_bytes(8, "little"),
+                        digest_size=8).digest()
+    return (int.from_bytes(d, "little") >> 2) | 1
+
+
 def merge_witness(reduce: Reducer, bufs: List[ShardBuffers], prepare: Callable):
     """Capacity greedy phase 1: global maxima (MAX) and counts (SUM) as merge_phase1, then the
     witnesses: a shard below a field's global maximum clears its witness of it (prepare),
@@ -245,8 +269,26 @@ class ShardExchange:
     """Drives libyoda handles (one per shard) through the sharded entry points."""
 
     def __init__(self, handles, reducer: Reducer, device, path_code=None, compact: bool = True,
-                 caller_order: bool = True):
+                 caller_order: bool = True, tie_draw=None):
+        """tie_draw: None, or (seed, pod_base) -- every step then ends in the seeded selectHost
+        draw (yoda_set_tie_draw + yoda_shard_tie_draw on the handles; one more MIN all-reduce of
+        [P] int64).  Every rank must pass the same value: checked here, with one MAX reduce."""
         self.handles = list(handles)
+        self.tie_draw = None if tie_draw is None else (int(tie_draw[0]), int(tie_draw[1]))
+        # a digest and its complement: after the MAX they are complements iff every rank agrees
+        d = [_draw_digest(self.tie_draw)]
+        chk = [torch.tensor([x, ~x], dtype=torch.int64, device=device)
+               for x in (d * len(self.handles))]
+        reducer(chk, "max")
+        lo, hi = (int(v) for v in chk[0].tolist())
+        if lo != ~hi:
+            raise ValueError("ShardExchange: the ranks disagree on tie_draw (seed, pod_base)")
+        for h in self.handles:
+            if self.tie_draw is None:
+                h.shard_tie_draw(False)
+            else:
+                h.set_tie_draw(*self.tie_draw)
+                h.shard_tie_draw(True)
         self.reduce = reducer
         self.device = device
         self.bufs = [ShardBuffers(h.n_pods, device) for h in self.handles]
@@ -276,23 +318,24 @@ class ShardExchange:
 
     @classmethod
     def local(cls, handles, device, shards=None, offsets=None, compact: bool = True,
-              caller_order: bool = True):
+              caller_order: bool = True, tie_draw=None):
         """Several shards in one process (single-GPU testing).  Pass the node shards to
         enforce a common record path."""
         red = Reducer(local=True)
         path = None
         if shards is not None:
             path = agree_on_path(red, handles, shards, offsets, device)
-        return cls(handles, red, device, path, compact=compact, caller_order=caller_order)
+        return cls(handles, red, device, path, compact=compact, caller_order=caller_order,
+                   tie_draw=tie_draw)
 
     @classmethod
-    def distributed(cls, handle, device, shard=None, offset=0, group=None):
+    def distributed(cls, handle, device, shard=None, offset=0, group=None, tie_draw=None):
         """One shard per rank over torch.distributed (RCCL)."""
         red = Reducer(group=group)
         path = None
         if shard is not None:
             path = agree_on_path(red, [handle], [shard], [offset], device)
-        return cls([handle], red, device, path)
+        return cls([handle], red, device, path, tie_draw=tie_draw)
 
     def _prepare(self, h, b: ShardBuffers):
         p = ShardBuffers.ptr
@@ -327,6 +370,14 @@ class ShardExchange:
                      else torch.distributed.get_world_size(self.reduce.group))
             for h, a in zip(self.handles, self.reduce.gather_tensors(recs)):
                 h.shard_exact_merge(a.data_ptr(), world)
+        if self.tie_draw is not None:
+            # the draw: each shard's MIN key per tied pod, the unsigned MIN over the shards, and
+            # every shard takes the winner's node
+            for h, b in zip(self.handles, self.bufs):
+                h.shard_draw_keys(mode, p(b.keys))
+            merge_draw_keys(self.reduce, self.bufs)
+            for h, b in zip(self.handles, self.bufs):
+                h.shard_draw_apply(p(b.keys))
 
     def run(self, mode: int) -> EvalResult:
         self.step(mode)
@@ -345,9 +396,14 @@ class LibExchange:
     exact-normalize records when K3 flags pods.  torch.distributed here only agrees on the
     record path and broadcasts the communicator id."""
 
-    def __init__(self, handle, device, shard=None, offset: int = 0, group=None):
+    def __init__(self, handle, device, shard=None, offset: int = 0, group=None, tie_draw=None):
+        """tie_draw: None, or (seed, pod_base): comm_run then ends in the draw (libyoda checks
+        that the ranks agree, in its first all-reduce)."""
         import torch.distributed as dist
         from .capi import comm_unique_id
+        if tie_draw is not None:
+            handle.set_tie_draw(int(tie_draw[0]), int(tie_draw[1]))
+        handle.shard_tie_draw(tie_draw is not None)
         if shard is not None:
             agree_on_path(Reducer(group=group), [handle], [shard], [offset], device)
         rank, world = dist.get_rank(group), dist.get_world_size(group)
