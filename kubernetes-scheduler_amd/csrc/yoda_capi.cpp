@@ -255,6 +255,10 @@ struct yoda_handle {
   long double sb_cards = 0.0L;  // its card and Allocate terms; sb_actual: the largest Actual
   uint64_t sb_actual = 0;
   uint64_t h_gmax[6] = {1, 1, 1, 1, 1, 1};  // the G maxima on the device (gtab_aux; N32)
+  // yoda_set_node_present: 1 per absent node (the records' kNodeAbsent), how many; an upload
+  // makes every node present.  The G maxima above are those of the PRESENT nodes.
+  std::vector<uint8_t> h_absent;
+  uint32_t n_absent = 0;
   // yoda_update_node_cards / yoda_snapshot_check: the changed nodes' packed rows (host), the
   // block summaries k_bsum_build writes for the self-check
   std::vector<uint32_t> cu_rows;
@@ -880,6 +884,15 @@ int pods_complete(yoda_t* h) {
   return YODA_OK;
 }
 
+// Mode B has no Filter and kernels of its own, none of which reads the presence bits
+// (yoda_set_node_present): while a node is absent its entry points refuse to run.
+int mode_b_absent(yoda_t* h, int mode) {
+  if (mode != YODA_MODE_DISKIO || h->n_absent == 0) return YODA_OK;
+  return fail(h, YODA_ERR_STATE,
+              "Mode B does not honour absent nodes (yoda_set_node_present): return every node "
+              "or upload the snapshot without them");
+}
+
 int check_ready(yoda_t* h, int mode) {
   if (!h) return YODA_ERR_INVALID_ARG;
   if (mode != YODA_MODE_SCV && mode != YODA_MODE_DISKIO)
@@ -888,6 +901,7 @@ int check_ready(yoda_t* h, int mode) {
   if (!h->has_pods) return fail(h, YODA_ERR_NO_PODS, "no pods uploaded");
   if (mode == YODA_MODE_DISKIO && !(h->nodes_diskio && h->pods_diskio))
     return fail(h, YODA_ERR_INVALID_ARG, "Mode B needs node cpu/disk_io and pod rio/rcpu");
+  if (int rc = mode_b_absent(h, mode)) return rc;
   HIP_TRY(h, hipSetDevice(h->device));
   return h->fast_run ? YODA_OK : pods_complete(h);
 }
@@ -2338,6 +2352,8 @@ int yoda_upload_nodes(yoda_t* h, const yoda_node_soa* nd, uint32_t node_offset, 
     h->h_card_number.assign(nd->card_number, nd->card_number + N);
     h->h_alloc.assign(N, 0);
     if (nd->alloc_memory) h->h_alloc.assign(nd->alloc_memory, nd->alloc_memory + N);
+    h->h_absent.assign(N, 0);  // every node of a fresh snapshot is present
+    h->n_absent = 0;
     h->nodes_diskio = diskio;
     h->all_one_model = rows.n_one_model == N;
     h->all_uni4 = rows.n_uni4 == N;
@@ -2998,8 +3014,10 @@ int yoda_score_rows_norm(yoda_t* h, int mode, uint32_t* bitmask_out, uint64_t n_
 }
 
 int yoda_eval(yoda_t* h, const yoda_pod_soa* pods, int mode, yoda_eval_out* out) {
-  int rc = yoda_upload_pods(h, pods);
+  if (!h) return YODA_ERR_INVALID_ARG;
+  int rc = mode_b_absent(h, mode);  // (before the pods are replaced)
   if (rc) return rc;
+  if ((rc = yoda_upload_pods(h, pods))) return rc;
   if ((rc = yoda_run(h, mode, 0))) return rc;
   return yoda_download(h, out);
 }
@@ -3064,8 +3082,9 @@ int yoda_shard_draw_keys(yoda_t* h, int mode, uint64_t* d_keys) {
   if (!d_keys) return fail(h, YODA_ERR_INVALID_ARG, "NULL key buffer");
   if (mode != YODA_MODE_SCV && mode != YODA_MODE_DISKIO)
     return fail(h, YODA_ERR_INVALID_ARG, "mode must be YODA_MODE_SCV or YODA_MODE_DISKIO");
-  int rc = shard_draw_ready(h, "yoda_shard_draw_keys");
+  int rc = mode_b_absent(h, mode);
   if (rc) return rc;
+  if ((rc = shard_draw_ready(h, "yoda_shard_draw_keys"))) return rc;
   if (mode != h->last_mode)
     return fail(h, YODA_ERR_STATE, "yoda_shard_draw_keys: the step ran in the other mode");
   try {
@@ -3602,6 +3621,7 @@ int yoda_greedy(yoda_t* h, const yoda_pod_soa* pods, int mode, uint32_t flags, i
   if (!h) return YODA_ERR_INVALID_ARG;
   if (!pods || !pick) return fail(h, YODA_ERR_INVALID_ARG, "NULL pods or pick");
   if (!h->has_nodes) return fail(h, YODA_ERR_NO_NODES, "no node snapshot uploaded");
+  if (int rc = mode_b_absent(h, mode)) return rc;
   try {
     HIP_TRY(h, hipSetDevice(h->device));
     GreedyScope scope(h);
@@ -4055,6 +4075,95 @@ uint64_t rec_field(const yoda_t* h, const unsigned char* r, int field, uint32_t 
   return u;
 }
 
+// Words of one packed node in h->cu_rows: its record, then on N32 its K1 summary, K2 summary,
+// model row and K1 tile (pack_node's outputs, node-major).
+uint32_t packed_row_words(const yoda_t* h) {
+  const int K = h->K;
+  if (h->path != Path::N32) return node_stride(K) / 4u;
+  return (n32_stride(K) + k1sum_stride(K) + k2sum_stride(K) + mix_stride(K) + x1_stride(K)) / 4u;
+}
+
+// Where pack_node writes node ti of h->cu_rows.
+void packed_row_out(yoda_t* h, uint32_t ti, uint32_t row_words, NodePackOut& out) {
+  const int K = h->K;
+  uint32_t* row = h->cu_rows.data() + (size_t)ti * row_words;
+  out = NodePackOut{};
+  out.rec = reinterpret_cast<unsigned char*>(row);
+  if (h->path == Path::N32) {
+    out.sum = row + n32_stride(K) / 4u;
+    out.sum2 = out.sum + k1sum_stride(K) / 4u;
+    out.mix = out.sum2 + k2sum_stride(K) / 4u;
+    out.x1 = out.mix + mix_stride(K) / 4u;
+  }
+}
+
+// The packed rows of the listed nodes (h->cu_rows, one row per entry of loc) onto the host
+// mirrors and the device: the records, the tiled tables and their block-grouped copies
+// (k_set_cards), then on N32 the block summaries of both orders again (k_bsum_build).  Ordered
+// on the handle's stream; pending run, phase-1 and top-k state is invalidated.  The one sparse
+// writer of whole rows: yoda_update_node_cards and yoda_set_node_present both end here.
+int apply_packed_rows(yoda_t* h, const std::vector<uint32_t>& loc, uint32_t row_words) {
+  const int K = h->K;
+  const bool n32 = h->path == Path::N32;
+  const size_t stride = n32 ? n32_stride(K) : node_stride(K);
+  const uint32_t cnt = (uint32_t)loc.size();
+  const uint32_t RW = (uint32_t)(stride / 4), SW = k1sum_stride(K) / 4u, S2W = k2sum_stride(K) / 4u;
+  const size_t o_rows = ((size_t)cnt * 4 + 15) / 16 * 16;
+  const size_t bytes = o_rows + (size_t)cnt * row_words * 4;
+  if (h->upd_pending) HIP_TRY(h, hipEventSynchronize(h->upd_event));
+  HIP_TRY(h, h->upd_stage.ensure(bytes));
+  HIP_TRY(h, h->upd_node.ensure(bytes));
+  unsigned char* st = static_cast<unsigned char*>(h->upd_stage.p);
+  std::memcpy(st, loc.data(), (size_t)cnt * 4);
+  std::memcpy(st + o_rows, h->cu_rows.data(), (size_t)cnt * row_words * 4);
+  for (uint32_t ti = 0; ti < cnt; ++ti) {
+    const uint32_t i = loc[ti];
+    const uint32_t* row = h->cu_rows.data() + (size_t)ti * row_words;
+    std::memcpy(h->host_records.data() + (size_t)i * stride, row, stride);
+    if (n32)
+      for (uint32_t w = 0; w < S2W; ++w)
+        h->host_k2sum[sum_index(i, w, k2sum_stride(K))] = row[RW + SW + w];
+  }
+  h->ran = false;
+  h->phase1_done = false;
+  h->topk_ready = false;
+  HIP_TRY(h, hipMemcpyAsync(h->upd_node.p, st, bytes, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipEventRecord(h->upd_event, h->stream));
+  h->upd_pending = true;
+  unsigned char* d = h->upd_node.as<unsigned char>();
+  HIP_TRY(h, launch_set_cards(h->nodes.as<unsigned char>(), (uint32_t)stride,
+                              reinterpret_cast<const uint32_t*>(d),
+                              reinterpret_cast<const uint32_t*>(d + o_rows), row_words, cnt, K,
+                              n32 ? h->k1sum.as<uint32_t>() : nullptr, h->k2sum.as<uint32_t>(),
+                              h->kmix.as<uint32_t>(), h->kx1.as<uint32_t>(), h->perm_copy(),
+                              h->stream));
+  if (!n32) return YODA_OK;
+  // the block summaries of both orders: the old ones are wrong now, not merely loose
+  return rebuild_block_sums(h);
+}
+
+// After apply_packed_rows on N32: the G maxima become g (those of the PRESENT nodes), the G table
+// of both orders is rebuilt from the new K2 summaries, the K2 block bounds are marked for a
+// rebuild before their next reader, and when a maximum moved its reciprocals are read back as
+// the upload reads them.
+int apply_gmax(yoda_t* h, const uint64_t g[6]) {
+  const bool g_moved = std::memcmp(g, h->h_gmax, sizeof(h->h_gmax)) != 0;
+  if (g_moved) {
+    std::memcpy(h->h_gmax, g, sizeof(h->h_gmax));
+    HIP_TRY(h, hipMemcpyAsync(h->gtab_aux.p, h->h_gmax, sizeof(h->h_gmax), hipMemcpyHostToDevice,
+                              h->stream));
+  }
+  int rc = relaunch_gtables(h);
+  if (rc) return rc;
+  h->kbub_dirty = true;
+  h->kbub_loose = false;
+  if (g_moved && h->g.tab && (rc = read_g_reciprocals(h))) return rc;
+  return YODA_OK;
+}
+
+// MaxValue field -> the CardField it is taken over.
+constexpr int kMaxToCard[6] = {kBandwidth, kClock, kCore, kFree, kPower, kTotal};
+
 }  // namespace
 
 int yoda_update_node_cards(yoda_t* h, uint32_t count, const uint32_t* nodes, uint32_t max_cards,
@@ -4072,9 +4181,7 @@ int yoda_update_node_cards(yoda_t* h, uint32_t count, const uint32_t* nodes, uin
     const int K = h->K;
     const bool n32 = h->path == Path::N32;
     const size_t stride = n32 ? n32_stride(K) : node_stride(K);
-    const uint32_t RW = (uint32_t)(stride / 4), SW = k1sum_stride(K) / 4u,
-                   S2W = k2sum_stride(K) / 4u, MW = mix_stride(K) / 4u, XW = x1_stride(K) / 4u;
-    const uint32_t row_words = RW + (n32 ? SW + S2W + MW + XW : 0u);
+    const uint32_t row_words = packed_row_words(h);
     // one entry per node, the last of a repeated id (the upd_slot pattern of yoda_set_node_state)
     if (h->upd_slot.size() != h->n_nodes) h->upd_slot.assign(h->n_nodes, ~0u);
     std::vector<uint32_t> loc, ent;
@@ -4106,6 +4213,8 @@ int yoda_update_node_cards(yoda_t* h, uint32_t count, const uint32_t* nodes, uin
       NodeHdrG hd;
       std::memcpy(&hd, r, sizeof(hd));
       const uint32_t nc = (uint32_t)__builtin_popcount(hd.real_mask);
+      // (an absent node takes its new values and stays absent: they count for G when it returns)
+      const bool absent = (hd.flags & kNodeAbsent) != 0u;
       if (nc > max_cards)
         return fail(h, YODA_ERR_INVALID_ARG, "max_cards below a listed node's card count");
       uint64_t fr[YODA_MAX_CARDS], tot[YODA_MAX_CARDS], ck[YODA_MAX_CARDS], bw[YODA_MAX_CARDS],
@@ -4137,6 +4246,7 @@ int yoda_update_node_cards(yoda_t* h, uint32_t count, const uint32_t* nodes, uin
         } else if (h->path == Path::F64 && f > kFastFieldMax) {
           return fail(h, YODA_ERR_RANGE, "FreeMemory leaves the fast path; re-upload the nodes");
         }
+        if (absent) continue;
         new_free_max = std::max(new_free_max, f);
         if (n32 && std::max<uint64_t>(rec_field(h, r, kFree, j), 1) == h->h_gmax[kMaxFree])
           held_max = true;
@@ -4154,6 +4264,7 @@ int yoda_update_node_cards(yoda_t* h, uint32_t count, const uint32_t* nodes, uin
       in.stat = s;
       in.zero_total = z;
       in.no_uniform = !(hd.flags & kNodeUniform4);  // (as uploaded: the card models are the same)
+      in.absent = absent;
       in.free_memory = fr;
       in.total_memory = tot;
       in.clock = ck;
@@ -4163,83 +4274,40 @@ int yoda_update_node_cards(yoda_t* h, uint32_t count, const uint32_t* nodes, uin
       in.healthy = hl;
       in.fcode = fc;
       in.tcode = tc;
-      uint32_t* row = h->cu_rows.data() + (size_t)ti * row_words;
       NodePackOut out;
-      out.rec = reinterpret_cast<unsigned char*>(row);
-      if (n32) {
-        out.sum = row + RW;
-        out.sum2 = out.sum + SW;
-        out.mix = out.sum2 + S2W;
-        out.x1 = out.mix + MW;
-      }
+      packed_row_out(h, ti, row_words, out);
       pack_node(h->path, K, in, out);
     }
-    // ---- the list passed: stage the rows, then the host copies, then the device ----
-    const size_t o_rows = ((size_t)cnt * 4 + 15) / 16 * 16;
-    const size_t bytes = o_rows + (size_t)cnt * row_words * 4;
-    if (h->upd_pending) HIP_TRY(h, hipEventSynchronize(h->upd_event));
-    HIP_TRY(h, h->upd_stage.ensure(bytes));
-    HIP_TRY(h, h->upd_node.ensure(bytes));
-    unsigned char* st = static_cast<unsigned char*>(h->upd_stage.p);
-    std::memcpy(st, loc.data(), (size_t)cnt * 4);
-    std::memcpy(st + o_rows, h->cu_rows.data(), (size_t)cnt * row_words * 4);
-    for (uint32_t ti = 0; ti < cnt; ++ti) {
-      const uint32_t i = loc[ti], t = ent[ti];
-      const uint32_t* row = h->cu_rows.data() + (size_t)ti * row_words;
-      std::memcpy(h->host_records.data() + (size_t)i * stride, row, stride);
-      if (n32)
-        for (uint32_t w = 0; w < S2W; ++w)
-          h->host_k2sum[sum_index(i, w, k2sum_stride(K))] = row[RW + SW + w];
-      h->h_free_sum[i] = free_memory_sum[t];
-    }
-    h->ran = false;
-    h->phase1_done = false;
-    h->topk_ready = false;
+    // ---- the list passed: the rows onto the mirrors and the device, then the host copies ----
+    int rc = apply_packed_rows(h, loc, row_words);
+    if (rc) return rc;
+    for (uint32_t ti = 0; ti < cnt; ++ti) h->h_free_sum[loc[ti]] = free_memory_sum[ent[ti]];
     if (new_actual > h->sb_actual) {  // the score bound may only grow
       h->sb_actual = new_actual;
       const long double b = h->sb_cards + (long double)new_actual;
       h->score_bound =
           std::max<uint64_t>(h->score_bound, b < 9.0e18L ? (uint64_t)b + 1u : ~(uint64_t)0);
     }
-    HIP_TRY(h, hipMemcpyAsync(h->upd_node.p, st, bytes, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipEventRecord(h->upd_event, h->stream));
-    h->upd_pending = true;
-    unsigned char* d = h->upd_node.as<unsigned char>();
-    HIP_TRY(h, launch_set_cards(h->nodes.as<unsigned char>(), (uint32_t)stride,
-                                reinterpret_cast<const uint32_t*>(d),
-                                reinterpret_cast<const uint32_t*>(d + o_rows), row_words, cnt, K,
-                                n32 ? h->k1sum.as<uint32_t>() : nullptr, h->k2sum.as<uint32_t>(),
-                                h->kmix.as<uint32_t>(), h->kx1.as<uint32_t>(), h->perm_copy(),
-                                h->stream));
     if (!n32) return YODA_OK;
-    // the block summaries of both orders: the old ones are wrong now, not merely loose
-    int rc = rebuild_block_sums(h);
-    if (rc) return rc;
-    // The G maximum of FreeMemory, exact: it rises with a larger free; when a changed node held
-    // it, recomputed from the host K2 summaries (word kS2Fs + 0: each node's largest free).
+    // The G maximum of FreeMemory over the present nodes, exact: it rises with a larger free; when
+    // a changed node held it, recomputed from the host K2 summaries (word kS2Fs + 0: each node's
+    // largest free).
     uint64_t gfree = std::max(h->h_gmax[kMaxFree], std::max<uint64_t>(new_free_max, 1));
     if (held_max) {
       gfree = 1;
       const uint32_t S2 = k2sum_stride(K);
       for (uint32_t n = 0; n < h->n_nodes; ++n) {
+        if (h->h_absent[n]) continue;
         const uint32_t c = h->host_k2sum[sum_index(n, kS2Fs, S2)];
         uint64_t v = c;
         if (h->mem_ranks) v = c >= 2u && c - 2u < h->h_frees.size() ? h->h_frees[c - 2u] : 0;
         gfree = std::max(gfree, v);
       }
     }
-    const bool g_moved = gfree != h->h_gmax[kMaxFree];
-    if (g_moved) {
-      h->h_gmax[kMaxFree] = gfree;
-      HIP_TRY(h, hipMemcpyAsync(h->gtab_aux.p, h->h_gmax, sizeof(h->h_gmax),
-                                hipMemcpyHostToDevice, h->stream));
-    }
-    if ((rc = relaunch_gtables(h))) return rc;
-    h->kbub_dirty = true;  // the K2 block bounds: rebuilt before their next reader
-    h->kbub_loose = false;
-    // the reciprocals of the new maxima, as the upload reads them
-    if (g_moved && h->g.tab && (rc = read_g_reciprocals(h))) return rc;
-    return YODA_OK;
+    uint64_t g[6];
+    std::memcpy(g, h->h_gmax, sizeof(g));
+    g[kMaxFree] = gfree;
+    return apply_gmax(h, g);
   } catch (const std::bad_alloc&) {
     h->upd_slot.clear();
     return fail(h, YODA_ERR_INVALID_ARG, "host allocation failed");
@@ -4247,6 +4315,149 @@ int yoda_update_node_cards(yoda_t* h, uint32_t count, const uint32_t* nodes, uin
     h->upd_slot.clear();
     return fail(h, YODA_ERR_INVALID_ARG, "unexpected exception");
   }
+}
+
+int yoda_set_node_present(yoda_t* h, uint32_t count, const uint32_t* nodes,
+                          const uint8_t* present) {
+  if (!h) return YODA_ERR_INVALID_ARG;
+  if (!h->has_nodes) return fail(h, YODA_ERR_NO_NODES, "no node snapshot uploaded");
+  if (count == 0) return YODA_OK;
+  if (!nodes || !present) return fail(h, YODA_ERR_INVALID_ARG, "NULL node presence array");
+  try {
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int K = h->K;
+    const bool n32 = h->path == Path::N32;
+    const size_t stride = n32 ? n32_stride(K) : node_stride(K);
+    const uint32_t row_words = packed_row_words(h);
+    // one entry per node, the last of a repeated id (the upd_slot pattern of yoda_set_node_state)
+    if (h->upd_slot.size() != h->n_nodes) h->upd_slot.assign(h->n_nodes, ~0u);
+    if (h->h_absent.size() != h->n_nodes) h->h_absent.assign(h->n_nodes, 0);
+    std::vector<uint32_t> seen, ent;
+    for (uint32_t t = 0; t < count; ++t) {
+      if (nodes[t] < h->node_offset || nodes[t] - h->node_offset >= h->n_nodes) continue;
+      const uint32_t i = nodes[t] - h->node_offset;
+      uint32_t& slot = h->upd_slot[i];
+      if (slot == ~0u) {
+        slot = (uint32_t)seen.size();
+        seen.push_back(i);
+        ent.push_back(t);
+      } else {
+        ent[slot] = t;
+      }
+    }
+    for (uint32_t i : seen) h->upd_slot[i] = ~0u;
+    // the pending outcomes are the old node set's, whether or not a listed node changes sides
+    h->ran = false;
+    h->phase1_done = false;
+    h->topk_ready = false;
+    h->draw_stage = 0;
+    // the nodes whose presence changes, their rows repacked from the host records with the new bit
+    std::vector<uint32_t> loc;
+    std::vector<uint8_t> gone;
+    for (size_t k = 0; k < seen.size(); ++k) {
+      const uint8_t a = present[ent[k]] ? 0 : 1;
+      if (a == h->h_absent[seen[k]]) continue;
+      loc.push_back(seen[k]);
+      gone.push_back(a);
+    }
+    const uint32_t cnt = (uint32_t)loc.size();
+    if (cnt == 0) return YODA_OK;
+    h->cu_rows.assign((size_t)cnt * row_words, 0u);
+    uint64_t g[6];
+    std::memcpy(g, h->h_gmax, sizeof(g));
+    uint32_t lost = 0;  // bit f: a node that leaves holds the G maximum of MaxValue field f
+    for (uint32_t ti = 0; ti < cnt; ++ti) {
+      const uint32_t i = loc[ti];
+      const unsigned char* r = h->host_records.data() + (size_t)i * stride;
+      NodeHdrG hd;
+      std::memcpy(&hd, r, sizeof(hd));
+      const uint32_t nc = (uint32_t)__builtin_popcount(hd.real_mask);
+      uint64_t v[kCardFields][YODA_MAX_CARDS];  // CardField order
+      uint8_t hl[YODA_MAX_CARDS];
+      uint32_t fc[YODA_MAX_CARDS] = {}, tc[YODA_MAX_CARDS] = {};
+      for (uint32_t j = 0; j < nc; ++j) {
+        for (int f = 0; f < kCardFields; ++f) v[f][j] = rec_field(h, r, f, j);
+        hl[j] = (hd.healthy_mask >> j) & 1u;
+        if (n32) {  // the memory codes as the record holds them (values, or ranks)
+          std::memcpy(&fc[j], r + n32_u32_off(kFree, K) + 4u * j, 4);
+          std::memcpy(&tc[j], r + n32_u32_off(kTotal, K) + 4u * j, 4);
+        }
+      }
+      if (n32)
+        for (int f = 0; f < 6; ++f) {
+          uint64_t m = 1;
+          for (uint32_t j = 0; j < nc; ++j) m = std::max(m, v[kMaxToCard[f]][j]);
+          if (gone[ti])
+            lost |= m == h->h_gmax[f] ? 1u << f : 0u;
+          else
+            g[f] = std::max(g[f], m);
+        }
+      NodePackIn in;
+      in.cnt = nc;
+      in.card_number = hd.card_number;
+      if (h->generic) {
+        in.stat = hd.static_score;
+      } else {
+        double sd;
+        std::memcpy(&sd, &hd.static_score, 8);
+        in.stat = (uint64_t)sd;
+      }
+      in.zero_total = hd.zero_total != 0u;
+      in.no_uniform = !(hd.flags & kNodeUniform4);  // (as uploaded: the card models are the same)
+      in.absent = gone[ti] != 0;
+      in.free_memory = v[kFree];
+      in.total_memory = v[kTotal];
+      in.clock = v[kClock];
+      in.bandwidth = v[kBandwidth];
+      in.core = v[kCore];
+      in.power = v[kPower];
+      in.healthy = hl;
+      in.fcode = fc;
+      in.tcode = tc;
+      NodePackOut out;
+      packed_row_out(h, ti, row_words, out);
+      pack_node(h->path, K, in, out);
+    }
+    int rc = apply_packed_rows(h, loc, row_words);
+    if (rc) return rc;
+    for (uint32_t ti = 0; ti < cnt; ++ti) {
+      h->h_absent[loc[ti]] = gone[ti];
+      if (gone[ti]) ++h->n_absent; else --h->n_absent;
+    }
+    if (!n32) return YODA_OK;
+    // The G maxima are those of the present nodes (a wave whose maxima are G's takes the G-table
+    // K2; with a stale G none would).  A returning node can only raise them (above); a field
+    // whose holder left is searched over the present nodes, stopping at the first that still
+    // reaches the old maximum (one GPU model in the fleet: the first node).
+    for (int f = 0; f < 6; ++f) {
+      if (!((lost >> f) & 1u)) continue;
+      const uint64_t old = h->h_gmax[f];
+      uint64_t m = 1;
+      for (uint32_t n = 0; n < h->n_nodes && m < old; ++n) {
+        if (h->h_absent[n]) continue;
+        const unsigned char* r = h->host_records.data() + (size_t)n * stride;
+        NodeHdrG hd;
+        std::memcpy(&hd, r, sizeof(hd));
+        const uint32_t nc = (uint32_t)__builtin_popcount(hd.real_mask);
+        for (uint32_t j = 0; j < nc; ++j) m = std::max(m, rec_field(h, r, kMaxToCard[f], j));
+      }
+      // (m < old: the scan was whole and m is the maximum; else g[f] holds the returning nodes')
+      g[f] = m < old ? m : std::max(g[f], m);
+    }
+    return apply_gmax(h, g);
+  } catch (const std::bad_alloc&) {
+    h->upd_slot.clear();
+    return fail(h, YODA_ERR_INVALID_ARG, "host allocation failed");
+  } catch (...) {
+    h->upd_slot.clear();
+    return fail(h, YODA_ERR_INVALID_ARG, "unexpected exception");
+  }
+}
+
+int yoda_nodes_absent(const yoda_t* h, uint32_t* n_absent) {
+  if (!h || !n_absent) return YODA_ERR_INVALID_ARG;
+  *n_absent = h->has_nodes ? h->n_absent : 0u;
+  return YODA_OK;
 }
 
 int yoda_snapshot_check(yoda_t* h, uint64_t* digest, uint32_t* mismatch) {
@@ -5589,6 +5800,9 @@ static int comm_step(yoda_t* const* hs, int n, int world, int mode, bool local, 
   yoda_t* h0 = hs[0];
   const uint32_t P = h0->n_pods;
   const size_t n1 = 6 * (size_t)P + kAgreeWords;  // maxima | agreement words
+  for (int i = 0; i < n; ++i)  // (before any shard's run is prepared)
+    if (hs[i]->n_absent && mode == YODA_MODE_DISKIO)
+      return fail(h0, mode_b_absent(hs[i], mode), hs[i]->last_error);
   for (int i = 0; i < n; ++i) {
     yoda_t* h = hs[i];
     if (h->n_pods != P) return fail(h0, YODA_ERR_INVALID_ARG, "shards hold different batches");
@@ -5996,6 +6210,9 @@ static int comm_greedy(yoda_t* const* hs, int n, int world, bool local, const yo
   const uint32_t P = pods->n_pods;
   for (int i = 0; i < n; ++i)
     if (!hs[i]->has_nodes) return fail(h0, YODA_ERR_NO_NODES, "no node snapshot uploaded");
+  for (int i = 0; i < n; ++i)
+    if (hs[i]->n_absent && mode == YODA_MODE_DISKIO)
+      return fail(h0, mode_b_absent(hs[i], mode), hs[i]->last_error);
   if (P == 0) return YODA_OK;
   int rc;
   PodGather win;

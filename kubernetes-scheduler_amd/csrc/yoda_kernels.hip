@@ -132,7 +132,9 @@ __device__ __forceinline__ bool k1_node(const unsigned char* rec, typename Rec<P
     for (int j = 0; j < K; ++j)
       cc += (uint32_t)(ck.v[j] == c) & ((hd.healthy_mask >> j) & 1u);  // filter.go:56-58
   }
-  const bool feas = (number <= hd.card_number) & (cm >= need_mem) & (cc >= need_clk);
+  // (an absent node, yoda_set_node_present, is in no Filter: nothing below folds it)
+  const bool feas = (number <= hd.card_number) & (cm >= need_mem) & (cc >= need_clk) &
+                    ((hd.flags & kNodeAbsent) == 0u);
   if (feas && uniform) {
     ++nf;
     nz += hd.zero_total;
@@ -434,7 +436,8 @@ __global__ __launch_bounds__(kBlock) void k1_witness(
       cc += (uint32_t)(ck.v[j] == c) & hj;  // CardFitsClock (filter.go:56-58)
     }
     const bool feas =
-        live && (number <= hd.card_number) & (cm >= need_mem) & (cc >= need_clk);
+        live && (number <= hd.card_number) & (cm >= need_mem) & (cc >= need_clk) &
+                    ((hd.flags & kNodeAbsent) == 0u);  // (absent: no count, no witness)
     bool uniform = false;  // one GPU model (scalar flag: a wave-uniform branch)
     if constexpr (PATH == Path::N32) uniform = (hd.flags & kNodeUniform4) != 0u;
     if (feas && uniform) {
@@ -690,6 +693,9 @@ __device__ __forceinline__ K1BlockClass k1_block_class(const uint32_t* B, bool b
   const bool noq = (ckmax < w.c_min) | (mrf_max <= w.m_min);
   // (other blocks: no clock-only noq -- the seed's level bound assumes every card passes)
   ball &= (r.allq | (one ? noq : mrf_max <= w.m_min)) & !bnone & (one | mix_all);
+  // a block with an absent node is never ALL: nreal / nzt, mx / wc / wl and the kbub level the
+  // seed reads are taken over every real node; NONE needs no such care
+  ball &= (fl & kBsAbsent) == 0u;
   r.none = bnone & bv & (r.nreal > 0u);
   r.all = ball & bv & (r.nreal > 0u);
   return r;
@@ -967,7 +973,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WIT ? 4 
     const bool clk_all = !any_pc || (c_uni && hc >= nc_max);
     const bool clk_none = all_pc && c_uni && hc < nc_min;
     const bool feas_all = (num_max <= cn) && mem_all && clk_all;
-    const bool feas_none = num_none || mem_none || clk_none;
+    // (an absent node, kSumAbsent, is NONE: never ALL, never PART -- the per-pod passes below
+    // see present nodes only)
+    const bool feas_none = num_none || mem_none || clk_none || (meta & kSumAbsent) != 0u;
     // The node's CollectMaxValues contribution (collection.go:46: cards with free >= m and
     // clock >= c, no health check) is the same for every pod of the wave when the SMALLEST
     // qualifying set (the wave's largest m and c) and the LARGEST (its smallest m and c) give
@@ -3906,7 +3914,8 @@ __global__ __launch_bounds__(kBlock) void k_one_filter(const unsigned char* __re
         cm += (uint32_t)(fr.v[j] >= m) & hj;  // CardFitsMemory (filter.go:52-54)
         cc += (uint32_t)(ck.v[j] == c) & hj;  // CardFitsClock (filter.go:56-58)
       }
-      f = (pod.number <= hd.card_number) & (cm >= pod.need_mem) & (cc >= pod.need_clk);
+      f = (pod.number <= hd.card_number) & (cm >= pod.need_mem) & (cc >= pod.need_clk) &
+          ((hd.flags & kNodeAbsent) == 0u);
       if (f) {
         ++nf;
         nz += hd.zero_total;
@@ -5474,6 +5483,7 @@ __global__ __launch_bounds__(kWave) void k_bsum_build(const uint32_t* __restrict
   const uint32_t not4 = wave_max_u32v((v && !(meta & kSumUni4)) ? 1u : 0u);
   const uint32_t nott = wave_max_u32v((v && !(meta & kSumUniTotal)) ? 1u : 0u);
   const uint32_t nzt = wave_sum_u32((v && (meta & kSumZeroTotal)) ? 1u : 0u);
+  const uint32_t nabs = wave_max_u32v((v && (meta & kSumAbsent)) ? 1u : 0u);
   const uint32_t ckmin = wave_min_u32v(v ? c0 : ~0u), ckmax = wave_max_u32v(v ? c1 : 0u);
   const uint32_t hmin = wave_min_u32v(v ? c2 : ~0u), hmax = wave_max_u32v(v ? c3 : 0u);
   const uint32_t nhmin = wave_min_u32v(v ? nh : ~0u), nhmax = wave_max_u32v(v ? nh : 0u);
@@ -5491,6 +5501,7 @@ __global__ __launch_bounds__(kWave) void k_bsum_build(const uint32_t* __restrict
     uint32_t fl = kBsOneModel | kBsUni4;
     if (not4) fl &= ~(kBsUni4 | kBsOneModel);
     if (nott) fl &= ~kBsOneModel;
+    if (nabs) fl |= kBsAbsent;  // (the other words stay bounds over EVERY real node)
     o[kBsCnMin] = (uint32_t)min(cmin, (uint64_t)0xffffffffu);
     o[kBsCnMax] = (uint32_t)min(cmax, (uint64_t)0xffffffffu);
     o[kBsFlags] = fl;

@@ -44,6 +44,10 @@ constexpr uint32_t kNodeUniform4 = 1u;
 // ... and also the same TotalMemory on every real card: the total-memory maximum and
 // quotient are per node too.
 constexpr uint32_t kNodeUniformTotal = 2u;
+// The node is ABSENT (yoda_set_node_present): it exists in no Filter, no PreScore maximum and no
+// pick until it returns; its other fields stay current.  No card value can say this -- a pod
+// labelled scv/number "0" passes a node of any values (filter.go:11-33) -- so it has a bit.
+constexpr uint32_t kNodeAbsent = 4u;
 static_assert(sizeof(NodeHdrF) == 32, "NodeHdrF layout");
 
 // Generic (exact uint64) path: same shape with uint64 card fields.
@@ -80,7 +84,7 @@ __host__ __device__ constexpr uint32_t n32_f64_off(int g, int k) {
 // k1sum_stride(K) bytes, words:
 //   cn_lo, cn_hi      Status.CardNumber
 //   clock             the clock of every real card (valid when kSumUni4)
-//   meta              kSumUni4 | kSumUniTotal | kSumZeroTotal | (healthy count << 8)
+//   meta              kSumUni4 | kSumUniTotal | kSumZeroTotal | kSumAbsent | (healthy count << 8)
 //   mrf1              1 + max FreeMemory over the real cards (0: empty CardList)
 //   total, bw, core, power   the per-node values (valid under kSumUni4 / kSumUniTotal)
 //   hfs[K]            1 + FreeMemory of the HEALTHY cards, sorted descending, 0-padded:
@@ -90,6 +94,7 @@ enum K1SumWord {
   kSumBw = 6, kSumCore = 7, kSumPower = 8, kSumHfs = 12
 };
 constexpr uint32_t kSumUni4 = 1u, kSumUniTotal = 2u, kSumZeroTotal = 4u;
+constexpr uint32_t kSumAbsent = 8u;  // the record's kNodeAbsent (K1 summary only)
 __host__ __device__ constexpr uint32_t k1sum_stride(int k) {
   return (48u + 4u * (uint32_t)k + 15u) & ~15u;
 }
@@ -116,7 +121,10 @@ __host__ __device__ constexpr uint32_t k2sum_stride(int k) { return 32u + 8u * (
 //                       k_set_static keeps them valid bounds with atomics, k_bsum_cn makes
 //                       them tight again
 //   flags    kBsOneModel: every node one GPU model with one TotalMemory (kSumUni4|UniTotal);
-//            kBsUni4: every node kSumUni4
+//            kBsUni4: every node kSumUni4;
+//            kBsAbsent: some real node of the block is absent (kSumAbsent): the block is never
+//            ALL -- every other word here is still taken over EVERY real node, so the NONE
+//            tests (bounds over a superset) stay sufficient
 //   ck_min, ck_max      the nodes' clock (one-model nodes) / card clocks (others)
 //   hck_min, hck_max    the clocks of the HEALTHY cards (~0 / 0: none)
 //   nh_min, nh_max      healthy cards per node
@@ -139,7 +147,7 @@ enum BlockSumWord {
   kBsHckMax = 6, kBsNhMin = 7, kBsNhMax = 8, kBsMrfMin = 9, kBsMrfMax = 10, kBsNReal = 11,
   kBsNzt = 12, kBsMx = 13, kBsWc = 19, kBsWl = 25, kBsSat = 31, kBsHc = 32, kBsT = 36
 };
-constexpr uint32_t kBsOneModel = 1u, kBsUni4 = 2u, kBsHcTab = 4u;
+constexpr uint32_t kBsOneModel = 1u, kBsUni4 = 2u, kBsHcTab = 4u, kBsAbsent = 8u;
 __host__ __device__ constexpr uint32_t bsum_stride(int k) { return 4u * (kBsT + 2u * (uint32_t)k); }
 
 // K2 block bounds (N32 path; waves whose reciprocals are the G table's): per 64-node block of a

@@ -1,7 +1,8 @@
 // yoda_node_pack.h — one node of a snapshot packed into the device layout of yoda_layout.h:
 // its record, its K1 and K2 summary rows, its per-card model row and its K1 mixed tile.  Host
 // code without a HIP runtime call: yoda_upload_nodes packs every node with it,
-// yoda_update_node_cards the nodes whose card metrics changed, and tools/check_node_pack.cpp
+// yoda_update_node_cards the nodes whose card metrics changed, yoda_set_node_present the nodes
+// that left or returned, and tools/check_node_pack.cpp
 // runs it under AddressSanitizer.  One packer, so the sparse path cannot drift from the upload;
 // what is derived from these rows (block summaries, G table) has one builder too, on the device
 // (k_bsum_build, k_gtable), which both callers run.
@@ -24,6 +25,7 @@ struct NodePackIn {
   uint64_t stat = 0;        // static score (CalculateAllocateScore + CalculateActualScore)
   bool zero_total = false;  // TotalMemorySum == 0
   bool no_uniform = false;  // YODA_UPLOAD_NO_UNIFORM: never mark the node one-model
+  bool absent = false;      // yoda_set_node_present: kNodeAbsent / kSumAbsent
   const uint64_t* free_memory = nullptr;
   const uint64_t* total_memory = nullptr;
   const uint64_t* clock = nullptr;
@@ -48,7 +50,7 @@ struct NodePackOut {
   bool zeroed = false;
 };
 
-// Packs the node; returns its record flags (kNodeUniform4 | kNodeUniformTotal).  Every row is
+// Packs the node; returns its record flags (kNodeUniform4 | kNodeUniformTotal | kNodeAbsent).  Every row is
 // written WHOLE -- cleared first unless out.zeroed -- so that packing over an older row of the
 // same node leaves what a fresh pack leaves (hfs past the healthy count, the ch entries, the
 // change bits).
@@ -73,6 +75,7 @@ inline uint32_t pack_node(Path path, int K, const NodePackIn& in, const NodePack
   for (uint32_t j = 1; j < cnt; ++j) uni_total = uni_total && in.total_memory[j] == in.total_memory[0];
   hd.flags = 0u;
   if (uni && !in.no_uniform) hd.flags = kNodeUniform4 | (uni_total ? kNodeUniformTotal : 0u);
+  if (in.absent) hd.flags |= kNodeAbsent;
   if (path == Path::U64) {
     hd.static_score = in.stat;
   } else {
@@ -87,7 +90,8 @@ inline uint32_t pack_node(Path path, int K, const NodePackIn& in, const NodePack
     s[kSumCnHi] = (uint32_t)(hd.card_number >> 32);
     s[kSumMeta] = ((hd.flags & kNodeUniform4) ? kSumUni4 : 0u) |
                   ((hd.flags & kNodeUniformTotal) ? kSumUniTotal : 0u) |
-                  (in.zero_total ? kSumZeroTotal : 0u) | ((uint32_t)__builtin_popcount(hm) << 8);
+                  (in.zero_total ? kSumZeroTotal : 0u) | (in.absent ? kSumAbsent : 0u) |
+                  ((uint32_t)__builtin_popcount(hm) << 8);
     if (cnt > 0) {  // the model values of card 0 (all cards under kSumUni4)
       s[kSumClock] = (uint32_t)in.clock[0];
       s[kSumTotal] = in.tcode[0];

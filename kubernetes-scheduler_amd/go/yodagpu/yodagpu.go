@@ -332,6 +332,26 @@ func (g *Handle) UpdateCards(idx []uint32, maxCards int, free []uint64, healthy 
 	return check(g.h, rc, "yoda_update_node_cards")
 }
 
+// SetNodePresent takes a few nodes out of the uploaded snapshot (present[i] == 0) or back in
+// without re-uploading it (yoda_set_node_present): a node that left the node set -- drained,
+// NotReady, its SCV deleted -- or returned.  idx are snapshot positions; the other nodes keep
+// theirs.  While a node is absent Mode A answers as a snapshot without it would; Mode B returns
+// an error that wraps YODA_ERR_STATE until every node is back.  Not a per-cycle mask for other
+// plugins' Filter results: a cordoned node's SCV still feeds CollectMaxValues, an absent one's
+// does not.
+func (g *Handle) SetNodePresent(idx []uint32, present []uint8) error {
+	if len(idx) != len(present) {
+		return errors.New("yodagpu: SetNodePresent arrays differ in length")
+	}
+	if len(idx) == 0 {
+		return nil
+	}
+	// plain-number Go slices passed directly as arguments: allowed by the cgo rules
+	rc := C.yoda_set_node_present(g.h, C.uint32_t(len(idx)), (*C.uint32_t)(unsafe.Pointer(&idx[0])),
+		(*C.uint8_t)(unsafe.Pointer(&present[0])))
+	return check(g.h, rc, "yoda_set_node_present")
+}
+
 // packPods parses the scv/* labels and the diskIO annotation with the reference's own
 // helpers (filter.go:60-74, sort.go:12-18, algorithm.go:103-104) into the C-side
 // yoda_pod_soa arrays.

@@ -83,6 +83,8 @@ _SIGS = {
     "yoda_topk_k_capacity": ([], C.c_int),
     "yoda_set_node_state": ([_vp, _u32, _vp, _vp, _vp], C.c_int),
     "yoda_update_node_cards": ([_vp, _u32, _vp, _u32, _vp, _vp, _vp], C.c_int),
+    "yoda_set_node_present": ([_vp, _u32, _vp, _vp], C.c_int),
+    "yoda_nodes_absent": ([_vp, C.POINTER(C.c_uint32)], C.c_int),
     "yoda_snapshot_check": ([_vp, _vp, _vp], C.c_int),
     "yoda_shard_topk": ([_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp], C.c_int),
     "yoda_shard_topk_depth": ([_vp], C.c_int),
@@ -486,6 +488,27 @@ class Yoda:
         self._check(lib().yoda_update_node_cards(self._h, n.size, _np_ptr(n), k, _np_ptr(f),
                                                  _np_ptr(hl), _np_ptr(s)),
                     "yoda_update_node_cards")
+
+    def set_node_present(self, ids, present):
+        """Take the listed GLOBAL node ids (others ignored) out of the uploaded snapshot
+        (present 0) or back in (non-zero), no re-upload (yoda_set_node_present): while absent a
+        node is in no Filter, no PreScore maximum and no pick of Mode A; Mode B raises YodaError
+        (YODA_ERR_STATE) until every node is back.  `present`: one flag per id, or a scalar for
+        all of them; a repeated id keeps its last flag."""
+        n = np.ascontiguousarray(ids, np.uint32).ravel()
+        f = np.ascontiguousarray(np.broadcast_to(np.asarray(present, np.uint8), n.shape)
+                                 if np.ndim(present) == 0 else present, np.uint8).ravel()
+        if f.size != n.size:
+            raise ValueError("set_node_present: ids and present differ in length")
+        self._check(lib().yoda_set_node_present(self._h, n.size, _np_ptr(n), _np_ptr(f)),
+                    "yoda_set_node_present")
+
+    @property
+    def nodes_absent(self) -> int:
+        """Nodes of this handle's snapshot that are absent now (yoda_nodes_absent; host only)."""
+        k = C.c_uint32(0)
+        self._check(lib().yoda_nodes_absent(self._h, C.byref(k)), "yoda_nodes_absent")
+        return int(k.value)
 
     def snapshot_check(self):
         """(digest [8] u64, mismatch [4] u32) of yoda_snapshot_check (diagnostic; synchronizes)."""

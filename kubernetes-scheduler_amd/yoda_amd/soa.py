@@ -151,6 +151,12 @@ class NodeSoA:
         return NodeSoA(**{f: np.ascontiguousarray(getattr(self, f)[lo:hi])
                           for f in self.__dataclass_fields__})
 
+    def take(self, idx) -> "NodeSoA":
+        """The nodes `idx` (positions or a boolean mask), in that order: the twin of PodSoA.take.
+        The survivors of a compaction get new positions; map picks back through `idx`."""
+        return NodeSoA(**{f: np.ascontiguousarray(getattr(self, f)[idx])
+                          for f in self.__dataclass_fields__})
+
     def c(self) -> CNodeSoA:
         return CNodeSoA(
             n_nodes=self.n_nodes,
