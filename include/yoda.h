@@ -511,7 +511,7 @@ int yoda_update_node_cards(yoda_t* h, uint32_t count, const uint32_t* nodes, uin
  * untouched.
  *   This is NOT a per-cycle candidate mask for other plugins' Filter results (cordon, taints,
  * nodeSelector): in the reference such a node's SCV still feeds CollectMaxValues, an absent
- * node's does not.
+ * node's does not.  That mask is yoda_set_candidates (below).
  *   Cost: the listed nodes' rows and every table derived from them, as yoda_update_node_cards; a
  * 64-node block with an absent node is classified node by node instead of as a whole.  Measured
  * at 100k pods x 100k nodes (profiles/nodepresent/timing.txt): the call plus the first run after
@@ -523,6 +523,60 @@ int yoda_set_node_present(yoda_t* h, uint32_t count, const uint32_t* nodes,
                           const uint8_t* present);
 /* Diagnostic (host only): how many nodes of this handle's snapshot are absent. */
 int yoda_nodes_absent(const yoda_t* h, uint32_t* n_absent);
+/* ---- Candidate classes: other plugins' Filter results in the batch path ----
+ * In kube-scheduler a node is scored for a pod only if EVERY Filter plugin passed it (cordon,
+ * taints, nodeSelector / affinity, resource fit), while CollectMaxValues
+ * (pkg/yoda/collection/collection.go:39-52) walks every SCV under Yoda's own predicates alone.
+ * With cand(p, n) the other plugins' verdict: the PreScore maxima are unchanged (over every
+ * present node that passes Yoda's Filter, candidate or not); the feasible set is
+ * F'(p) = {n : Yoda's Filter passes and cand(p, n)}; a node outside F' has feasibility bit 0 and
+ * raw and normalized row scores of -1 and is in no tie set and no draw; a node of F' scores what
+ * it scores without candidates; n_feasible, the single-feasible-node rule, UNSCHEDULABLE,
+ * DIV_ZERO (a node of F' with TotalMemorySum == 0 and |F'| >= 2), NormalizeScore's highest and
+ * lowest, n_ties, top_score, the lowest-node pick and the draw of yoda_set_tie_draw all follow F'.
+ * An absent node (yoda_set_node_present) stays out of everything whatever its word says.
+ *   Pods with the same scheduling constraints share one node set: each node carries a 64-bit
+ * word, bit c set when it is a candidate for class c; each pod carries a class byte.  Cordoning
+ * a node is one yoda_update_candidates entry with word 0.
+ *   Honoured by yoda_eval, yoda_run (with and without YODA_RUN_BITMASK), yoda_download,
+ * yoda_download_bitmask, yoda_score_rows and yoda_score_rows_norm in Mode A.  While candidates
+ * are on, Mode B, yoda_greedy*, yoda_shard_* and yoda_comm_* return YODA_ERR_STATE and do nothing
+ * else -- every shard call that starts, advances or reads a step, the exact-normalize, merge,
+ * witness and draw calls included; only the settings (yoda_shard_tie_draw,
+ * yoda_shard_exchange_order) and the host queries (yoda_shard_topk_depth,
+ * yoda_shard_overflow_count) answer.  A change of the candidate state also drops a sharded
+ * step's pending exact merge.  With candidates off they run as they always did.
+ *   The calls are ordered on the handle's stream and invalidate pending run, phase-1 and top-k
+ * state, as yoda_set_node_present does; each validates its arguments before it writes anything.
+ *   Cost: one pass over K1's masks after the Filter kernel (k_cand_narrow); the K2 pruning seeds
+ * are off while candidates are on.  Measured at 100k pods x 100k nodes, config 3
+ * (profiles/candidates/timing.txt): the step 0.38 ms with candidates never set (the parent's),
+ * 0.42 ms with all-ones words and one class (0.025 ms of lost seeds, 0.016 ms of a pass that
+ * visits nothing), 0.82 / 0.96 ms with 8 classes that each lack 1 % / 30 % of the nodes, of which
+ * the pass is 0.39 / 0.43 ms -- 2.6 times K1, because with 8 classes in every pod wave no block is
+ * skipped; yoda_set_candidates 0.1 ms, yoda_update_candidates of up to 1,024 nodes under 0.07 ms. */
+#define YODA_MAX_CAND_CLASSES 64
+#define YODA_CAND_ANY 0xFFu /* the pod is unrestricted: every node is a candidate */
+/* words[n_nodes of this handle's shard], upload order.  n_classes 1..64; bits >= n_classes are
+ * ignored.  n_classes == 0 (words may be NULL) turns candidates off; so does yoda_upload_nodes.
+ * YODA_ERR_NO_NODES before an upload. */
+int yoda_set_candidates(yoda_t* h, uint32_t n_classes, const uint64_t* words);
+/* Sparse: replace the words of the listed nodes.  GLOBAL ids; ids outside the shard are ignored;
+ * the LAST entry of a repeated id wins; count == 0 is a no-op.  YODA_ERR_STATE while candidates
+ * are off. */
+int yoda_update_candidates(yoda_t* h, uint32_t count, const uint32_t* nodes,
+                           const uint64_t* words);
+/* The class of every pod of the batches run from now on: cls[n_pods], each < n_classes or
+ * YODA_CAND_ANY.  NULL or n_pods == 0 makes every pod YODA_CAND_ANY again.  Stays on the handle
+ * across uploads of pods; a run with candidates on whose class array is not as long as the
+ * uploaded batch returns YODA_ERR_STATE and launches nothing. */
+int yoda_set_pod_classes(yoda_t* h, uint32_t n_pods, const uint8_t* cls);
+/* Diagnostic, host only: out[3] = {n_classes (0 = off), the length of the class array, nodes
+ * whose word lacks at least one of the n_classes bits}. */
+int yoda_candidates_info(const yoda_t* h, uint32_t* out);
+/* Diagnostic: the narrowing pass's time (HIP events, ms) summed over the runs that the
+ * yoda_profile_read calls since the last call of this one have read (yoda_profile on). */
+int yoda_candidates_profile(yoda_t* h, double* narrow_ms);
 /* Diagnostic (synchronizes).  digest[8]: a 64-bit hash per table over its words as the device
  * holds them -- records, K1 summaries, K2 summaries, per-card model rows, K1 mixed tiles, block
  * summaries, G table, G maxima + reciprocals (0 where the record path has none).  mismatch[4]:

@@ -259,6 +259,17 @@ struct yoda_handle {
   // makes every node present.  The G maxima above are those of the PRESENT nodes.
   std::vector<uint8_t> h_absent;
   uint32_t n_absent = 0;
+  // yoda_set_candidates: other plugins' Filter results as candidate classes.  cand_classes != 0:
+  // on.  One 64-bit word per node (bit c: a candidate of class c): the host mirror, the device
+  // table in upload order with the AND and the zero_total bits of each 64-node block, and all
+  // three again in the block-grouped order (perm_on).  The pods' class bytes (caller order; empty: every pod YODA_CAND_ANY) stay
+  // across pod uploads; cls_top: the largest class in them, -1 none.
+  uint32_t cand_classes = 0;
+  std::vector<uint64_t> h_cand;
+  DevBuf cand_w, cand_and, cand_zt, cand_w_p, cand_and_p, cand_zt_p;
+  std::vector<uint8_t> h_cls;
+  int cls_top = -1;
+  DevBuf cand_cls;
   // yoda_update_node_cards / yoda_snapshot_check: the changed nodes' packed rows (host), the
   // block summaries k_bsum_build writes for the self-check
   std::vector<uint32_t> cu_rows;
@@ -416,6 +427,8 @@ struct yoda_handle {
   bool profiling = false;
   std::vector<hipEvent_t> ev_pool;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_k1, ev_k2;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_cand;  // around the narrowing pass
+  double cand_ms = 0;  // ... summed by yoda_profile_read, handed out by yoda_candidates_profile
   size_t ev_used = 0;
 
   hipEvent_t next_event() {
@@ -887,10 +900,33 @@ int pods_complete(yoda_t* h) {
 // Mode B has no Filter and kernels of its own, none of which reads the presence bits
 // (yoda_set_node_present): while a node is absent its entry points refuse to run.
 int mode_b_absent(yoda_t* h, int mode) {
-  if (mode != YODA_MODE_DISKIO || h->n_absent == 0) return YODA_OK;
+  if (mode != YODA_MODE_DISKIO) return YODA_OK;
+  if (h->cand_classes)
+    return fail(h, YODA_ERR_STATE,
+                "Mode B does not honour candidate classes (yoda_set_candidates): turn them off");
+  if (h->n_absent == 0) return YODA_OK;
   return fail(h, YODA_ERR_STATE,
               "Mode B does not honour absent nodes (yoda_set_node_present): return every node "
               "or upload the snapshot without them");
+}
+
+// Candidate classes narrow the batch path only (yoda_run, yoda_eval, the row calls): the greedy,
+// shard and communicator entry points refuse to run while they are on, as Mode B does.
+int cand_refuse(yoda_t* h, const char* what) {
+  if (!h->cand_classes) return YODA_OK;
+  return fail(h, YODA_ERR_STATE,
+              std::string(what) + " does not honour candidate classes (yoda_set_candidates): "
+                                  "turn them off (n_classes 0)");
+}
+
+// A batch run with candidates on: the class array fits the uploaded batch and the class count.
+int cand_ready(yoda_t* h) {
+  if (!h->cand_classes) return YODA_OK;
+  if (!h->h_cls.empty() && h->h_cls.size() != h->n_pods)
+    return fail(h, YODA_ERR_STATE, "yoda_set_pod_classes: the class array's length is not n_pods");
+  if (h->cls_top >= (int)h->cand_classes)
+    return fail(h, YODA_ERR_STATE, "yoda_set_pod_classes: a class is not below n_classes");
+  return YODA_OK;
 }
 
 int check_ready(yoda_t* h, int mode) {
@@ -902,6 +938,7 @@ int check_ready(yoda_t* h, int mode) {
   if (mode == YODA_MODE_DISKIO && !(h->nodes_diskio && h->pods_diskio))
     return fail(h, YODA_ERR_INVALID_ARG, "Mode B needs node cpu/disk_io and pod rio/rcpu");
   if (int rc = mode_b_absent(h, mode)) return rc;
+  if (int rc = cand_ready(h)) return rc;
   HIP_TRY(h, hipSetDevice(h->device));
   return h->fast_run ? YODA_OK : pods_complete(h);
 }
@@ -1303,7 +1340,9 @@ int phase1(yoda_t* h, int mode, uint64_t* maxima, uint32_t* counts,
   hipEvent_t e1 = h->profiling ? h->next_event() : nullptr;
   h->blk_valid = h->has_k1sum;
   h->bm_sparse = h->has_k1sum;  // the block K1 writes the sparse form
-  h->seeds_valid = h->has_k1sum && mode == YODA_MODE_SCV;
+  // (candidates on: no seed -- it is a best over every node of an ALL block, and may sit above
+  // the best of a pod's candidates)
+  h->seeds_valid = h->has_k1sum && mode == YODA_MODE_SCV && !h->cand_classes;
   h->blk_fresh = h->has_k1sum;  // (the memset below or the order scatter clears it whole)
   if (h->blk_valid && !h->blk_zeroed)  // (the list and the seeds after it)
     HIP_TRY(h, hipMemsetAsync(h->blk.p, 0, blk_words(h, P) * 8, h->stream));
@@ -1362,6 +1401,31 @@ int phase1(yoda_t* h, int mode, uint64_t* maxima, uint32_t* counts,
                             h->has_k1sum ? pod_params(h).cmask1 : nullptr));
   h->lpt_sorted = h->lpt_active;  // (the order of this run's pod blocks, for phase 2)
   h->rcp_ready = rcp;
+  if (h->cand_classes) {  // the masks and counts from Yoda's Filter to every plugin's
+    CandArgs a{};
+    a.words = (pr ? h->cand_w_p : h->cand_w).as<uint64_t>();
+    a.band = (pr ? h->cand_and_p : h->cand_and).as<uint64_t>();
+    a.cls = h->h_cls.empty() ? nullptr : h->cand_cls.as<uint8_t>();
+    a.perm = h->ordered ? h->perm.as<uint32_t>() : nullptr;
+    a.zt = (pr ? h->cand_zt_p : h->cand_zt).as<uint64_t>();
+    a.n_nodes = h->n_nodes;
+    a.n_work = P;
+    a.bm = h->bitmask.as<uint64_t>();
+    a.bs = h->bm_sparse ? h->bsum.as<BlockMask>() : nullptr;
+    a.blk = h->bm_sparse ? h->blk.as<uint64_t>() : nullptr;
+    a.bm_stride = bm_row(h->n_nodes);
+    a.bs_stride = bs_row(h->n_nodes);
+    a.blk_stride = blk_row(h->n_nodes);
+    a.counts = counts;
+    hipEvent_t c0 = h->profiling ? h->next_event() : nullptr;
+    hipEvent_t c1 = h->profiling ? h->next_event() : nullptr;
+    if (c0) HIP_TRY(h, hipEventRecord(c0, h->stream));
+    HIP_TRY(h, launch_cand_narrow(a, h->stream));
+    if (c1) {
+      HIP_TRY(h, hipEventRecord(c1, h->stream));
+      h->ev_cand.emplace_back(c0, c1);
+    }
+  }
   return YODA_OK;
 }
 
@@ -2354,6 +2418,8 @@ int yoda_upload_nodes(yoda_t* h, const yoda_node_soa* nd, uint32_t node_offset, 
     if (nd->alloc_memory) h->h_alloc.assign(nd->alloc_memory, nd->alloc_memory + N);
     h->h_absent.assign(N, 0);  // every node of a fresh snapshot is present
     h->n_absent = 0;
+    h->cand_classes = 0;  // ... and a candidate of every pod (yoda_set_candidates: off)
+    h->h_cand.clear();
     h->nodes_diskio = diskio;
     h->all_one_model = rows.n_one_model == N;
     h->all_uni4 = rows.n_uni4 == N;
@@ -3082,8 +3148,9 @@ int yoda_shard_draw_keys(yoda_t* h, int mode, uint64_t* d_keys) {
   if (!d_keys) return fail(h, YODA_ERR_INVALID_ARG, "NULL key buffer");
   if (mode != YODA_MODE_SCV && mode != YODA_MODE_DISKIO)
     return fail(h, YODA_ERR_INVALID_ARG, "mode must be YODA_MODE_SCV or YODA_MODE_DISKIO");
-  int rc = mode_b_absent(h, mode);
+  int rc = cand_refuse(h, "yoda_shard_draw_keys");
   if (rc) return rc;
+  if ((rc = mode_b_absent(h, mode))) return rc;
   if ((rc = shard_draw_ready(h, "yoda_shard_draw_keys"))) return rc;
   if (mode != h->last_mode)
     return fail(h, YODA_ERR_STATE, "yoda_shard_draw_keys: the step ran in the other mode");
@@ -3120,8 +3187,9 @@ int yoda_shard_draw_keys(yoda_t* h, int mode, uint64_t* d_keys) {
 int yoda_shard_draw_apply(yoda_t* h, const uint64_t* d_keys) {
   if (!h) return YODA_ERR_INVALID_ARG;
   if (!d_keys) return fail(h, YODA_ERR_INVALID_ARG, "NULL key buffer");
-  int rc = shard_draw_ready(h, "yoda_shard_draw_apply");
+  int rc = cand_refuse(h, "yoda_shard_draw_apply");
   if (rc) return rc;
+  if ((rc = shard_draw_ready(h, "yoda_shard_draw_apply"))) return rc;
   if (h->draw_stage != 2)
     return fail(h, YODA_ERR_STATE, "yoda_shard_draw_apply before this step's yoda_shard_draw_keys");
   HIP_TRY(h, hipSetDevice(h->device));
@@ -3139,6 +3207,7 @@ int yoda_shard_exchange_order(yoda_t* h, int caller_order) {
 
 int yoda_shard_phase1(yoda_t* h, int mode, uint64_t* d_maxima, uint32_t* d_counts) {
   if (!h) return YODA_ERR_INVALID_ARG;
+  if (int rc = cand_refuse(h, "yoda_shard_phase1")) return rc;
   // caller-order exchange (yoda_shard_exchange_order): each shard its private order; not on the
   // U64 path (its exact-normalize records are per sorted position)
   h->xo = h->xo_enabled && !h->generic;
@@ -3165,8 +3234,10 @@ int yoda_shard_phase1(yoda_t* h, int mode, uint64_t* d_maxima, uint32_t* d_count
 
 int yoda_shard_phase2(yoda_t* h, int mode, const uint64_t* d_maxima, const uint32_t* d_counts,
                       int64_t* d_best, uint32_t* d_idx, uint32_t* d_ties, int64_t* d_lowest) {
-  int rc = check_ready(h, mode);
+  if (!h) return YODA_ERR_INVALID_ARG;
+  int rc = cand_refuse(h, "yoda_shard_phase2");
   if (rc) return rc;
+  if ((rc = check_ready(h, mode))) return rc;
   if (!h->phase1_done) return fail(h, YODA_ERR_STATE, "yoda_shard_phase2 before phase1");
   if (!d_maxima || !d_counts || !d_best || !d_idx || !d_ties || !d_lowest)
     return fail(h, YODA_ERR_INVALID_ARG, "NULL exchange buffer");
@@ -3195,6 +3266,7 @@ int yoda_shard_phase2(yoda_t* h, int mode, const uint64_t* d_maxima, const uint3
 int yoda_shard_prepare_merge(yoda_t* h, const int64_t* d_best_global, const int64_t* d_best_local,
                              uint32_t* d_idx, uint32_t* d_ties) {
   if (!h) return YODA_ERR_INVALID_ARG;
+  if (int rc = cand_refuse(h, "yoda_shard_prepare_merge")) return rc;
   if (!d_best_global || !d_best_local || !d_idx || !d_ties)
     return fail(h, YODA_ERR_INVALID_ARG, "NULL exchange buffer");
   HIP_TRY(h, hipSetDevice(h->device));
@@ -3206,8 +3278,10 @@ int yoda_shard_prepare_merge(yoda_t* h, const int64_t* d_best_global, const int6
 
 int yoda_shard_finalize(yoda_t* h, int mode, const uint32_t* d_counts, const int64_t* d_best,
                         const uint32_t* d_idx, const uint32_t* d_ties, const int64_t* d_lowest) {
-  int rc = check_ready(h, mode);
+  if (!h) return YODA_ERR_INVALID_ARG;
+  int rc = cand_refuse(h, "yoda_shard_finalize");
   if (rc) return rc;
+  if ((rc = check_ready(h, mode))) return rc;
   if (!d_counts || !d_best || !d_idx || !d_ties || !d_lowest)
     return fail(h, YODA_ERR_INVALID_ARG, "NULL exchange buffer");
   try {
@@ -3249,6 +3323,7 @@ int yoda_shard_finalize(yoda_t* h, int mode, const uint32_t* d_counts, const int
 
 int yoda_shard_exact_records(yoda_t* h, void* d_rec) {
   if (!h || !d_rec) return YODA_ERR_INVALID_ARG;
+  if (int rc = cand_refuse(h, "yoda_shard_exact_records")) return rc;
   if (!h->k3_pending) return fail(h, YODA_ERR_STATE, "no exact-normalize pods pending");
   HIP_TRY(h, hipSetDevice(h->device));
   HIP_TRY(h, hipMemcpyAsync(d_rec, h->k3rec.p, (size_t)h->n_work * sizeof(ShardRec),
@@ -3258,6 +3333,7 @@ int yoda_shard_exact_records(yoda_t* h, void* d_rec) {
 
 int yoda_shard_exact_merge(yoda_t* h, const void* d_all, int world) {
   if (!h || !d_all || world < 1) return YODA_ERR_INVALID_ARG;
+  if (int rc = cand_refuse(h, "yoda_shard_exact_merge")) return rc;
   if (!h->k3_pending) return fail(h, YODA_ERR_STATE, "no exact-normalize pods pending");
   try {
     HIP_TRY(h, hipSetDevice(h->device));
@@ -3395,11 +3471,17 @@ int yoda_profile_read(yoda_t* h, double* k1_ms, double* k2_ms, uint32_t* n_launc
     HIP_TRY(h, hipEventElapsedTime(&ms, pr.first, pr.second));
     t2 += ms;
   }
+  for (auto& pr : h->ev_cand) {
+    float ms = 0;
+    HIP_TRY(h, hipEventElapsedTime(&ms, pr.first, pr.second));
+    h->cand_ms += ms;
+  }
   if (k1_ms) *k1_ms = t1;
   if (k2_ms) *k2_ms = t2;
   if (n_launches) *n_launches = (uint32_t)h->ev_k2.size();
   h->ev_k1.clear();
   h->ev_k2.clear();
+  h->ev_cand.clear();
   h->ev_used = 0;
   return YODA_OK;
 }
@@ -3621,6 +3703,7 @@ int yoda_greedy(yoda_t* h, const yoda_pod_soa* pods, int mode, uint32_t flags, i
   if (!h) return YODA_ERR_INVALID_ARG;
   if (!pods || !pick) return fail(h, YODA_ERR_INVALID_ARG, "NULL pods or pick");
   if (!h->has_nodes) return fail(h, YODA_ERR_NO_NODES, "no node snapshot uploaded");
+  if (int rc = cand_refuse(h, "yoda_greedy")) return rc;
   if (int rc = mode_b_absent(h, mode)) return rc;
   try {
     HIP_TRY(h, hipSetDevice(h->device));
@@ -4460,6 +4543,187 @@ int yoda_nodes_absent(const yoda_t* h, uint32_t* n_absent) {
   return YODA_OK;
 }
 
+namespace {
+// A change of the candidate state: the pending outcomes are the old candidates', a sharded
+// step's pending exact merge included.
+void cand_invalidate(yoda_t* h) {
+  h->k3_pending = false;
+  h->ran = false;
+  h->phase1_done = false;
+  h->topk_ready = false;
+  h->draw_stage = 0;
+}
+
+// The per-block ANDs of both node orders from the device tables (whole: one wave per block).
+int cand_rebuild_sums(yoda_t* h, bool copy) {
+  const unsigned char* rec = h->nodes.as<unsigned char>();
+  const uint32_t stride = h->path == Path::N32 ? n32_stride(h->K) : node_stride(h->K);
+  HIP_TRY(h, launch_cand_build(h->cand_w.as<uint64_t>(), nullptr, rec, stride, h->n_nodes, nullptr,
+                               h->cand_and.as<uint64_t>(), h->cand_zt.as<uint64_t>(), h->stream));
+  if (h->perm_on)  // (copy: the grouped table too; else it is current -- k_cand_update)
+    HIP_TRY(h, launch_cand_build(h->cand_w.as<uint64_t>(), h->perm_ids.as<uint32_t>(), rec, stride,
+                                 h->n_nodes, copy ? h->cand_w_p.as<uint64_t>() : nullptr,
+                                 h->cand_and_p.as<uint64_t>(), h->cand_zt_p.as<uint64_t>(),
+                                 h->stream));
+  return YODA_OK;
+}
+}  // namespace
+
+int yoda_set_candidates(yoda_t* h, uint32_t n_classes, const uint64_t* words) {
+  if (!h) return YODA_ERR_INVALID_ARG;
+  if (n_classes > YODA_MAX_CAND_CLASSES)
+    return fail(h, YODA_ERR_INVALID_ARG, "n_classes above YODA_MAX_CAND_CLASSES");
+  if (n_classes == 0) {
+    if (h->cand_classes) cand_invalidate(h);
+    h->cand_classes = 0;
+    h->h_cand.clear();
+    return YODA_OK;
+  }
+  if (!words) return fail(h, YODA_ERR_INVALID_ARG, "NULL candidate words");
+  if (!h->has_nodes) return fail(h, YODA_ERR_NO_NODES, "no node snapshot uploaded");
+  try {
+    HIP_TRY(h, hipSetDevice(h->device));
+    const uint32_t N = h->n_nodes;
+    const size_t nb = std::max<size_t>((N + 63u) / 64u, 1);
+    HIP_TRY(h, h->cand_w.ensure(std::max<size_t>(N, 1) * 8));
+    HIP_TRY(h, h->cand_and.ensure(nb * 8));
+    HIP_TRY(h, h->cand_zt.ensure(nb * 8));
+    if (h->perm_on) {
+      HIP_TRY(h, h->cand_w_p.ensure(std::max<size_t>(N, 1) * 8));
+      HIP_TRY(h, h->cand_and_p.ensure(nb * 8));
+      HIP_TRY(h, h->cand_zt_p.ensure(nb * 8));
+    }
+    cand_invalidate(h);
+    h->cand_classes = 0;  // (off until the tables are whole)
+    h->h_cand.assign(words, words + N);
+    if (N) {
+      HIP_TRY(h, hipMemcpyAsync(h->cand_w.p, h->h_cand.data(), (size_t)N * 8,
+                                hipMemcpyHostToDevice, h->stream));
+      if (int rc = cand_rebuild_sums(h, true)) return rc;
+      HIP_TRY(h, hipStreamSynchronize(h->stream));  // (the copy's source is pageable)
+    }
+    h->cand_classes = n_classes;
+    return YODA_OK;
+  } catch (const std::bad_alloc&) {
+    return fail(h, YODA_ERR_INVALID_ARG, "host allocation failed");
+  } catch (...) {
+    return fail(h, YODA_ERR_INVALID_ARG, "unexpected exception");
+  }
+}
+
+int yoda_update_candidates(yoda_t* h, uint32_t count, const uint32_t* nodes,
+                           const uint64_t* words) {
+  if (!h) return YODA_ERR_INVALID_ARG;
+  if (!h->has_nodes) return fail(h, YODA_ERR_NO_NODES, "no node snapshot uploaded");
+  if (!h->cand_classes)
+    return fail(h, YODA_ERR_STATE, "yoda_update_candidates: candidates are off");
+  if (count == 0) return YODA_OK;
+  if (!nodes || !words) return fail(h, YODA_ERR_INVALID_ARG, "NULL candidate update array");
+  try {
+    HIP_TRY(h, hipSetDevice(h->device));
+    // one entry per node, the last of a repeated id (the upd_slot pattern of yoda_set_node_state)
+    if (h->upd_slot.size() != h->n_nodes) h->upd_slot.assign(h->n_nodes, ~0u);
+    std::vector<uint32_t> loc;
+    std::vector<uint64_t> val;
+    for (uint32_t t = 0; t < count; ++t) {
+      if (nodes[t] < h->node_offset || nodes[t] - h->node_offset >= h->n_nodes) continue;
+      const uint32_t i = nodes[t] - h->node_offset;
+      uint32_t& slot = h->upd_slot[i];
+      if (slot == ~0u) {
+        slot = (uint32_t)loc.size();
+        loc.push_back(i);
+        val.push_back(words[t]);
+      } else {
+        val[slot] = words[t];
+      }
+    }
+    for (uint32_t i : loc) h->upd_slot[i] = ~0u;
+    cand_invalidate(h);
+    const uint32_t cnt = (uint32_t)loc.size();
+    if (cnt == 0) return YODA_OK;
+    const size_t o_val = ((size_t)cnt * 4 + 15) / 16 * 16;
+    const size_t bytes = o_val + (size_t)cnt * 8;
+    if (h->upd_pending) HIP_TRY(h, hipEventSynchronize(h->upd_event));
+    HIP_TRY(h, h->upd_stage.ensure(bytes));
+    HIP_TRY(h, h->upd_node.ensure(bytes));
+    unsigned char* st = static_cast<unsigned char*>(h->upd_stage.p);
+    std::memcpy(st, loc.data(), (size_t)cnt * 4);
+    std::memcpy(st + o_val, val.data(), (size_t)cnt * 8);
+    for (uint32_t t = 0; t < cnt; ++t) h->h_cand[loc[t]] = val[t];
+    HIP_TRY(h, hipMemcpyAsync(h->upd_node.p, st, bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipEventRecord(h->upd_event, h->stream));
+    h->upd_pending = true;
+    const unsigned char* d = h->upd_node.as<unsigned char>();
+    HIP_TRY(h, launch_cand_update(reinterpret_cast<const uint32_t*>(d),
+                                  reinterpret_cast<const uint64_t*>(d + o_val), cnt,
+                                  h->cand_w.as<uint64_t>(),
+                                  h->perm_on ? h->perm_inv.as<uint32_t>() : nullptr,
+                                  h->perm_on ? h->cand_w_p.as<uint64_t>() : nullptr, h->stream));
+    // the block ANDs of both orders: whole, one wave a block (12 KB each at 100k nodes)
+    return cand_rebuild_sums(h, false);
+  } catch (const std::bad_alloc&) {
+    h->upd_slot.clear();
+    return fail(h, YODA_ERR_INVALID_ARG, "host allocation failed");
+  } catch (...) {
+    h->upd_slot.clear();
+    return fail(h, YODA_ERR_INVALID_ARG, "unexpected exception");
+  }
+}
+
+int yoda_set_pod_classes(yoda_t* h, uint32_t n_pods, const uint8_t* cls) {
+  if (!h) return YODA_ERR_INVALID_ARG;
+  if (!cls || n_pods == 0) {
+    if (!h->h_cls.empty()) cand_invalidate(h);
+    h->h_cls.clear();
+    h->cls_top = -1;
+    return YODA_OK;
+  }
+  // (candidates off: any class a later yoda_set_candidates could name; the run checks again)
+  const uint32_t lim = h->cand_classes ? h->cand_classes : (uint32_t)YODA_MAX_CAND_CLASSES;
+  int top = -1;
+  for (uint32_t p = 0; p < n_pods; ++p) {
+    if (cls[p] == YODA_CAND_ANY) continue;
+    if (cls[p] >= lim)
+      return fail(h, YODA_ERR_INVALID_ARG, "a pod class is neither below n_classes nor YODA_CAND_ANY");
+    top = std::max(top, (int)cls[p]);
+  }
+  try {
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, h->cand_cls.ensure(n_pods));
+    std::vector<uint8_t> copy(cls, cls + n_pods);
+    HIP_TRY(h, hipMemcpyAsync(h->cand_cls.p, copy.data(), n_pods, hipMemcpyHostToDevice,
+                              h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));  // (the copy's source is pageable)
+    cand_invalidate(h);
+    h->h_cls.swap(copy);
+    h->cls_top = top;
+    return YODA_OK;
+  } catch (const std::bad_alloc&) {
+    return fail(h, YODA_ERR_INVALID_ARG, "host allocation failed");
+  } catch (...) {
+    return fail(h, YODA_ERR_INVALID_ARG, "unexpected exception");
+  }
+}
+
+int yoda_candidates_profile(yoda_t* h, double* narrow_ms) {
+  if (!h || !narrow_ms) return YODA_ERR_INVALID_ARG;
+  *narrow_ms = h->cand_ms;
+  h->cand_ms = 0;
+  return YODA_OK;
+}
+
+int yoda_candidates_info(const yoda_t* h, uint32_t* out) {
+  if (!h || !out) return YODA_ERR_INVALID_ARG;
+  out[0] = h->cand_classes;
+  out[1] = (uint32_t)h->h_cls.size();
+  out[2] = 0;
+  if (h->cand_classes) {
+    const uint64_t all = h->cand_classes == 64 ? ~0ull : (1ull << h->cand_classes) - 1ull;
+    for (uint64_t w : h->h_cand) out[2] += (w & all) != all;
+  }
+  return YODA_OK;
+}
+
 int yoda_snapshot_check(yoda_t* h, uint64_t* digest, uint32_t* mismatch) {
   if (!h) return YODA_ERR_INVALID_ARG;
   if (!h->has_nodes) return fail(h, YODA_ERR_NO_NODES, "no node snapshot uploaded");
@@ -4557,8 +4821,10 @@ namespace {
 // whatever this shard's kernels.
 int shard_topk_impl(yoda_t* h, const uint64_t* d_maxima, const uint32_t* d_counts, uint32_t k,
                     uint32_t deep, uint32_t* counts, double* top_score, uint32_t* top_node) {
-  int rc = check_ready(h, YODA_MODE_SCV);
+  if (!h) return YODA_ERR_INVALID_ARG;
+  int rc = cand_refuse(h, "yoda_shard_topk");
   if (rc) return rc;
+  if ((rc = check_ready(h, YODA_MODE_SCV))) return rc;
   if (h->xo)  // (the window top-k reads the shared radix order's buffers)
     return fail(h, YODA_ERR_STATE, "yoda_shard_topk after a caller-order phase 1: turn "
                                    "yoda_shard_exchange_order off for greedy windows");
@@ -4630,6 +4896,7 @@ int shard_topk_impl(yoda_t* h, const uint64_t* d_maxima, const uint32_t* d_count
 int yoda_shard_phase1_witness(yoda_t* h, uint64_t* d_maxima, uint32_t* d_counts,
                               uint32_t* d_wit) {
   if (!h) return YODA_ERR_INVALID_ARG;
+  if (int rc = cand_refuse(h, "yoda_shard_phase1_witness")) return rc;
   h->xo = false;  // (greedy windows: the shared radix order)
   int rc = prepare_run(h, YODA_MODE_SCV);
   if (rc) return rc;
@@ -4651,6 +4918,7 @@ int yoda_shard_phase1_witness(yoda_t* h, uint64_t* d_maxima, uint32_t* d_counts,
 int yoda_shard_witness_prepare(yoda_t* h, const uint64_t* d_maxima_global,
                                const uint64_t* d_maxima_local, uint32_t* d_wit) {
   if (!h) return YODA_ERR_INVALID_ARG;
+  if (int rc = cand_refuse(h, "yoda_shard_witness_prepare")) return rc;
   if (!d_maxima_global || !d_maxima_local || !d_wit)
     return fail(h, YODA_ERR_INVALID_ARG, "NULL buffer");
   HIP_TRY(h, hipSetDevice(h->device));
@@ -4661,6 +4929,7 @@ int yoda_shard_witness_prepare(yoda_t* h, const uint64_t* d_maxima_global,
 int yoda_shard_witness_download(yoda_t* h, const uint64_t* d_maxima, const uint32_t* d_wit,
                                 uint64_t* maxima, uint32_t* wit) {
   if (!h) return YODA_ERR_INVALID_ARG;
+  if (int rc = cand_refuse(h, "yoda_shard_witness_download")) return rc;
   if (!d_maxima || !d_wit || !maxima || !wit) return fail(h, YODA_ERR_INVALID_ARG, "NULL buffer");
   if (!h->topk_ready)
     return fail(h, YODA_ERR_STATE, "yoda_shard_witness_download before yoda_shard_topk");
@@ -4687,6 +4956,7 @@ int yoda_shard_witness_download(yoda_t* h, const uint64_t* d_maxima, const uint3
 
 int yoda_shard_best_one(yoda_t* h, uint32_t pod, double* score, int32_t* node) {
   if (!h) return YODA_ERR_INVALID_ARG;
+  if (int rc = cand_refuse(h, "yoda_shard_best_one")) return rc;
   if (!score || !node) return fail(h, YODA_ERR_INVALID_ARG, "NULL output");
   if (!h->topk_ready) return fail(h, YODA_ERR_STATE, "yoda_shard_best_one before yoda_shard_topk");
   if (pod >= h->n_pods) return fail(h, YODA_ERR_INVALID_ARG, "pod index out of range");
@@ -5800,9 +6070,11 @@ static int comm_step(yoda_t* const* hs, int n, int world, int mode, bool local, 
   yoda_t* h0 = hs[0];
   const uint32_t P = h0->n_pods;
   const size_t n1 = 6 * (size_t)P + kAgreeWords;  // maxima | agreement words
-  for (int i = 0; i < n; ++i)  // (before any shard's run is prepared)
+  for (int i = 0; i < n; ++i) {  // (before any shard's run is prepared)
+    if (hs[i]->cand_classes) return fail(h0, cand_refuse(hs[i], "yoda_comm_run"), hs[i]->last_error);
     if (hs[i]->n_absent && mode == YODA_MODE_DISKIO)
       return fail(h0, mode_b_absent(hs[i], mode), hs[i]->last_error);
+  }
   for (int i = 0; i < n; ++i) {
     yoda_t* h = hs[i];
     if (h->n_pods != P) return fail(h0, YODA_ERR_INVALID_ARG, "shards hold different batches");
@@ -6210,9 +6482,12 @@ static int comm_greedy(yoda_t* const* hs, int n, int world, bool local, const yo
   const uint32_t P = pods->n_pods;
   for (int i = 0; i < n; ++i)
     if (!hs[i]->has_nodes) return fail(h0, YODA_ERR_NO_NODES, "no node snapshot uploaded");
-  for (int i = 0; i < n; ++i)
+  for (int i = 0; i < n; ++i) {
+    if (hs[i]->cand_classes)
+      return fail(h0, cand_refuse(hs[i], "yoda_comm_greedy"), hs[i]->last_error);
     if (hs[i]->n_absent && mode == YODA_MODE_DISKIO)
       return fail(h0, mode_b_absent(hs[i], mode), hs[i]->last_error);
+  }
   if (P == 0) return YODA_OK;
   int rc;
   PodGather win;

@@ -4935,6 +4935,200 @@ __global__ __launch_bounds__(kBlock) void k_bitmask_transpose(const MaskSrc ms,
 }
 
 // ---------------------------------------------------------------------------------------
+// Candidate classes (yoda_set_candidates; DESIGN.md §5 "Other plugins' Filter results").
+//
+// The candidate table of one node order: out[pos] = words[ids ? ids[pos] : pos] (out == nullptr:
+// the order is the table's own), band[b] = the AND of the words of block b's real nodes (an
+// absent node counts: the AND over a superset only skips less) and zt[b] = the block's nodes
+// whose record says zero_total (TotalMemorySum == 0: static).  One wave per 64-node block.
+__global__ __launch_bounds__(kWave) void k_cand_build(const uint64_t* __restrict__ words,
+                                                      const uint32_t* __restrict__ ids,
+                                                      const unsigned char* __restrict__ nodes,
+                                                      uint32_t stride, uint32_t n_nodes,
+                                                      uint64_t* __restrict__ out,
+                                                      uint64_t* __restrict__ band,
+                                                      uint64_t* __restrict__ zt) {
+  const uint32_t b = blockIdx.x, n = 64u * b + threadIdx.x;
+  uint64_t v = ~0ull;
+  bool z = false;
+  if (n < n_nodes) {
+    const uint32_t id = ids ? ids[n] : n;
+    v = words[id];
+    if (out) out[n] = v;
+    // (the record header's zero_total; NodeHdrF and NodeHdrG agree)
+    z = reinterpret_cast<const NodeHdrG*>(nodes + (size_t)id * stride)->zero_total != 0u;
+  }
+  uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    lo &= (uint32_t)__shfl_xor((int)lo, d);
+    hi &= (uint32_t)__shfl_xor((int)hi, d);
+  }
+  const uint64_t zb = ballot(z);
+  if (threadIdx.x == 0) {
+    band[b] = (uint64_t)lo | ((uint64_t)hi << 32);
+    zt[b] = zb;
+  }
+}
+
+// yoda_update_candidates: the listed nodes' words into the table and its block-grouped copy.
+__global__ __launch_bounds__(kBlock) void k_cand_update(const uint32_t* __restrict__ node,
+                                                        const uint64_t* __restrict__ value,
+                                                        uint32_t count, uint64_t* __restrict__ words,
+                                                        const uint32_t* __restrict__ inv,
+                                                        uint64_t* __restrict__ words_p) {
+  const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+  if (t >= count) return;
+  const uint32_t n = node[t];
+  words[n] = value[t];
+  if (words_p) words_p[inv[n]] = value[t];
+}
+
+__device__ __forceinline__ uint64_t readlane_u64(uint64_t v, uint32_t l) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, (int)l);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), (int)l);
+  return (uint64_t)lo | ((uint64_t)hi << 32);
+}
+
+// The 64 x 64 bit transpose of a wave's 64-bit words: lane l ends with bit j = bit l of lane j's
+// word.  Six butterfly steps; step d swaps the off-diagonal d x d blocks of every 2d x 2d block
+// between lanes l and l ^ d.  Whole wave active.
+template <int D>
+__device__ __forceinline__ uint64_t transpose_step(uint64_t x, uint32_t lane, uint64_t m) {
+  const uint64_t y = (uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)x, D) |
+                     ((uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)(x >> 32), D) << 32);
+  return (lane & (uint32_t)D) ? ((x & ~m) | ((y & ~m) >> D)) : ((x & m) | ((y & m) << D));
+}
+__device__ __forceinline__ uint64_t wave_transpose64(uint64_t x, uint32_t lane) {
+  x = transpose_step<32>(x, lane, 0x00000000ffffffffull);
+  x = transpose_step<16>(x, lane, 0x0000ffff0000ffffull);
+  x = transpose_step<8>(x, lane, 0x00ff00ff00ff00ffull);
+  x = transpose_step<4>(x, lane, 0x0f0f0f0f0f0f0f0full);
+  x = transpose_step<2>(x, lane, 0x3333333333333333ull);
+  x = transpose_step<1>(x, lane, 0x5555555555555555ull);
+  return x;
+}
+
+// Bit-sliced counters of the narrowing pass: lane j (a node slot) holds, per pod bit l, a
+// kCandPlanes-bit count spread over the planes (plane k = bit k of the 64 counts).  Adding a
+// 64-bit vector of 0/1 is a ripple carry over the planes; 2^kCandPlanes - 1 additions fit.
+constexpr int kCandPlanes = 6;
+constexpr uint32_t kCandFlush = (1u << kCandPlanes) - 1u;
+__device__ __forceinline__ void cand_add(uint64_t (&pl)[kCandPlanes], uint64_t x) {
+#pragma unroll
+  for (int k = 0; k < kCandPlanes; ++k) {
+    const uint64_t carry = pl[k] & x;
+    pl[k] ^= x;
+    x = carry;
+  }
+}
+// The counters summed over the node slots, lane = pod: per plane one transpose and a popcount.
+// A plane that is zero on every lane costs one ballot.
+__device__ __forceinline__ uint32_t cand_fold(const uint64_t (&pl)[kCandPlanes], uint32_t lane) {
+  uint32_t c = 0;
+#pragma unroll
+  for (int k = 0; k < kCandPlanes; ++k) {
+    if (ballot(pl[k] != 0ull) == 0ull) continue;
+    c += (uint32_t)__builtin_popcountll(wave_transpose64(pl[k], lane)) << k;
+  }
+  return c;
+}
+
+// The narrowing pass: K1's masks from F (Yoda's Filter) to F' = F and cand, in place, with
+// counts[0] (n_feasible) and counts[1] (n_zero_total) corrected; the PreScore maxima are K1's,
+// over F (collection.go:39-52 never sees another plugin's Filter).  One wave per (pod wave,
+// window of 64 node blocks), lane = pod for the wave's classes and the counts, lane = block for
+// the window's skip tests, lane = node inside a block.  Per task once: the distinct classes (a
+// 64-bit set, pm) and, in lane c, the pod lanes of class c; YODA_CAND_ANY lanes pass every node.
+// A block is skipped without mask traffic when the wave does not list it (one word of the block
+// list covers the window) or when every class of the wave is in the block's AND (nothing to
+// narrow: one ballot over the window's ANDs); else the node's candidate lanes are the OR over
+// the wave's classes set in its word.  Sparse form: nz / full recomputed, bm[n] written for
+// every node that ends up partial and changed (K1 never wrote it for a full node), a block left
+// without a feasible pod leaves the wave's list.  The lost bits are counted per pod through the
+// bit-sliced counters above, folded once per task.
+__global__ __launch_bounds__(kWave) void k_cand_narrow(const CandArgs a) {
+  const Tile tl = tile();
+  const uint32_t w = tl.pb, lane = threadIdx.x;
+  const uint32_t NB = (a.n_nodes + 63u) >> 6;
+  const uint32_t wb = tl.chunk * 64u;
+  if (wb >= NB) return;
+  // (the window is one word of the wave's block list; a bit past the last block is clear)
+  unsigned long long* blkw =
+      a.bs ? reinterpret_cast<unsigned long long*>(a.blk) + (size_t)w * a.blk_stride + tl.chunk
+           : nullptr;
+  const uint64_t listed = blkw ? uniform_u64(*blkw) : ~0ull;
+  if (listed == 0ull) return;
+  const uint32_t p = 64u * w + lane;
+  const uint64_t live = wave_live(w, a.n_work);
+  // (a padding position is a copy of its pod, class included: it writes what the pod writes)
+  uint32_t c = 0xffu;
+  if (p < a.n_work && a.cls) c = a.cls[a.perm ? a.perm[p] : p];
+  const uint64_t any = ballot(c == 0xffu) & live;
+  uint64_t rem = live & ~any;
+  if (rem == 0ull) return;  // every pod of the wave is unrestricted
+  uint64_t pm = 0ull, ls = 0ull;
+  while (rem) {
+    const uint32_t cc = (uint32_t)__builtin_amdgcn_readlane((int)c, __builtin_ctzll(rem)) & 63u;
+    const uint64_t set = ballot(c == cc);
+    pm |= 1ull << cc;
+    if (lane == cc) ls = set;
+    rem &= ~set;
+  }
+  const uint64_t band = wb + lane < NB ? a.band[wb + lane] : ~0ull;
+  uint64_t todo = ballot((pm & ~band) != 0ull) & listed;
+  uint64_t pf[kCandPlanes] = {}, pz[kCandPlanes] = {};
+  uint32_t pending = 0;
+  auto flush = [&]() {
+    const uint32_t df = cand_fold(pf, lane), dz = cand_fold(pz, lane);
+    if (df) atomicSub(a.counts + p, df);  // (df != 0: a lost bit of this lane, so p < n_work)
+    if (dz) atomicSub(a.counts + a.n_work + p, dz);
+#pragma unroll
+    for (int k = 0; k < kCandPlanes; ++k) pf[k] = pz[k] = 0ull;
+    pending = 0;
+  };
+  uint64_t* bmw = a.bm + (size_t)w * a.bm_stride;
+  while (todo) {
+    const uint32_t j = (uint32_t)__builtin_ctzll(todo);
+    todo &= todo - 1ull;
+    const uint32_t b = wb + j, n = 64u * b + lane;
+    const bool real = n < a.n_nodes;
+    const uint64_t wd = real ? a.words[n] : 0ull;
+    uint64_t old = 0ull;
+    if (a.bs) {
+      const BlockMask bk = a.bs[(size_t)w * a.bs_stride + b];
+      if ((bk.full >> lane) & 1ull) old = live;
+      else if ((bk.nz >> lane) & 1ull) old = bmw[n];
+    } else if (real) {
+      old = bmw[n];
+    }
+    old = real ? old & live : 0ull;  // (no bit of a lane past the batch is ever counted)
+    uint64_t cand = any;
+    for (uint64_t m = pm; m; m &= m - 1ull) {
+      const uint32_t cc = (uint32_t)__builtin_ctzll(m);
+      const uint64_t s = readlane_u64(ls, cc);
+      if ((wd >> cc) & 1ull) cand |= s;
+    }
+    const uint64_t keep = old & cand, lost = old & ~cand;
+    if (ballot(lost != 0ull) == 0ull) continue;
+    if (a.bs) {
+      const uint64_t nz = ballot(keep != 0ull), full = ballot(keep == live);
+      if (lost != 0ull && keep != 0ull && keep != live) bmw[n] = keep;
+      if (lane == 0) {
+        a.bs[(size_t)w * a.bs_stride + b] = BlockMask{nz, full};
+        if (nz == 0ull) atomicAnd(blkw, ~(1ull << j));
+      }
+    } else if (lost != 0ull) {
+      bmw[n] = keep;
+    }
+    cand_add(pf, lost);
+    cand_add(pz, ((a.zt[b] >> lane) & 1ull) ? lost : 0ull);
+    if (++pending == kCandFlush) flush();
+  }
+  if (pending) flush();
+}
+
+// ---------------------------------------------------------------------------------------
 // Launchers (host side of this translation unit).
 #define YODA_K_SWITCH(K, ...)                       \
   switch (K) {                                      \
@@ -5801,6 +5995,39 @@ hipError_t launch_bitmask_transpose(const uint64_t* bm, uint32_t bm_stride, cons
   if (bs && !blk) return hipErrorInvalidValue;  // sparse masks are read through their block list
   hipLaunchKernelGGL(k_bitmask_transpose, grid, dim3(kBlock), 0, s, ms, n_nodes, W,
                      n_pods, perm, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_cand_build(const uint64_t* words, const uint32_t* ids,
+                             const unsigned char* nodes, uint32_t stride, uint32_t n_nodes,
+                             uint64_t* out, uint64_t* band, uint64_t* zt, hipStream_t s) {
+  if (n_nodes == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_cand_build, dim3((n_nodes + 63u) / 64u), dim3(kWave), 0, s, words, ids,
+                     nodes, stride, n_nodes, out, band, zt);
+  return hipGetLastError();
+}
+
+hipError_t launch_cand_update(const uint32_t* node, const uint64_t* value, uint32_t count,
+                              uint64_t* words, const uint32_t* inv, uint64_t* words_p,
+                              hipStream_t s) {
+  if (count == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_cand_update, pod_grid(count), dim3(kBlock), 0, s, node, value, count, words,
+                     inv, words_p);
+  return hipGetLastError();
+}
+
+// Grid (pod waves, windows of 64 node blocks), placed by tile() as K1's (pod blocks, chunks) are:
+// from 8 windows on their number is rounded up to a multiple of 8 (the XCD tiling; the trailing
+// windows are empty).  One wave a workgroup, no LDS; 94 VGPRs (the two sets of counter planes and
+// the transpose) leave 5 waves a SIMD, and at 100k x 100k the 39k tasks of real windows fill
+// those slots seven times over (profiles/candidates/kernel_regs.txt).
+hipError_t launch_cand_narrow(const CandArgs& a, hipStream_t s) {
+  if (a.n_work == 0 || a.n_nodes == 0) return hipSuccess;
+  if (a.bs && !a.blk) return hipErrorInvalidValue;  // sparse masks are read through their list
+  const uint32_t nw = (a.n_work + 63u) / 64u;
+  uint32_t C = blk_row(a.n_nodes);
+  if (C >= 8u) C = (C + 7u) / 8u * 8u;
+  hipLaunchKernelGGL(k_cand_narrow, dim3(nw, C), dim3(kWave), 0, s, a);
   return hipGetLastError();
 }
 

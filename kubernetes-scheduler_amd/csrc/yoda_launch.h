@@ -211,6 +211,17 @@ hipError_t launch_merge3_top(const ShardRec* all, uint32_t n_pods, uint32_t worl
                              uint32_t max_flagged, int64_t* norm_top, hipStream_t s);
 hipError_t launch_min_multi(const PtrList& src, uint32_t k, uint64_t n, uint64_t* dst,
                             hipStream_t s);
+// Candidate classes (yoda_set_candidates).  launch_cand_build: the table of one node order
+// (out, or nullptr for the table's own order), its per-block AND and the blocks' zero_total
+// bits; launch_cand_update: a sparse list of words into the table and its block-grouped copy;
+// launch_cand_narrow: K1's masks and counts from F to F' in place, after launch_reduce1.
+hipError_t launch_cand_build(const uint64_t* words, const uint32_t* ids,
+                             const unsigned char* nodes, uint32_t stride, uint32_t n_nodes,
+                             uint64_t* out, uint64_t* band, uint64_t* zt, hipStream_t s);
+hipError_t launch_cand_update(const uint32_t* node, const uint64_t* value, uint32_t count,
+                              uint64_t* words, const uint32_t* inv, uint64_t* words_p,
+                              hipStream_t s);
+hipError_t launch_cand_narrow(const CandArgs& a, hipStream_t s);
 
 // ---- yoda_order.hip ----
 // Scratch for the sort: keys[2][P] u64, idx[2][P] u32, then hipcub's temp storage.

@@ -549,6 +549,23 @@ struct PermTable {
   uint32_t n;
 };
 
+// Candidate classes (include/yoda.h yoda_set_candidates): what the narrowing pass reads and
+// narrows.  words / band follow the run's node order (position n, block n / 64); cls is in the
+// caller's pod order, reached through perm (sorted position -> caller pod; nullptr: unordered).
+struct CandArgs {
+  const uint64_t* words;  // [n_nodes] bit c: the node is a candidate of class c
+  const uint64_t* band;   // [blocks] the AND of the block's words
+  const uint64_t* zt;     // [blocks] bit j: node 64 b + j has TotalMemorySum == 0
+  const uint8_t* cls;     // [caller pods] class, or 0xFF (YODA_CAND_ANY); nullptr: all 0xFF
+  const uint32_t* perm;
+  uint32_t n_nodes, n_work;
+  uint64_t* bm;           // the masks, dense or sparse (bs != nullptr), as MaskSrc
+  BlockMask* bs;
+  uint64_t* blk;
+  uint32_t bm_stride, bs_stride, blk_stride;
+  uint32_t* counts;       // [2][n_work]
+};
+
 // selectHost draw (include/yoda.h yoda_set_tie_draw): the draw word of (seed, pod, node) and the
 // 64-bit key (word << 32 | node) whose MIN over a pod's tie set is its pick.  mix64: the
 // splitmix64 finalizer; fmix32: the murmur3 32-bit finalizer (a bijection of the u32, so for

@@ -352,6 +352,57 @@ func (g *Handle) SetNodePresent(idx []uint32, present []uint8) error {
 	return check(g.h, rc, "yoda_set_node_present")
 }
 
+// CandAny is the class byte of an unrestricted pod (YODA_CAND_ANY): every node is a candidate.
+const CandAny uint8 = 0xFF
+
+// SetCandidates hands the batch path the other plugins' Filter results as candidate classes
+// (yoda_set_candidates): words[i] is node i's 64-bit word, bit c set when the node is a
+// candidate for class c; nClasses 1..64.  nClasses 0 turns candidates off (words may be nil), as
+// UploadNodes does.  The PreScore maxima do not move -- CollectMaxValues never sees another
+// plugin's Filter -- while Filter, the counts, NormalizeScore and the picks follow the
+// candidates.  While on, Mode B, greedy, shard and communicator calls return an error that
+// wraps YODA_ERR_STATE.
+func (g *Handle) SetCandidates(nClasses uint32, words []uint64) error {
+	var p *C.uint64_t
+	if len(words) > 0 {
+		p = (*C.uint64_t)(unsafe.Pointer(&words[0]))
+	}
+	return check(g.h, C.yoda_set_candidates(g.h, C.uint32_t(nClasses), p), "yoda_set_candidates")
+}
+
+// UpdateCandidates replaces the candidate words of a few nodes (yoda_update_candidates); idx
+// are GLOBAL node ids (the snapshot position plus the handle's node offset; ids outside the
+// handle's shard are ignored), a repeated one keeps its last word.  Cordoning a node is word 0.
+func (g *Handle) UpdateCandidates(idx []uint32, words []uint64) error {
+	if len(idx) != len(words) {
+		return errors.New("yodagpu: UpdateCandidates arrays differ in length")
+	}
+	if len(idx) == 0 {
+		return nil
+	}
+	rc := C.yoda_update_candidates(g.h, C.uint32_t(len(idx)), (*C.uint32_t)(unsafe.Pointer(&idx[0])),
+		(*C.uint64_t)(unsafe.Pointer(&words[0])))
+	return check(g.h, rc, "yoda_update_candidates")
+}
+
+// SetPodClasses sets the class byte of every pod of the batches run from now on
+// (yoda_set_pod_classes): below nClasses, or CandAny.  nil makes every pod CandAny again.
+func (g *Handle) SetPodClasses(cls []uint8) error {
+	var p *C.uint8_t
+	if len(cls) > 0 {
+		p = (*C.uint8_t)(unsafe.Pointer(&cls[0]))
+	}
+	return check(g.h, C.yoda_set_pod_classes(g.h, C.uint32_t(len(cls)), p), "yoda_set_pod_classes")
+}
+
+// CandidatesInfo reports {nClasses (0: off), length of the class array, nodes that are not a
+// candidate of every class} (yoda_candidates_info; host only).
+func (g *Handle) CandidatesInfo() ([3]uint32, error) {
+	var out [3]uint32
+	rc := C.yoda_candidates_info(g.h, (*C.uint32_t)(unsafe.Pointer(&out[0])))
+	return out, check(g.h, rc, "yoda_candidates_info")
+}
+
 // packPods parses the scv/* labels and the diskIO annotation with the reference's own
 // helpers (filter.go:60-74, sort.go:12-18, algorithm.go:103-104) into the C-side
 // yoda_pod_soa arrays.

@@ -85,6 +85,11 @@ _SIGS = {
     "yoda_update_node_cards": ([_vp, _u32, _vp, _u32, _vp, _vp, _vp], C.c_int),
     "yoda_set_node_present": ([_vp, _u32, _vp, _vp], C.c_int),
     "yoda_nodes_absent": ([_vp, C.POINTER(C.c_uint32)], C.c_int),
+    "yoda_set_candidates": ([_vp, _u32, _vp], C.c_int),
+    "yoda_update_candidates": ([_vp, _u32, _vp, _vp], C.c_int),
+    "yoda_set_pod_classes": ([_vp, _u32, _vp], C.c_int),
+    "yoda_candidates_info": ([_vp, _vp], C.c_int),
+    "yoda_candidates_profile": ([_vp, C.POINTER(C.c_double)], C.c_int),
     "yoda_snapshot_check": ([_vp, _vp, _vp], C.c_int),
     "yoda_shard_topk": ([_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp], C.c_int),
     "yoda_shard_topk_depth": ([_vp], C.c_int),
@@ -509,6 +514,51 @@ class Yoda:
         k = C.c_uint32(0)
         self._check(lib().yoda_nodes_absent(self._h, C.byref(k)), "yoda_nodes_absent")
         return int(k.value)
+
+    def set_candidates(self, words, n_classes):
+        """Other plugins' Filter results as candidate classes (yoda_set_candidates): `words` holds
+        one uint64 per node of this handle, bit c set when the node is a candidate for class c;
+        n_classes 1..64.  n_classes 0 (words may be None) turns candidates off, as upload_nodes
+        does.  The PreScore maxima do not move; Filter, counts, scores and picks follow the
+        candidates.  While on, Mode B, greedy, shard and comm calls raise YODA_ERR_STATE."""
+        w = None if words is None else np.ascontiguousarray(words, np.uint64).ravel()
+        if w is not None and n_classes and w.size != self.n_nodes:
+            raise ValueError("set_candidates: one word per node of this handle")
+        self._check(lib().yoda_set_candidates(self._h, int(n_classes),
+                                              None if w is None else _np_ptr(w)),
+                    "yoda_set_candidates")
+
+    def update_candidates(self, ids, words):
+        """Replace the candidate words of the listed GLOBAL node ids (others ignored; a repeated
+        id keeps its last word), no re-upload (yoda_update_candidates).  A cordon is word 0."""
+        n = np.ascontiguousarray(ids, np.uint32).ravel()
+        w = np.ascontiguousarray(words, np.uint64).ravel()
+        if w.size != n.size:
+            raise ValueError("update_candidates: ids and words differ in length")
+        self._check(lib().yoda_update_candidates(self._h, n.size, _np_ptr(n), _np_ptr(w)),
+                    "yoda_update_candidates")
+
+    def set_pod_classes(self, cls):
+        """The class byte of every pod of the batches run from now on (yoda_set_pod_classes):
+        below n_classes, or CAND_ANY (0xFF) for an unrestricted pod.  None: every pod CAND_ANY."""
+        c = None if cls is None else np.ascontiguousarray(cls, np.uint8).ravel()
+        self._check(lib().yoda_set_pod_classes(self._h, 0 if c is None else c.size,
+                                               None if c is None else _np_ptr(c)),
+                    "yoda_set_pod_classes")
+
+    def candidates_info(self):
+        """(n_classes or 0 when off, length of the class array, nodes that are not a candidate
+        of every class) -- yoda_candidates_info; host only."""
+        out = np.zeros(3, np.uint32)
+        self._check(lib().yoda_candidates_info(self._h, _np_ptr(out)), "yoda_candidates_info")
+        return tuple(int(v) for v in out)
+
+    def candidates_profile(self) -> float:
+        """The narrowing pass's HIP-event time (ms) over the runs read by profile_read since the
+        last call (yoda_candidates_profile)."""
+        ms = C.c_double(0)
+        self._check(lib().yoda_candidates_profile(self._h, C.byref(ms)), "yoda_candidates_profile")
+        return ms.value
 
     def snapshot_check(self):
         """(digest [8] u64, mismatch [4] u32) of yoda_snapshot_check (diagnostic; synchronizes)."""
