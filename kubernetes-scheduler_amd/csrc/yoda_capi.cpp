@@ -29,6 +29,7 @@
 #include "yoda_layout.h"
 #include "yoda_launch.h"
 #include "yoda_node_pack.h"
+#include "yoda_greedy_session.h"
 
 
 using namespace yoda;
@@ -473,16 +474,6 @@ int pow2_cards(uint32_t kmax) {
   return k;
 }
 
-// CalculateAllocateScore + CalculateActualScore (algorithm.go:293-310), uint64 wrap.
-// zero_total: TotalMemorySum == 0, where the reference divides by zero.
-uint64_t static_score(uint64_t free_sum, uint64_t total_sum, uint64_t alloc, bool* zero_total) {
-  *zero_total = total_sum == 0;
-  if (total_sum == 0) return 0;
-  const uint64_t allocate = total_sum < alloc ? 0 : (total_sum - alloc) * 100u / total_sum * 3u;
-  const uint64_t actual = (free_sum * 100u / total_sum) * 2u;
-  return allocate + actual;
-}
-
 // Node chunking of one kernel: C chunks x ceil(P/256) pod blocks = B workgroups.  B is sized
 // to ~8 full "rounds" of the kernel's resident capacity (occupancy API), so the last round is
 // nearly full (efficiency >= 1 - pod_blocks / (8 cap)) and chunks stay small enough to
@@ -589,19 +580,6 @@ class HostPool {
   std::atomic<bool> stop_{false};
 };
 
-// Tuning knobs of the A/B harness (tools/ab_lib.sh).  Only the A/B build reads them from
-// the environment (`make ab` -> libyoda_ab.so, -DYODA_AB_KNOBS); in the release library
-// YODA_KNOB(name, default) is the default itself and the name is not even in the binary, so
-// a scheduler process's environment cannot change kernel choice, chunking or greedy policy.
-#ifdef YODA_AB_KNOBS
-static uint32_t knob_env(const char* name, uint32_t dflt) {
-  const char* s = std::getenv(name);
-  return (s && *s) ? (uint32_t)std::strtoul(s, nullptr, 10) : dflt;
-}
-#define YODA_KNOB(name, dflt) knob_env(name, dflt)
-#else
-#define YODA_KNOB(name, dflt) ((uint32_t)(dflt))
-#endif
 uint32_t pool_spin_us() {
   // how long a HostPool worker spins for the next batch before parking (YODA_POOL_SPIN_US,
   // A/B knob; 0 parks at once).  1 ms covers a batch-to-batch gap of the e2e loop (~0.9 ms);
@@ -3488,73 +3466,66 @@ int yoda_profile_read(yoda_t* h, double* k1_ms, double* k2_ms, uint32_t* n_launc
 
 namespace {
 
-// Device-side node state for the greedy resolve: the static score (Allocate + Actual) and
-// CardNumber of the nodes picked so far, pushed in small batches (k_set_static).
-struct GreedyState {
-  yoda_t* h;
-  std::vector<uint64_t> alloc, card_number, stat;    // current, per node
-  std::vector<uint64_t> stat_w;                       // static at window start
-  std::vector<uint8_t> touched_w, dirty;
-  std::vector<uint32_t> touched_list, dirty_list;
+// A static score as the record header holds it: f64 bits on the fast paths.
+uint64_t stat_bits(const yoda_t* h, uint64_t s) {
+  if (h->generic) return s;
+  const double d = (double)s;
+  uint64_t b;
+  std::memcpy(&b, &d, 8);
+  return b;
+}
 
-  uint64_t stat_bits(uint64_t v) const {  // header word: f64 bits on the fast paths
-    if (h->generic) return v;
-    const double d = (double)v;
-    uint64_t b;
-    std::memcpy(&b, &d, 8);
-    return b;
+// The one node-state push: the static score (Allocate + Actual) and CardNumber of `cnt` LOCAL
+// nodes (each at most once) go to the device (k_set_static).
+// The host copies are the caller's business: yoda_set_node_state keeps them current, the greedy
+// batch on one handle restores the device at its end instead.
+// mapped: k_set_static reads the pinned staging pages itself, else a device copy of them.  The
+// greedy batch's pushes are mapped: a few nodes, and the host waits for the kernel behind them,
+// so the copy's own launch is what counts (config 5 with them copied: flags 0 0.248 -> 0.252 s,
+// capacity 0.932 -> 0.943 s).  yoda_set_node_state's are copied: lists of any size, read over the
+// link one entry per thread (14.6 vs 17.6 us a call at 256 entries, equal from 4096 on;
+// profiles/greedy_session/ab.txt).
+int push_node_state(yoda_t* h, uint32_t cnt, const uint32_t* loc, const uint64_t* stat,
+                    const uint64_t* card_number, bool mapped) {
+  if (cnt == 0) return YODA_OK;
+  // one pinned staging copy: [node u32 x cnt | pad | static u64 x cnt | CardNumber u64 x cnt]
+  const size_t o_val = ((size_t)cnt * 4 + 15) / 16 * 16, o_cn = o_val + (size_t)cnt * 8;
+  const size_t bytes = o_cn + (size_t)cnt * 8;
+  if (h->upd_pending) HIP_TRY(h, hipEventSynchronize(h->upd_event));
+  HIP_TRY(h, h->upd_stage.ensure(bytes));
+  unsigned char* st = static_cast<unsigned char*>(h->upd_stage.p);
+  uint32_t* nd = reinterpret_cast<uint32_t*>(st);
+  uint64_t* val = reinterpret_cast<uint64_t*>(st + o_val);
+  uint64_t* cn = reinterpret_cast<uint64_t*>(st + o_cn);
+  h->blksum_loose = true;  // (the atomics keep the block bounds valid, not tight)
+  for (uint32_t t = 0; t < cnt; ++t) {
+    nd[t] = loc[t];
+    val[t] = stat_bits(h, stat[t]);
+    cn[t] = card_number[t];
+    h->note_static(loc[t], stat[t]);  // the K2 block bounds stay valid while scores only fall
   }
-  void touch(uint32_t n) {
-    if (!touched_w[n]) {
-      touched_w[n] = 1;
-      stat_w[n] = stat[n];
-      touched_list.push_back(n);
-    }
-    if (!dirty[n]) {
-      dirty[n] = 1;
-      dirty_list.push_back(n);
-    }
-  }
-  int push(std::vector<uint32_t>& list, std::vector<uint8_t>* marks) {
-    if (list.empty()) return YODA_OK;
-    // one pinned staging copy: [node u32 x cnt | pad | static u64 x cnt | CardNumber u64 x cnt]
-    const uint32_t cnt = (uint32_t)list.size();
-    const size_t o_val = ((size_t)cnt * 4 + 15) / 16 * 16, o_cn = o_val + (size_t)cnt * 8;
-    const size_t bytes = o_cn + (size_t)cnt * 8;
-    if (h->upd_pending) HIP_TRY(h, hipEventSynchronize(h->upd_event));
-    HIP_TRY(h, h->upd_stage.ensure(bytes));
-    unsigned char* st = static_cast<unsigned char*>(h->upd_stage.p);
-    uint32_t* nd = reinterpret_cast<uint32_t*>(st);
-    uint64_t* val = reinterpret_cast<uint64_t*>(st + o_val);
-    uint64_t* cn = reinterpret_cast<uint64_t*>(st + o_cn);
-    for (uint32_t i = 0; i < cnt; ++i) {
-      nd[i] = list[i];
-      val[i] = stat_bits(stat[list[i]]);
-      cn[i] = card_number[list[i]];
-    }
-    // k_set_static reads the (mapped) staging pages itself: no copy; the event marks the
-    // end of that read, before which the pages are not rewritten
-    const unsigned char* d = static_cast<const unsigned char*>(h->upd_stage.dp);
-    const uint32_t stride = h->path == Path::N32 ? n32_stride(h->K) : node_stride(h->K);
-    h->blksum_loose = true;  // (the atomics keep the block bounds valid, not tight)
-    for (uint32_t i = 0; i < cnt; ++i) h->note_static(list[i], stat[list[i]]);
-    HIP_TRY(h, launch_set_static(h->nodes.as<unsigned char>(), stride,
-                                 reinterpret_cast<const uint32_t*>(d),
-                                 reinterpret_cast<const uint64_t*>(d + o_val),
-                                 reinterpret_cast<const uint64_t*>(d + o_cn), cnt,
-                                 h->has_k1sum ? h->k1sum.as<unsigned char>() : nullptr,
-                                 k1sum_stride(h->K),
-                                 h->has_k2sum ? h->k2sum.as<unsigned char>() : nullptr,
-                                 k2sum_stride(h->K), h->perm_copy(), h->stream));
+  // the event marks the end of the staging pages' read (by the copy, or by the kernel itself),
+  // before which they are not rewritten
+  const unsigned char* d = static_cast<const unsigned char*>(h->upd_stage.dp);
+  if (!mapped) {
+    HIP_TRY(h, h->upd_node.ensure(bytes));
+    HIP_TRY(h, hipMemcpyAsync(h->upd_node.p, st, bytes, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipEventRecord(h->upd_event, h->stream));
-    h->upd_pending = true;
-    if (marks)
-      for (uint32_t n : list) (*marks)[n] = 0;
-    list.clear();
-    return YODA_OK;
+    d = h->upd_node.as<unsigned char>();
   }
-  int push_dirty() { return push(dirty_list, &dirty); }
-};
+  const uint32_t stride = h->path == Path::N32 ? n32_stride(h->K) : node_stride(h->K);
+  HIP_TRY(h, launch_set_static(h->nodes.as<unsigned char>(), stride,
+                               reinterpret_cast<const uint32_t*>(d),
+                               reinterpret_cast<const uint64_t*>(d + o_val),
+                               reinterpret_cast<const uint64_t*>(d + o_cn), cnt,
+                               h->has_k1sum ? h->k1sum.as<unsigned char>() : nullptr,
+                               k1sum_stride(h->K),
+                               h->has_k2sum ? h->k2sum.as<unsigned char>() : nullptr,
+                               k2sum_stride(h->K), h->perm_copy(), h->stream));
+  if (mapped) HIP_TRY(h, hipEventRecord(h->upd_event, h->stream));
+  h->upd_pending = true;
+  return YODA_OK;
+}
 
 // A pod SoA holding the pods `idx` of `src` (in that order).
 struct PodGather {
@@ -3585,32 +3556,6 @@ struct PodGather {
   }
 };
 
-// Queue order (sort.go:8-10): scv/priority descending, then input index.  A counting sort
-// when the priorities span < 2^16 values (the usual small integers), else a stable sort.
-void queue_order(const int64_t* prio, uint32_t P, std::vector<uint32_t>& order) {
-  order.resize(P);
-  if (!prio || P == 0) {
-    for (uint32_t i = 0; i < P; ++i) order[i] = i;
-    return;
-  }
-  int64_t lo = prio[0], hi = prio[0];
-  for (uint32_t i = 1; i < P; ++i) {
-    lo = std::min(lo, prio[i]);
-    hi = std::max(hi, prio[i]);
-  }
-  if ((uint64_t)hi - (uint64_t)lo < (1u << 16)) {
-    const uint32_t R = (uint32_t)((uint64_t)hi - (uint64_t)lo) + 1;
-    std::vector<uint32_t> start(R + 1, 0);
-    for (uint32_t i = 0; i < P; ++i) ++start[(uint32_t)((uint64_t)hi - (uint64_t)prio[i]) + 1];
-    for (uint32_t r = 0; r < R; ++r) start[r + 1] += start[r];
-    for (uint32_t i = 0; i < P; ++i) order[start[(uint32_t)((uint64_t)hi - (uint64_t)prio[i])]++] = i;
-    return;
-  }
-  for (uint32_t i = 0; i < P; ++i) order[i] = i;
-  std::stable_sort(order.begin(), order.end(),
-                   [prio](uint32_t a, uint32_t b) { return prio[a] > prio[b]; });
-}
-
 // 6144 pods: larger windows cost fewer, longer GPU windows but more exact fallbacks (touched
 // nodes invalidate more candidate lists); profiles/r02/final/greedy_window_ab.txt
 constexpr uint32_t kGreedyWindow = 6144;
@@ -3623,12 +3568,11 @@ uint32_t greedy_window() {
   return w;
 }
 
-// Exact evaluation of ONE pod against the current device state (pushes pending updates).
-int greedy_eval_one(GreedyState& g, const yoda_pod_soa* pods, uint32_t p, int mode,
+// Exact evaluation of ONE pod against the current device state (the caller has pushed the
+// pending node updates).
+int greedy_eval_one(yoda_t* h, const yoda_pod_soa* pods, uint32_t p, int mode,
                     int32_t* pick_out) {
-  yoda_t* h = g.h;
-  int rc = g.push_dirty();
-  if (rc) return rc;
+  int rc;
   PodGather one;
   one.build(pods, &p, 1);
   if ((rc = yoda_upload_pods(h, &one.soa))) return rc;
@@ -3642,11 +3586,8 @@ int greedy_eval_one(GreedyState& g, const yoda_pod_soa* pods, uint32_t p, int mo
 
 // Exact evaluation of the window pod at sorted position s against the current node state,
 // reusing the window's feasibility bits and maxima (only static scores change inside a
-// window, and push_dirty makes them current): one launch + an 4-byte copy.
-int greedy_eval_fast(GreedyState& g, uint32_t s, int32_t* pick_out) {
-  yoda_t* h = g.h;
-  int rc = g.push_dirty();
-  if (rc) return rc;
+// window, and the caller's push has made them current): one launch + an 4-byte copy.
+int greedy_eval_fast(yoda_t* h, uint32_t s, int32_t* pick_out) {
   const uint32_t nb = greedy_one_blocks();
   if (h->g1_done.bytes == 0) {
     HIP_TRY(h, h->g1_done.ensure(16));
@@ -3696,7 +3637,8 @@ int greedy_eval_fast(GreedyState& g, uint32_t s, int32_t* pick_out) {
 }  // namespace
 
 }  // extern "C"
-static int greedy_capacity(yoda_t* h, const yoda_pod_soa* pods, int32_t* pick);
+static int greedy_batch(yoda_t* h, const yoda_pod_soa* pods, int mode, uint32_t flags,
+                        int32_t* pick);
 extern "C" {
 
 int yoda_greedy(yoda_t* h, const yoda_pod_soa* pods, int mode, uint32_t flags, int32_t* pick) {
@@ -3708,276 +3650,28 @@ int yoda_greedy(yoda_t* h, const yoda_pod_soa* pods, int mode, uint32_t flags, i
   try {
     HIP_TRY(h, hipSetDevice(h->device));
     GreedyScope scope(h);
-    const uint32_t P = pods->n_pods, N = h->n_nodes;
+    const uint32_t P = pods->n_pods;
     h->greedy_windows = 0;
     h->greedy_fallbacks = 0;
     h->greedy_restarts = 0;
     h->greedy_refreshes = 0;
     h->greedy_window_ms = h->greedy_fallback_ms = h->greedy_resolve_ms = 0;
     h->greedy_prep_ms = 0;
-    using Clock = std::chrono::steady_clock;
-    auto ms_since = [](Clock::time_point t0) {
-      return std::chrono::duration<double, std::milli>(Clock::now() - t0).count();
-    };
     if (P == 0) return YODA_OK;
+    if (mode != YODA_MODE_DISKIO) return greedy_batch(h, pods, mode, flags, pick);
+    // Mode B reads no assumed-pod state: independent cycles, in queue order (sort.Less,
+    // sort.go:8-10 -- scv/priority descending, then input index)
     int rc;
-    // Queue order: sort.Less (sort.go:8-10) -- scv/priority descending, then input index.
     std::vector<uint32_t> order;
     queue_order(pods->priority, P, order);
-    if (mode == YODA_MODE_DISKIO) {  // Mode B reads no assumed-pod state: independent cycles
-      PodGather all;
-      all.build(pods, order.data(), P);
-      if ((rc = yoda_upload_pods(h, &all.soa)) || (rc = run_private(h, mode, 0, false)))
-        return rc;
-      std::vector<int32_t> pk(P);
-      // the handle's stream may be non-blocking: copy and wait on it, not on the null stream
-      HIP_TRY(h, hipMemcpyAsync(pk.data(), h->pick.p, P * 4ull, hipMemcpyDeviceToHost, h->stream));
-      HIP_TRY(h, hipStreamSynchronize(h->stream));
-      for (uint32_t i = 0; i < P; ++i) pick[order[i]] = pk[i];
-      return YODA_OK;
-    }
-    if ((flags & YODA_GREEDY_CARD_CAPACITY) && !h->generic) return greedy_capacity(h, pods, pick);
-    GreedyState g;
-    g.h = h;
-    g.alloc = h->h_alloc;
-    g.card_number = h->h_card_number;
-    g.stat.resize(N);
-    g.stat_w.resize(N);
-    g.touched_w.assign(N, 0);
-    g.dirty.assign(N, 0);
-    for (uint32_t n = 0; n < N; ++n) {
-      bool z;
-      g.stat[n] = static_score(h->h_free_sum[n], h->h_total_sum[n], g.alloc[n], &z);
-    }
-    const std::vector<uint64_t> stat0 = g.stat;
-    std::vector<uint32_t> all_touched;
-    std::vector<uint8_t> ever(N, 0);
-    auto apply_pick = [&](uint32_t p, int32_t node) {
-      if (node < 0) return;
-      const uint32_t n = (uint32_t)node - h->node_offset;
-      g.touch(n);  // snapshots the window-start static before it changes
-      if (pods->has_memory[p]) g.alloc[n] += pods->memory[p];  // uint64 wrap (algorithm.go:301)
-      if (flags & YODA_GREEDY_CARD_CAPACITY) {
-        const uint64_t num = pods->has_number[p] ? pods->number[p] : 1;
-        g.card_number[n] = g.card_number[n] >= num ? g.card_number[n] - num : 0;
-      }
-      bool z;
-      g.stat[n] = static_score(h->h_free_sum[n], h->h_total_sum[n], g.alloc[n], &z);
-      if (!ever[n]) {
-        ever[n] = 1;
-        all_touched.push_back(n);
-      }
-    };
-    const bool exact_seq = (flags & YODA_GREEDY_CARD_CAPACITY) || h->generic;
-    if (exact_seq) {
-      // Feasibility (CardNumber) or the U64 normalize check can change after every pick:
-      // evaluate each pod exactly against the current state.
-      for (uint32_t i = 0; i < P; ++i) {
-        const uint32_t p = order[i];
-        int32_t pk = -1;
-        if ((rc = greedy_eval_one(g, pods, p, mode, &pk))) return rc;
-        pick[p] = pk;
-        apply_pick(p, pk);
-        ++h->greedy_fallbacks;
-      }
-    } else {
-      // Windowed top-k + certified sequential resolve (greedy).  Within a
-      // window only the Allocate term of picked nodes changes, and it never increases
-      // (unless alloc wraps around 2^64: then the rest of the window is evaluated exactly).
-      // YODA_GREEDY_TOPK=16 (A/B knob): the capacity mode's deeper lists for this mode too
-      static const uint32_t kt_env = YODA_KNOB("YODA_GREEDY_TOPK", 0);
-      const uint32_t KT = kt_env == (uint32_t)topk_k_capacity() ? kt_env : (uint32_t)topk_k();
-      // Small windows: the GPU work is the same P x N in total, while fewer nodes are
-      // touched per window, so fewer candidate lists lose certification.
-      const uint32_t W = std::min<uint32_t>(P, greedy_window());
-      PodGather win;
-      std::vector<uint32_t> counts(2 * (size_t)W);
-      std::vector<double> ts((size_t)KT * W);
-      std::vector<uint32_t> ti((size_t)KT * W);
-      std::vector<uint32_t> perm(W), pos(W), Tidx, ti2;
-      std::vector<double> Tw, ts2;
-      for (uint32_t ws = 0; ws < P; ws += W) {
-        const uint32_t wn = std::min(W, P - ws);
-        const auto tw = Clock::now();
-        if ((rc = g.push_dirty())) return rc;
-        for (uint32_t n : g.touched_list) g.touched_w[n] = 0;
-        g.touched_list.clear();
-        win.build(pods, order.data() + ws, wn);
-        if ((rc = yoda_upload_pods(h, &win.soa))) return rc;
-        if ((rc = prepare_run(h, YODA_MODE_SCV))) return rc;
-        // sort the window like any batch (whole waves skip nodes); outputs stay in sorted
-        // order and are read through pos[i] = sorted position of window pod i
-        if ((rc = order_pods(h, YODA_MODE_SCV))) return rc;
-        h->greedy_prep_ms += ms_since(tw);
-        if (N > 0) {
-          if ((rc = phase1(h, YODA_MODE_SCV, h->maxima.as<uint64_t>(), h->counts.as<uint32_t>(),
-                           Maxima::Own)))
-            return rc;
-          HIP_TRY(h, launch_prep2(h->maxima.as<uint64_t>(), wn, h->rcp.as<double>(),
-                                   h->stream));
-          if ((rc = topk_lists(h, wn, KT, h->counts.as<uint32_t>()))) return rc;
-          HIP_TRY(h, hipMemcpyAsync(counts.data(), h->counts.p, 2ull * wn * 4,
-                                    hipMemcpyDeviceToHost, h->stream));
-          HIP_TRY(h, hipMemcpyAsync(ts.data(), h->tk_s.p, (size_t)KT * wn * 8,
-                                    hipMemcpyDeviceToHost, h->stream));
-          HIP_TRY(h, hipMemcpyAsync(ti.data(), h->tk_i.p, (size_t)KT * wn * 4,
-                                    hipMemcpyDeviceToHost, h->stream));
-          if (h->ordered)
-            HIP_TRY(h, hipMemcpyAsync(perm.data(), h->perm.p, (size_t)wn * 4,
-                                      hipMemcpyDeviceToHost, h->stream));
-          HIP_TRY(h, hipStreamSynchronize(h->stream));
-        } else {
-          std::fill(counts.begin(), counts.end(), 0u);
-        }
-        for (uint32_t i = 0; i < wn; ++i) pos[i] = i;
-        if (h->ordered)
-          for (uint32_t q = 0; q < wn; ++q) pos[perm[q]] = q;
-        // each list's certificate threshold: its last entry's window-start (or refresh-time)
-        // score and node
-        Tw.resize(wn), Tidx.resize(wn);
-        auto set_thresholds = [&](uint32_t q) {
-          const uint32_t len = std::max<uint32_t>(1, std::min<uint32_t>(counts[q], KT));
-          Tw[q] = ts[(size_t)(len - 1) * wn + q];
-          Tidx[q] = ti[(size_t)(len - 1) * wn + q];
-        };
-        for (uint32_t q = 0; q < wn; ++q) set_thresholds(q);
-        ++h->greedy_windows;
-        h->greedy_window_ms += ms_since(tw);
-        const auto tr = Clock::now();
-        double fb_ms = 0;
-        bool wrapped = false;
-        // the best current candidate of sorted position q (window-start score - old static +
-        // new static) and whether it is certified: every node outside the list scored <= T at
-        // window start (ties: higher index) and its score can only have dropped since
-        auto certify = [&](uint32_t q, uint32_t* best_node) {
-          const uint32_t nf = counts[q];
-          const uint32_t len = std::min<uint32_t>(nf, KT);
-          double bs = -1.0;
-          uint32_t bi = 0xffffffffu;
-          for (uint32_t k = 0; k < len; ++k) {
-            const uint32_t node = ti[(size_t)k * wn + q];
-            const uint32_t n = node - h->node_offset;
-            double cur = ts[(size_t)k * wn + q];
-            if (g.touched_w[n]) cur = cur - (double)g.stat_w[n] + (double)g.stat[n];
-            if (cur > bs || (cur == bs && node < bi)) {
-              bs = cur;
-              bi = node;
-            }
-          }
-          *best_node = bi;
-          return nf <= KT || bs > Tw[q] || (bs == Tw[q] && bi <= Tidx[q]);
-        };
-        // Mid-window list refresh: a window whose lists went stale (similar pods took their
-        // shared top nodes) would otherwise send each of its remaining similar pods to an
-        // exact fallback.  Every kFbCheck (8) fallbacks the next kScan (256) window pods are
-        // checked; if at least kScanMin (16) of them are uncertified already (they stay so:
-        // scores only drop),
-        // the window's top-k K2 runs again against the current state (the window's K1 masks
-        // and maxima stay valid: only static scores change in this mode).  A refreshed entry
-        // is stored as  score + old static - current static  of its node, so the certificate
-        // above yields its current score from then on; the threshold is the refresh-time
-        // score (unlisted nodes scored at most that then and only dropped since).
-        // (YODA_GREEDY_REFRESH_EVERY / _MIN: A/B knobs for the check period and the bar)
-        static const uint32_t kFbCheck =
-            std::max<uint32_t>(1, YODA_KNOB("YODA_GREEDY_REFRESH_EVERY", 8));
-        static const uint32_t kScanMin = YODA_KNOB("YODA_GREEDY_REFRESH_MIN", 16);
-        constexpr uint32_t kScan = 256;
-        uint32_t fb_since = 0;
-        auto maybe_refresh = [&](uint32_t i) -> int {
-          if (wrapped || N == 0 || ++fb_since < kFbCheck || wn - i < 2 * kScan)
-            return YODA_OK;
-          fb_since = 0;
-          uint32_t unc = 0, bj;
-          for (uint32_t j = i + 1; j < std::min(wn, i + 1 + kScan); ++j) {
-            const uint32_t qj = pos[j];
-            if (counts[qj] >= 2 && counts[(size_t)wn + qj] == 0 && !certify(qj, &bj)) ++unc;
-          }
-          if (unc < kScanMin) return YODA_OK;
-          int r = g.push_dirty();
-          if (r) return r;
-          if ((r = topk_lists(h, wn, KT, h->counts.as<uint32_t>()))) return r;
-          ts2.resize((size_t)KT * wn), ti2.resize((size_t)KT * wn);
-          HIP_TRY(h, hipMemcpyAsync(ts2.data(), h->tk_s.p, (size_t)KT * wn * 8,
-                                    hipMemcpyDeviceToHost, h->stream));
-          HIP_TRY(h, hipMemcpyAsync(ti2.data(), h->tk_i.p, (size_t)KT * wn * 4,
-                                    hipMemcpyDeviceToHost, h->stream));
-          HIP_TRY(h, hipStreamSynchronize(h->stream));
-          for (uint32_t j = i; j < wn; ++j) {
-            const uint32_t qj = pos[j];
-            const uint32_t len = std::min<uint32_t>(counts[qj], KT);
-            for (uint32_t k = 0; k < len; ++k) {
-              const size_t o = (size_t)k * wn + qj;
-              const uint32_t n = ti2[o] - h->node_offset;
-              ti[o] = ti2[o];
-              ts[o] = g.touched_w[n] ? ts2[o] + (double)g.stat_w[n] - (double)g.stat[n] : ts2[o];
-            }
-            if (len) {
-              Tw[qj] = ts2[(size_t)(len - 1) * wn + qj];
-              Tidx[qj] = ti2[(size_t)(len - 1) * wn + qj];
-            }
-          }
-          ++h->greedy_refreshes;
-          return YODA_OK;
-        };
-        for (uint32_t i = 0; i < wn; ++i) {
-          const uint32_t p = order[ws + i];
-          const uint32_t q = pos[i];  // sorted position: the device outputs' index
-          const uint32_t nf = counts[q], nz = counts[(size_t)wn + q];
-          int32_t pk;
-          if (nf == 0) {
-            pk = YODA_PICK_NONE;
-          } else if (nf >= 2 && nz > 0) {
-            pk = YODA_PICK_ERROR;  // Score would divide by TotalMemorySum == 0
-          } else if (nf == 1) {
-            pk = (int32_t)ti[q];   // the only feasible node, returned without scoring
-          } else if (wrapped) {
-            const auto tf = Clock::now();
-            if ((rc = greedy_eval_fast(g, q, &pk))) return rc;
-            ++h->greedy_fallbacks;
-            fb_ms += ms_since(tf);
-          } else {
-            uint32_t bi;
-            bool certified = certify(q, &bi);
-            if (!certified) {
-              const auto tf = Clock::now();
-              const uint32_t before = h->greedy_refreshes;
-              if ((rc = maybe_refresh(i))) return rc;
-              if (h->greedy_refreshes != before) certified = certify(q, &bi);
-              if (!certified) {
-                if ((rc = greedy_eval_fast(g, q, &pk))) return rc;
-                ++h->greedy_fallbacks;
-              }
-              fb_ms += ms_since(tf);
-            }
-            if (certified) pk = (int32_t)bi;
-          }
-          pick[p] = pk;
-          if (pk >= 0) {
-            const uint32_t n = (uint32_t)pk - h->node_offset;
-            const uint64_t before = g.alloc[n];
-            apply_pick(p, pk);
-            if (g.alloc[n] < before) wrapped = true;  // Allocate may grow: stop certifying
-          }
-        }
-        h->greedy_fallback_ms += fb_ms;
-        h->greedy_resolve_ms += ms_since(tr) - fb_ms;
-      }
-    }
-    if (std::getenv("YODA_GREEDY_DEBUG"))
-      std::fprintf(stderr, "greedy: windows %u (%.1f ms, of which host prep %.1f ms), fallbacks %u "
-                   "(%.1f ms), resolve %.1f ms\n", h->greedy_windows, h->greedy_window_ms,
-                   h->greedy_prep_ms, h->greedy_fallbacks, h->greedy_fallback_ms,
-                   h->greedy_resolve_ms);
-    if (std::getenv("YODA_GREEDY_DEBUG"))
-      std::fprintf(stderr, "greedy: mid-window list refreshes %u\n", h->greedy_refreshes);
-    // Leave the uploaded snapshot unchanged: restore static score and CardNumber.
-    for (uint32_t n : all_touched) {
-      g.stat[n] = stat0[n];
-      g.card_number[n] = h->h_card_number[n];
-    }
-    if ((rc = g.push(all_touched, nullptr))) return rc;
+    PodGather all;
+    all.build(pods, order.data(), P);
+    if ((rc = yoda_upload_pods(h, &all.soa)) || (rc = run_private(h, mode, 0, false))) return rc;
+    std::vector<int32_t> pk(P);
+    // the handle's stream may be non-blocking: copy and wait on it, not on the null stream
+    HIP_TRY(h, hipMemcpyAsync(pk.data(), h->pick.p, P * 4ull, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->ran = false;
+    for (uint32_t i = 0; i < P; ++i) pick[order[i]] = pk[i];
     return YODA_OK;
   } catch (const std::bad_alloc&) {
     return fail(h, YODA_ERR_INVALID_ARG, "host allocation failed");
@@ -4022,50 +3716,6 @@ int yoda_greedy_stats(const yoda_t* h, uint32_t* windows, uint32_t* fallbacks,
 int yoda_topk_k(void) { return topk_k(); }
 int yoda_topk_k_capacity(void) { return topk_k_capacity(); }
 
-namespace {
-
-// Overwrite the static score (and CardNumber) of a few local nodes on the device.
-int push_node_state(yoda_t* h, const std::vector<uint32_t>& loc, const std::vector<uint64_t>& val,
-                    const std::vector<uint64_t>& cn) {
-  const uint32_t cnt = (uint32_t)loc.size();
-  if (cnt == 0) return YODA_OK;
-  const size_t o_val = ((size_t)cnt * 4 + 15) / 16 * 16, o_cn = o_val + (size_t)cnt * 8;
-  const size_t bytes = o_cn + (size_t)cnt * 8;
-  if (h->upd_pending) HIP_TRY(h, hipEventSynchronize(h->upd_event));
-  HIP_TRY(h, h->upd_stage.ensure(bytes));
-  HIP_TRY(h, h->upd_node.ensure(bytes));
-  unsigned char* st = static_cast<unsigned char*>(h->upd_stage.p);
-  std::memcpy(st, loc.data(), (size_t)cnt * 4);
-  std::memcpy(st + o_val, val.data(), (size_t)cnt * 8);
-  std::memcpy(st + o_cn, cn.data(), (size_t)cnt * 8);
-  HIP_TRY(h, hipMemcpyAsync(h->upd_node.p, st, bytes, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipEventRecord(h->upd_event, h->stream));
-  h->upd_pending = true;
-  unsigned char* d = h->upd_node.as<unsigned char>();
-  const uint32_t stride = h->path == Path::N32 ? n32_stride(h->K) : node_stride(h->K);
-  h->blksum_loose = true;  // (the atomics keep the block bounds valid, not tight)
-  for (uint32_t t = 0; t < cnt; ++t) {  // the K2 block bounds stay valid while scores only fall
-    uint64_t sv = val[t];
-    if (!h->generic) {
-      double d;
-      std::memcpy(&d, &val[t], 8);
-      sv = (uint64_t)d;
-    }
-    h->note_static(loc[t], sv);
-  }
-  HIP_TRY(h, launch_set_static(h->nodes.as<unsigned char>(), stride,
-                               reinterpret_cast<const uint32_t*>(d),
-                               reinterpret_cast<const uint64_t*>(d + o_val),
-                               reinterpret_cast<const uint64_t*>(d + o_cn), cnt,
-                               h->has_k1sum ? h->k1sum.as<unsigned char>() : nullptr,
-                               k1sum_stride(h->K),
-                               h->has_k2sum ? h->k2sum.as<unsigned char>() : nullptr,
-                               k2sum_stride(h->K), h->perm_copy(), h->stream));
-  return YODA_OK;
-}
-
-}  // namespace
-
 int yoda_set_node_state(yoda_t* h, uint32_t count, const uint32_t* nodes, const uint64_t* alloc,
                         const uint64_t* card_number) {
   if (!h) return YODA_ERR_INVALID_ARG;
@@ -4079,7 +3729,7 @@ int yoda_set_node_state(yoda_t* h, uint32_t count, const uint32_t* nodes, const 
     // while the host copies keep the last.  upd_slot[i] = node i's entry in this list.
     if (h->upd_slot.size() != h->n_nodes) h->upd_slot.assign(h->n_nodes, ~0u);
     std::vector<uint32_t> loc;
-    std::vector<uint64_t> al, val, cn;
+    std::vector<uint64_t> al, st, cn;
     auto forget = [&] { for (uint32_t i : loc) h->upd_slot[i] = ~0u; };
     for (uint32_t t = 0; t < count; ++t) {
       if (nodes[t] < h->node_offset || nodes[t] - h->node_offset >= h->n_nodes) continue;
@@ -4090,21 +3740,16 @@ int yoda_set_node_state(yoda_t* h, uint32_t count, const uint32_t* nodes, const 
         forget();
         return fail(h, YODA_ERR_RANGE, "static score leaves the fast path; re-upload the nodes");
       }
-      uint64_t bits = s;
-      if (!h->generic) {
-        const double d = (double)s;
-        std::memcpy(&bits, &d, 8);
-      }
       uint32_t& slot = h->upd_slot[i];
       if (slot == ~0u) {
         slot = (uint32_t)loc.size();
         loc.push_back(i);
         al.push_back(alloc[t]);
-        val.push_back(bits);
+        st.push_back(s);
         cn.push_back(card_number[t]);
       } else {
         al[slot] = alloc[t];
-        val[slot] = bits;
+        st[slot] = s;
         cn[slot] = card_number[t];
       }
     }
@@ -4116,14 +3761,15 @@ int yoda_set_node_state(yoda_t* h, uint32_t count, const uint32_t* nodes, const 
       h->h_alloc[i] = al[ti];
       h->h_card_number[i] = cn[ti];
       unsigned char* r = h->host_records.data() + (size_t)i * stride;
-      std::memcpy(r, &val[ti], 8);       // header word 0: static score
+      const uint64_t bits = stat_bits(h, st[ti]);
+      std::memcpy(r, &bits, 8);          // header word 0: static score
       std::memcpy(r + 8, &cn[ti], 8);    // header word 1: CardNumber
       if (h->has_k2sum) {
-        h->host_k2sum[sum_index(i, kS2Static, k2sum_stride(h->K))] = (uint32_t)val[ti];
-        h->host_k2sum[sum_index(i, kS2Static + 1, k2sum_stride(h->K))] = (uint32_t)(val[ti] >> 32);
+        h->host_k2sum[sum_index(i, kS2Static, k2sum_stride(h->K))] = (uint32_t)bits;
+        h->host_k2sum[sum_index(i, kS2Static + 1, k2sum_stride(h->K))] = (uint32_t)(bits >> 32);
       }
     }
-    return push_node_state(h, loc, val, cn);
+    return push_node_state(h, (uint32_t)loc.size(), loc.data(), st.data(), cn.data(), false);
   } catch (const std::bad_alloc&) {
     h->upd_slot.clear();  // (rebuilt empty by the next call)
     return fail(h, YODA_ERR_INVALID_ARG, "host allocation failed");
@@ -4997,680 +4643,6 @@ int yoda_shard_best_one(yoda_t* h, uint32_t pod, double* score, int32_t* node) {
 
 }  // extern "C"
 
-// ---- host-side greedy session ---------------------------------------------------------
-// The sequential part of the greedy batch (yoda_greedy's resolve), over the GLOBAL node set,
-// fed with merged candidate lists.  Pure host code: identical on every rank.
-struct yoda_greedy_session {
-  static constexpr uint32_t kCrossQ = 64;  // capacity mode: per-q removal counts up to here
-  uint32_t N = 0, P = 0, flags = 0;
-  std::vector<uint64_t> free_sum, total_sum, alloc, card_number, alloc0, cn0, stat, stat_w;
-  std::vector<uint64_t> cn_w;  // CardNumber of a window-touched node at the window start
-  std::vector<uint8_t> has_memory, has_number, has_clock, touched_w, dirty, ever;
-  std::vector<uint64_t> memory, number, clock;
-  // capacity mode: the nodes' cards (when the snapshot passed them), [N][K] in CardField
-  // order, to tell which lost nodes were witnesses of a pod's maxima
-  uint32_t K = 0;
-  std::vector<uint64_t> cards;  // [N][6][K]
-  std::vector<uint32_t> hmask, rmask;  // healthy / real card bits per node
-  std::vector<uint32_t> order, touched_list, dirty_list, ever_list;
-  std::vector<int32_t> pick;
-  // current window (queue positions [ws, ws + wn)), inputs in window order
-  uint32_t ws = 0, wn = 0, k = 0, next = 0, resolved = 0, assigned = 0, refreshes = 0;
-  bool in_window = false, wrapped = false;
-  // some node's static score rose within the window (never, short of a wrap: Allocate only
-  // grows): a listed node's current score may then exceed its window-start one
-  bool stat_rose = false;
-  std::vector<uint32_t> counts, ti_own;
-  std::vector<double> ts_own;
-  // the window's lists [k][wn]: the session's copies, or (greedy_capacity, gs_begin_window_at)
-  // the caller's staging, valid until the window ends
-  double* ts = nullptr;
-  uint32_t* ti = nullptr;
-  // entry kk of window pod i: [k][wn] (the API's layout), or [wn][k] (row_major: a pod's list
-  // contiguous, as k_window_out writes the capacity windows' staging)
-  bool row_major = false;
-  size_t at(uint32_t i, uint32_t kk) const {
-    return row_major ? (size_t)i * k + kk : (size_t)kk * wn + i;
-  }
-  // each list's certificate threshold (flags 0): its last entry's window-start -- or, after a
-  // mid-window refresh (yoda_gs_refresh), refresh-time -- score and node
-  std::vector<double> Tw;
-  // entries of each list before its first empty one (a deep merge stops where it is no longer
-  // exact, k_topk_merge_deep): the list holds every feasible node only when that is nf
-  std::vector<uint32_t> vlen;
-  std::vector<uint32_t> Tix;
-  // YODA_GREEDY_CARD_CAPACITY (greedy): cross[q] = window-touched nodes whose
-  // CardNumber has dropped from >= q (window start) to < q, i.e. nodes a pod needing q cards
-  // has lost since its candidate list was made; and the window's PreScore maxima with their
-  // witnesses ([6][wn] each, window order), when the caller supplied them.
-  uint32_t cross[kCrossQ + 1] = {};
-  std::vector<uint32_t> cross_list[kCrossQ + 1];  // the nodes counted in cross[q]
-  bool has_wit = false;
-  std::vector<uint64_t> wmax;
-  std::vector<uint32_t> wcnt, wnode;
-
-  void apply(uint32_t p, int32_t node) {
-    if (node < 0) return;
-    const uint32_t n = (uint32_t)node;
-    if (!touched_w[n]) {
-      touched_w[n] = 1;
-      stat_w[n] = stat[n];
-      cn_w[n] = card_number[n];
-      touched_list.push_back(n);
-    }
-    if (!dirty[n]) {
-      dirty[n] = 1;
-      dirty_list.push_back(n);
-    }
-    if (!ever[n]) {
-      ever[n] = 1;
-      ever_list.push_back(n);
-    }
-    const uint64_t before = alloc[n];
-    if (has_memory[p]) alloc[n] += memory[p];  // uint64 wrap (algorithm.go:301)
-    if (alloc[n] < before) wrapped = true;     // Allocate may grow: stop certifying
-    if (flags & YODA_GREEDY_CARD_CAPACITY) {
-      const uint64_t num = has_number[p] ? number[p] : 1;
-      const uint64_t a = card_number[n], b = a >= num ? a - num : 0;
-      card_number[n] = b;
-      // pods needing q in (b, a] cards have just lost this node
-      for (uint64_t q = b + 1; q <= std::min<uint64_t>(a, kCrossQ); ++q) {
-        ++cross[q];
-        cross_list[q].push_back(n);
-      }
-    }
-    bool z;
-    const int64_t before_stat = stat[n];
-    stat[n] = static_score(free_sum[n], total_sum[n], alloc[n], &z);
-    if (stat[n] > before_stat) stat_rose = true;
-  }
-  // PodFitsNumber operand of pod p (filter.go:11-16): the label, or 1 (CardNumber > 0)
-  uint64_t need_cards(uint32_t p) const { return has_number[p] ? number[p] : 1; }
-  // node n was feasible for a pod needing q cards at the window start and is not any more
-  bool removed(uint32_t n, uint64_t q) const {
-    return touched_w[n] && card_number[n] < q && cn_w[n] >= q;
-  }
-  // how many nodes a pod needing q cards has lost in this window (an upper bound on its
-  // feasible nodes lost: a touched node may never have passed its other predicates)
-  uint64_t lost(uint64_t q) const {
-    if (q <= kCrossQ) return cross[q];
-    uint64_t r = 0;
-    for (uint32_t n : touched_list) r += removed(n, q) ? 1 : 0;
-    return r;
-  }
-  // Node n passed pod p's Filter at the window start (it needs q cards; PodFitsNumber held
-  // then, n being a lost node): PodFitsMemory / PodFitsClock (filter.go:18-50) on its cards.
-  bool fit_ws(uint32_t n, uint32_t p, uint64_t q) const {
-    const uint64_t* c = cards.data() + (size_t)n * 6 * K;
-    uint64_t cm = 0, cc = 0;
-    for (uint32_t j = 0; j < K; ++j) {
-      if (!((hmask[n] >> j) & 1u)) continue;
-      cm += c[0 * K + j] >= memory[p];  // kFree
-      cc += c[1 * K + j] == clock[p];   // kClock
-    }
-    return (!has_memory[p] || cm >= q) && (!has_clock[p] || cc >= q);
-  }
-  // Node n's contribution to pod p's maxima (ProcessMaxValueWithCard over the cards with
-  // FreeMemory >= m and Clock >= c, collection.go:46-76), MaxValue field order.
-  // per node (MaxValue order) the largest value over its real cards: no pod's contrib() from
-  // the node exceeds it (scan_lost skips nodes that cannot be a witness)
-  std::vector<uint64_t> nodemax;
-  bool contrib(uint32_t n, uint32_t p, uint64_t v[6]) const {
-    const uint64_t* c = cards.data() + (size_t)n * 6 * K;
-    const uint64_t m = has_memory[p] ? memory[p] : 0, ck = has_clock[p] ? clock[p] : 0;
-    bool any = false;
-    for (int f = 0; f < 6; ++f) v[f] = 0;
-    for (uint32_t j = 0; j < K; ++j) {
-      if (!((rmask[n] >> j) & 1u) || c[0 * K + j] < m || c[1 * K + j] < ck) continue;
-      any = true;
-      // CardField (free, clock, total, bw, core, power) -> MaxValue (bw, clock, core, free,
-      // power, total)
-      v[0] = std::max(v[0], c[3 * K + j]);
-      v[1] = std::max(v[1], c[1 * K + j]);
-      v[2] = std::max(v[2], c[4 * K + j]);
-      v[3] = std::max(v[3], c[0 * K + j]);
-      v[4] = std::max(v[4], c[5 * K + j]);
-      v[5] = std::max(v[5], c[2 * K + j]);
-    }
-    return any;
-  }
-  // The nodes pod p (needing q cards, window pod i) has lost in this window, examined with
-  // the cards at hand: how many had passed its Filter at the window start (lf), how many of
-  // those had TotalMemorySum == 0 (lz), and how many were witnesses of each of its maxima
-  // (lw).  False (nothing computed) without the cards or when too many nodes were lost.
-  static constexpr uint64_t kExactLost = 512;
-  // witness_only: the caller needs lw only (nf0 >= 2 + lq and no zero-total node at the window
-  // start: lf and lz cannot change its outcome) -- and only for the fields whose witnesses lq
-  // lost nodes could all be (wcnt <= lq); a node below every such maximum is skipped unvisited
-  // (lf / lz then count only the visited nodes)
-  bool scan_lost(uint32_t i, uint32_t p, uint64_t q, uint64_t lq, uint64_t* lf, uint64_t* lz,
-                 uint64_t lw[6], bool witness_only = false) const {
-    *lf = *lz = 0;
-    for (int f = 0; f < 6; ++f) lw[f] = 0;
-    if (lq == 0) return true;
-    if (cards.empty() || lq > kExactLost) return false;
-    ++n_scan;
-    uint32_t fmask = 0x3fu;
-    if (witness_only && has_wit) {
-      fmask = 0;
-      for (int f = 0; f < 6; ++f) {
-        const size_t o = (size_t)f * wn + i;
-        if (wmax[o] > 1 && wcnt[o] <= lq) fmask |= 1u << f;
-      }
-      if (fmask == 0) return true;
-    }
-    auto visit = [&](uint32_t x) {
-      if (witness_only && has_wit) {
-        const uint64_t* nm = nodemax.data() + (size_t)x * 6;
-        bool maybe = false;
-        for (int f = 0; f < 6 && !maybe; ++f)
-          maybe = ((fmask >> f) & 1u) && nm[f] >= wmax[(size_t)f * wn + i];
-        if (!maybe) return;
-      }
-      ++n_scan_nodes;
-      if (!fit_ws(x, p, q)) return;
-      ++*lf;
-      *lz += total_sum[x] == 0 ? 1 : 0;
-      uint64_t v[6];
-      if (has_wit && contrib(x, p, v))
-        for (int f = 0; f < 6; ++f) lw[f] += v[f] == wmax[(size_t)f * wn + i] ? 1 : 0;
-    };
-    if (q <= kCrossQ) {
-      for (uint32_t x : cross_list[q]) visit(x);
-    } else {
-      for (uint32_t x : touched_list)
-        if (removed(x, q)) visit(x);
-    }
-    return true;
-  }
-  // CollectMaxValues over the remaining feasible nodes still gives window pod i's maxima:
-  // every field keeps a witness.  A maximum of 1 is the floor and cannot drop
-  // (collection.go:31-38).  Exact: a field keeps its maximum iff fewer of its witnesses were
-  // lost than it had (lw from scan_lost).  Bounds only: more witnesses than lost nodes, or a
-  // single witness that is not lost.
-  bool maxima_kept(uint32_t i, uint64_t q, uint64_t lq, bool exact, const uint64_t lw[6]) const {
-    if (lq == 0) return true;
-    if (!has_wit) return false;
-    for (int f = 0; f < 6; ++f) {
-      const size_t o = (size_t)f * wn + i;
-      if (wmax[o] <= 1) continue;
-      if (exact) {
-        if (wcnt[o] > lw[f]) continue;
-      } else {
-        if (wcnt[o] > lq) continue;
-        if (wcnt[o] == 1 && wnode[o] < N && !removed(wnode[o], q)) continue;
-      }
-      return false;
-    }
-    return true;
-  }
-  // Capacity-mode resolve of window pod i (input pod p): true with *pk when certified.
-  bool resolve_capacity(uint32_t i, uint32_t p, int32_t* pk);
-  // flags 0: window pod i's best current candidate (window-start score - old static + new
-  // static) and whether the list certifies it: every unlisted node scored <= T at the window
-  // start or last refresh (ties: higher index) and its score can only have dropped since
-  bool certify0(uint32_t i, uint32_t* best) const {
-    const uint32_t nf = counts[i], len = std::min<uint32_t>(nf, vlen[i]);
-    double bs = -1.0;
-    uint32_t bi = 0xffffffffu;
-    for (uint32_t kk = 0; kk < len; ++kk) {  // (the listed entries: none empty, every id < N)
-      const uint32_t n = ti[at(i, kk)];
-      double cur = ts[at(i, kk)];
-      if (touched_w[n]) cur = cur - (double)stat_w[n] + (double)stat[n];
-      if (cur > bs || (cur == bs && n < bi)) {
-        bs = cur;
-        bi = n;
-      }
-    }
-    *best = bi;
-    if (bi == 0xffffffffu) return false;  // nothing listed
-    return (nf <= k && vlen[i] >= nf) || bs > Tw[i] || (bs == Tw[i] && bi <= Tix[i]);
-  }
-  // why capacity certificates failed: wrap, few feasible left, zero-total, maxima, list
-  // exhausted, below the threshold
-  uint64_t why[6] = {};
-  // (diagnostics, YODA_GREEDY_DEBUG) capacity resolves, lost-node scans and nodes they visited
-  mutable uint64_t n_resolve = 0, n_scan = 0, n_scan_nodes = 0;
-};
-
-bool yoda_greedy_session::resolve_capacity(uint32_t i, uint32_t p, int32_t* pk) {
-  const uint32_t KT = k;
-  const uint32_t nf0 = counts[i], nz0 = counts[(size_t)wn + i];
-  ++n_resolve;
-  if (nf0 == 0) {  // feasibility only shrinks: still no node
-    *pk = YODA_PICK_NONE;
-    return true;
-  }
-  if (wrapped) return ++why[0], false;
-  const uint64_t q = need_cards(p);
-  const uint32_t len = std::min<uint32_t>(nf0, KT);
-  // the list holds every feasible node of the window start
-  const bool whole = nf0 <= KT && vlen[i] >= nf0;
-  const uint64_t lq = lost(q);
-  uint32_t alive = 0, first = 0xffffffffu, alive_zero = 0;
-  double bs = -1.0;
-  uint32_t bi = 0xffffffffu;
-  // the list's best current candidate; alive / first / alive_zero too on a full scan.  A
-  // partial scan stops at the first entry whose window-start score is below the best so far:
-  // the list is in descending window-start order and a score only falls in a window (deep
-  // lists, k_topk_merge_deep, make the full scan the resolve's main cost)
-  auto scan = [&](bool full) {
-    alive = 0, first = 0xffffffffu, alive_zero = 0;
-    bs = -1.0, bi = 0xffffffffu;
-    for (uint32_t kk = 0; kk < len; ++kk) {
-      const size_t o = at(i, kk);
-      if (!full && ts[o] < bs) break;
-      const uint32_t n = ti[o];
-      if (n >= N || removed(n, q)) continue;
-      ++alive;
-      if (first == 0xffffffffu) first = n;
-      alive_zero += total_sum[n] == 0 ? 1u : 0u;
-      double cur = ts[o];
-      if (touched_w[n]) cur = cur - (double)stat_w[n] + (double)stat[n];
-      if (cur > bs || (cur == bs && n < bi)) {
-        bs = cur;
-        bi = n;
-      }
-    }
-  };
-  const bool full_scan = whole || stat_rose;
-  scan(full_scan);
-  uint64_t lf = 0, lz = 0, lw[6] = {};
-  // The bounds-only certificate first (no card scan): whatever it certifies, the exact one
-  // certifies with the same outcome (nf0 >= 2 + lq leaves >= 2 feasible nodes; a field with
-  // more witnesses than lost nodes, or an unlost single witness, keeps its maximum since
-  // lw[f] <= lq).  The lost nodes' cards are examined only when it fails.
-  bool exact = false;
-  if (!whole && lq > 0 && nf0 >= 2 + lq && nz0 == 0 && bi != 0xffffffffu &&
-      maxima_kept(i, q, lq, false, lw)) {
-    // (falls through to the list certificate below with exact == false)
-  } else {
-    exact = scan_lost(i, p, q, lq, &lf, &lz, lw, nf0 >= 2 + lq && nz0 == 0);
-  }
-  if (whole) {
-    if (alive == 0) {
-      *pk = YODA_PICK_NONE;
-      return true;
-    }
-    if (alive == 1) {  // k8s returns the only feasible node without scoring
-      *pk = (int32_t)first;
-      return true;
-    }
-    if (alive_zero > 0) {  // Score would divide by TotalMemorySum == 0
-      *pk = YODA_PICK_ERROR;
-      return true;
-    }
-  } else if (exact) {
-    // the feasible set is the window start's minus the lost nodes that were in it
-    const uint64_t nf = nf0 - std::min<uint64_t>(nf0, lf);
-    if (nf == 0) {
-      *pk = YODA_PICK_NONE;
-      return true;
-    }
-    if (nf == 1) {  // the only feasible node: listed and alive, or somewhere unlisted
-      if (!full_scan) scan(true);
-      if (alive != 1) return ++why[1], false;
-      *pk = (int32_t)first;
-      return true;
-    }
-    if (nz0 > lz) {  // a feasible zero-total node remains
-      *pk = YODA_PICK_ERROR;
-      return true;
-    }
-  } else {
-    if (nf0 < 2 + lq) return ++why[1], false;  // might be down to 0 or 1 feasible nodes
-    if (nz0 > 0) {
-      if (lq > 0) return ++why[2], false;      // a zero-total node may be among the lost ones
-      *pk = YODA_PICK_ERROR;
-      return true;
-    }
-  }
-  if (!maxima_kept(i, q, lq, exact, lw)) return ++why[3], false;  // unlisted scores may move
-  if (bi == 0xffffffffu) return ++why[4], false;       // every listed node lost
-  if (!whole) {
-    // every unlisted node scored <= T at the window start or the list's last refresh (ties:
-    // higher index) and has only lost Allocate since, or feasibility
-    if (!(bs > Tw[i] || (bs == Tw[i] && bi <= Tix[i]))) return ++why[5], false;
-  }
-  *pk = (int32_t)bi;
-  return true;
-}
-
-extern "C" {
-
-int yoda_gs_create(const yoda_node_soa* nodes, const yoda_pod_soa* pods, uint32_t flags,
-                   yoda_gs_t** out) {
-  if (!out || !nodes || !pods) return YODA_ERR_INVALID_ARG;
-  *out = nullptr;
-  const uint32_t N = nodes->n_nodes, P = pods->n_pods;
-  if (N && (!nodes->free_memory_sum || !nodes->total_memory_sum || !nodes->card_number))
-    return YODA_ERR_INVALID_ARG;
-  if (P && (!pods->has_memory || !pods->memory || !pods->has_number || !pods->number))
-    return YODA_ERR_INVALID_ARG;
-  if (N >= 0x7fffffffu) return YODA_ERR_RANGE;
-  try {
-    yoda_gs_t* g = new yoda_gs_t();
-    g->N = N, g->P = P, g->flags = flags;
-    g->free_sum.assign(nodes->free_memory_sum, nodes->free_memory_sum + N);
-    g->total_sum.assign(nodes->total_memory_sum, nodes->total_memory_sum + N);
-    g->card_number.assign(nodes->card_number, nodes->card_number + N);
-    if (nodes->alloc_memory)
-      g->alloc.assign(nodes->alloc_memory, nodes->alloc_memory + N);
-    else
-      g->alloc.assign(N, 0);
-    g->alloc0 = g->alloc;
-    g->cn0 = g->card_number;
-    g->stat.resize(N);
-    g->stat_w.resize(N);
-    g->cn_w.resize(N);
-    for (uint32_t n = 0; n < N; ++n) {
-      bool z;
-      g->stat[n] = static_score(g->free_sum[n], g->total_sum[n], g->alloc[n], &z);
-    }
-    g->touched_w.assign(N, 0);
-    g->dirty.assign(N, 0);
-    g->ever.assign(N, 0);
-    g->has_memory.assign(pods->has_memory, pods->has_memory + P);
-    g->memory.assign(pods->memory, pods->memory + P);
-    g->has_number.assign(pods->has_number, pods->has_number + P);
-    g->number.assign(pods->number, pods->number + P);
-    if (pods->has_clock && pods->clock) {
-      g->has_clock.assign(pods->has_clock, pods->has_clock + P);
-      g->clock.assign(pods->clock, pods->clock + P);
-    } else {
-      g->has_clock.assign(P, 0);
-      g->clock.assign(P, 0);
-    }
-    // capacity mode: keep the cards for the exact witness accounting (optional)
-    if ((flags & YODA_GREEDY_CARD_CAPACITY) && N && nodes->max_cards >= 1 &&
-        nodes->max_cards <= YODA_MAX_CARDS && nodes->card_count && nodes->card_free_memory &&
-        nodes->card_total_memory && nodes->card_clock && nodes->card_bandwidth &&
-        nodes->card_core && nodes->card_power && nodes->card_healthy) {
-      const uint32_t K = nodes->max_cards;
-      g->K = K;
-      g->cards.assign((size_t)N * 6 * K, 0);
-      g->hmask.assign(N, 0);
-      g->rmask.assign(N, 0);
-      const uint64_t* src[6] = {nodes->card_free_memory, nodes->card_clock,
-                                nodes->card_total_memory, nodes->card_bandwidth,
-                                nodes->card_core, nodes->card_power};  // CardField order
-      for (uint32_t n = 0; n < N; ++n) {
-        const uint32_t cnt = std::min<uint32_t>(nodes->card_count[n], K);
-        for (uint32_t j = 0; j < cnt; ++j) {
-          const size_t k = (size_t)n * K + j;
-          for (int f = 0; f < 6; ++f) g->cards[((size_t)n * 6 + f) * K + j] = src[f][k];
-          g->rmask[n] |= 1u << j;
-          if (nodes->card_healthy[k]) g->hmask[n] |= 1u << j;
-        }
-      }
-      // each node's largest contribution to any pod's maxima (contrib() over every real card)
-      g->nodemax.assign((size_t)N * 6, 0);
-      for (uint32_t n = 0; n < N; ++n) {
-        uint64_t* v = g->nodemax.data() + (size_t)n * 6;
-        const uint64_t* c = g->cards.data() + (size_t)n * 6 * K;
-        for (uint32_t j = 0; j < K; ++j) {
-          if (!((g->rmask[n] >> j) & 1u)) continue;
-          v[0] = std::max(v[0], c[3 * K + j]);
-          v[1] = std::max(v[1], c[1 * K + j]);
-          v[2] = std::max(v[2], c[4 * K + j]);
-          v[3] = std::max(v[3], c[0 * K + j]);
-          v[4] = std::max(v[4], c[5 * K + j]);
-          v[5] = std::max(v[5], c[2 * K + j]);
-        }
-      }
-    }
-    g->pick.assign(P, YODA_PICK_NONE);
-    // queue order: sort.Less (sort.go:8-10), scv/priority descending, then input index
-    queue_order(pods->priority, P, g->order);
-    *out = g;
-    return YODA_OK;
-  } catch (...) {
-    return YODA_ERR_INVALID_ARG;
-  }
-}
-
-int yoda_gs_destroy(yoda_gs_t* g) {
-  if (!g) return YODA_ERR_INVALID_ARG;
-  delete g;
-  return YODA_OK;
-}
-
-int yoda_gs_queue_order(const yoda_gs_t* g, uint32_t* order) {
-  if (!g || (!order && g->P)) return YODA_ERR_INVALID_ARG;
-  std::copy(g->order.begin(), g->order.end(), order);
-  return YODA_OK;
-}
-
-namespace {
-// yoda_gs_begin_window without copying the lists: the session reads (and, on a refresh,
-// writes) top_score / top_node in place until the window ends (greedy_capacity's staging)
-int gs_begin_window_at(yoda_gs_t* g, uint32_t ws, uint32_t wn, uint32_t k,
-                       const uint32_t* counts, double* top_score, uint32_t* top_node,
-                       bool borrow, bool row_major = false);
-}  // namespace
-
-int yoda_gs_begin_window(yoda_gs_t* g, uint32_t ws, uint32_t wn, uint32_t k,
-                         const uint32_t* counts, const double* top_score,
-                         const uint32_t* top_node) {
-  return gs_begin_window_at(g, ws, wn, k, counts, const_cast<double*>(top_score),
-                            const_cast<uint32_t*>(top_node), false, false);
-}
-
-namespace {
-int gs_begin_window_at(yoda_gs_t* g, uint32_t ws, uint32_t wn, uint32_t k,
-                       const uint32_t* counts, double* top_score, uint32_t* top_node,
-                       bool borrow, bool row_major) {
-  if (row_major && !borrow) return YODA_ERR_INVALID_ARG;
-  if (!g || ws > g->P || wn > g->P - ws || k == 0 || !counts || !top_score || !top_node)
-    return YODA_ERR_INVALID_ARG;
-  if (!borrow)  // (the borrowed lists are libyoda's own kernel output)
-    for (uint32_t i = 0; i < (uint32_t)k * wn; ++i)
-      if (top_node[i] != 0xffffffffu && top_node[i] >= g->N) return YODA_ERR_RANGE;
-  try {
-    for (uint32_t n : g->touched_list) g->touched_w[n] = 0;
-    g->touched_list.clear();
-    g->ws = ws, g->wn = wn, g->k = k, g->next = 0;
-    g->row_major = row_major;
-    g->in_window = true;
-    g->wrapped = false;
-    g->stat_rose = false;
-    std::fill(std::begin(g->cross), std::end(g->cross), 0u);
-    for (auto& l : g->cross_list) l.clear();
-    g->has_wit = false;
-    g->counts.assign(counts, counts + 2 * (size_t)wn);
-    if (borrow) {
-      g->ts = top_score;
-      g->ti = top_node;
-    } else {
-      g->ts_own.assign(top_score, top_score + (size_t)k * wn);
-      g->ti_own.assign(top_node, top_node + (size_t)k * wn);
-      g->ts = g->ts_own.data();
-      g->ti = g->ti_own.data();
-    }
-    g->Tw.resize(wn);
-    g->Tix.resize(wn);
-    g->vlen.resize(wn);
-    for (uint32_t i = 0; i < wn; ++i) {
-      const uint32_t cap = std::min<uint32_t>(counts[i], k);
-      uint32_t v = 0;
-      while (v < cap && top_node[g->at(i, v)] != 0xffffffffu) ++v;
-      g->vlen[i] = v;
-      const uint32_t len = std::max<uint32_t>(1, v);  // (threshold: the last entry listed)
-      g->Tw[i] = top_score[g->at(i, len - 1)];
-      g->Tix[i] = top_node[g->at(i, len - 1)];
-    }
-    return YODA_OK;
-  } catch (...) {
-    return YODA_ERR_INVALID_ARG;
-  }
-}
-}  // namespace
-
-int yoda_gs_set_witness(yoda_gs_t* g, const uint64_t* maxima, const uint32_t* wit_count,
-                        const uint32_t* wit_node) {
-  if (!g || !g->in_window || (g->wn && (!maxima || !wit_count || !wit_node)))
-    return YODA_ERR_INVALID_ARG;
-  try {
-    const size_t n = 6 * (size_t)g->wn;
-    g->wmax.assign(maxima, maxima + n);
-    g->wcnt.assign(wit_count, wit_count + n);
-    g->wnode.assign(wit_node, wit_node + n);
-    g->has_wit = true;
-    return YODA_OK;
-  } catch (...) {
-    return YODA_ERR_INVALID_ARG;
-  }
-}
-
-// Resolve the window in queue order until a pod cannot be certified from its candidate list
-// (greedy): *next = its window index, or wn when the window is done.
-int yoda_gs_resolve(yoda_gs_t* g, uint32_t* next) {
-  if (!g || !next || !g->in_window) return YODA_ERR_INVALID_ARG;
-  const uint32_t wn = g->wn;
-  const bool capacity = (g->flags & YODA_GREEDY_CARD_CAPACITY) != 0;
-  while (g->next < wn) {
-    const uint32_t i = g->next;
-    const uint32_t p = g->order[g->ws + i];
-    const uint32_t nf = g->counts[i], nz = g->counts[(size_t)wn + i];
-    int32_t pk;
-    if (capacity) {
-      if (!g->resolve_capacity(i, p, &pk)) break;
-    } else if (nf == 0) {
-      pk = YODA_PICK_NONE;
-    } else if (nf >= 2 && nz > 0) {
-      pk = YODA_PICK_ERROR;  // Score would divide by TotalMemorySum == 0
-    } else if (nf == 1) {
-      if (g->vlen[i] == 0) break;  // (not listed: the caller evaluates it)
-      pk = (int32_t)g->ti[g->at(i, 0)];  // the only feasible node, returned without scoring
-    } else if (g->wrapped) {
-      break;
-    } else {
-      uint32_t bi;
-      if (!g->certify0(i, &bi)) break;
-      pk = (int32_t)bi;
-    }
-    g->pick[p] = pk;
-    g->apply(p, pk);
-    ++g->next;
-    ++g->resolved;
-  }
-  *next = g->next;
-  return YODA_OK;
-}
-
-uint32_t yoda_greedy_next_window(uint32_t progress, uint32_t wmax) {
-  // the next window holds 130 % of this one's progress, in whole waves: small windows cost
-  // less (K1 / K2 time grows with the pods) and most restart near where the last one did;
-  // profiles/r03/greedy_capacity/grow_ab.txt (1.81-1.91 s with the earlier power of two >=
-  // twice the progress, 1.57-1.64 s at 130 %).  YODA_GREEDY_GROW_PCT: A/B knob
-  static const uint32_t grow = YODA_KNOB("YODA_GREEDY_GROW_PCT", 130);
-  wmax = std::max<uint32_t>(wmax, 1);
-  const uint64_t t = (uint64_t)progress * grow / 100;
-  return (uint32_t)std::min<uint64_t>(wmax, std::max<uint64_t>(64, (t + 63) / 64 * 64));
-}
-
-int yoda_gs_uncertified(const yoda_gs_t* g, uint32_t from, uint32_t scan, uint32_t* count) {
-  if (!g || !count || !g->in_window) return YODA_ERR_INVALID_ARG;
-  if (g->flags & YODA_GREEDY_CARD_CAPACITY) return YODA_ERR_STATE;
-  uint32_t c = 0, bi;
-  // once Allocate has wrapped (alloc < before) no list certifies any more: a refresh cannot
-  // help, so report none (the one rule of yoda_greedy, yoda_comm_greedy and dist.sharded_greedy)
-  if (g->wrapped) {
-    *count = 0;
-    return YODA_OK;
-  }
-  const uint32_t end = (uint32_t)std::min<uint64_t>(g->wn, (uint64_t)from + scan);
-  for (uint32_t i = from; i < end; ++i)
-    if (g->counts[i] >= 2 && g->counts[(size_t)g->wn + i] == 0 && !g->certify0(i, &bi)) ++c;
-  *count = c;
-  return YODA_OK;
-}
-
-int yoda_gs_refresh(yoda_gs_t* g, uint32_t from, const double* top_score,
-                    const uint32_t* top_node) {
-  if (!g || !g->in_window || !top_score || !top_node || from > g->wn) return YODA_ERR_INVALID_ARG;
-  // capacity sessions judge feasibility and maxima against the window start and restart
-  // instead of refreshing (as yoda_gs_uncertified)
-  if (g->flags & YODA_GREEDY_CARD_CAPACITY) return YODA_ERR_STATE;
-  const uint32_t wn = g->wn, k = g->k;
-  // validate every listed node first: a bad id leaves the session unchanged
-  for (uint32_t i = from; i < wn; ++i) {
-    const uint32_t len = std::min<uint32_t>(g->counts[i], k);
-    for (uint32_t kk = 0; kk < len; ++kk)
-      if (top_node[(size_t)kk * wn + i] >= g->N) return YODA_ERR_RANGE;
-  }
-  for (uint32_t i = from; i < wn; ++i) {
-    const uint32_t len = std::min<uint32_t>(g->counts[i], k);
-    for (uint32_t kk = 0; kk < len; ++kk) {
-      const size_t o = (size_t)kk * wn + i;
-      const uint32_t n = top_node[o];
-      // stored so that the certificate's  stored - old static + current static  is its
-      // current score (the refresh scored it with the current static)
-      g->ti[g->at(i, kk)] = n;
-      g->ts[g->at(i, kk)] = g->touched_w[n] ? top_score[o] + (double)g->stat_w[n] - (double)g->stat[n]
-                                 : top_score[o];
-    }
-    g->vlen[i] = len;  // (a refresh's lists are whole: every id validated above)
-    if (len) {
-      g->Tw[i] = top_score[(size_t)(len - 1) * wn + i];
-      g->Tix[i] = top_node[(size_t)(len - 1) * wn + i];
-    }
-  }
-  ++g->refreshes;
-  return YODA_OK;
-}
-
-int yoda_gs_assign(yoda_gs_t* g, uint32_t queue_pos, int32_t pick) {
-  if (!g || queue_pos >= g->P) return YODA_ERR_INVALID_ARG;
-  if (pick >= 0 && (uint32_t)pick >= g->N) return YODA_ERR_RANGE;
-  const uint32_t p = g->order[queue_pos];
-  g->pick[p] = pick;
-  g->apply(p, pick);
-  ++g->assigned;
-  if (g->in_window && queue_pos == g->ws + g->next) ++g->next;
-  return YODA_OK;
-}
-
-int yoda_gs_take_dirty(yoda_gs_t* g, uint32_t cap, uint32_t* nodes, uint64_t* alloc,
-                       uint64_t* card_number, uint32_t* count) {
-  if (!g || !count || (cap && (!nodes || !alloc || !card_number))) return YODA_ERR_INVALID_ARG;
-  const uint32_t n = std::min<uint32_t>(cap, (uint32_t)g->dirty_list.size());
-  for (uint32_t t = 0; t < n; ++t) {
-    const uint32_t v = g->dirty_list[t];
-    nodes[t] = v;
-    alloc[t] = g->alloc[v];
-    card_number[t] = g->card_number[v];
-    g->dirty[v] = 0;
-  }
-  g->dirty_list.erase(g->dirty_list.begin(), g->dirty_list.begin() + n);
-  *count = n;
-  return YODA_OK;
-}
-
-int yoda_gs_touched_original(const yoda_gs_t* g, uint32_t cap, uint32_t* nodes, uint64_t* alloc,
-                             uint64_t* card_number, uint32_t* count) {
-  if (!g || !count || (cap && (!nodes || !alloc || !card_number))) return YODA_ERR_INVALID_ARG;
-  const uint32_t n = std::min<uint32_t>(cap, (uint32_t)g->ever_list.size());
-  for (uint32_t t = 0; t < n; ++t) {
-    const uint32_t v = g->ever_list[t];
-    nodes[t] = v;
-    alloc[t] = g->alloc0[v];
-    card_number[t] = g->cn0[v];
-  }
-  *count = n;
-  return YODA_OK;
-}
-
-int yoda_gs_picks(const yoda_gs_t* g, int32_t* pick, uint32_t* resolved, uint32_t* assigned) {
-  if (!g) return YODA_ERR_INVALID_ARG;
-  if (pick) std::copy(g->pick.begin(), g->pick.end(), pick);
-  if (resolved) *resolved = g->resolved;
-  if (assigned) *assigned = g->assigned;
-  return YODA_OK;
-}
-
-}  // extern "C"
-
 // Pod p of `pods` scheduled exactly against the CURRENT device node state (k_one_*: Filter,
 // CollectMaxValues, Score, then k8s' outcome rules as k_finalize applies them).  Local pick.
 static int greedy_eval_exact(yoda_t* h, const yoda_pod_soa* pods, uint32_t p, int32_t* pick) {
@@ -5719,14 +4691,102 @@ static int greedy_eval_exact(yoda_t* h, const yoda_pod_soa* pods, uint32_t p, in
   return YODA_OK;
 }
 
-// ---- capacity-decrement greedy on one handle -------------------------------------------
-// YODA_GREEDY_CARD_CAPACITY on a fast record path (greedy): windows of pods
-// are evaluated on the device against the state at the window start (k1_witness + top-k
-// K2), then the host session resolves them in queue order with the capacity certificate
-// (yoda_greedy_session::resolve_capacity).  A pod it cannot certify starts the next window,
-// so it is evaluated against the current state; the window size adapts to how far the last
-// window got.  Node ids inside are local; picks are returned global.
-static FILE* greedy_trace_file() {
+// ---- the greedy batch on one handle (yoda_greedy, Mode A) --------------------------------
+// One driver for flags 0, YODA_GREEDY_CARD_CAPACITY and the exact sequence of the U64 record
+// path (greedy).  The sequential part is the host session's
+// (yoda_greedy_session.h), built from the handle's host copies over its LOCAL node ids; the
+// driver evaluates windows of pods on the device against the state at the window start (K1 or
+// k1_witness + top-k K2), hands the lists to the session in window order, answers the pods the
+// session cannot certify, and pushes the nodes the session changed.  Inside the batch the
+// handle's node_offset is 0, so every kernel writes local ids; the picks get the offset once,
+// at the end, and the snapshot its original node state.
+namespace {
+
+// The handle's host copies as the session's snapshot; with_cards: the cards too, decoded from
+// the host copy of the records, for the capacity certificate's exact witness accounting
+// (CardField order: free, clock, total, bandwidth, core, power).
+struct HostNodes {
+  yoda_node_soa nv{};
+  std::vector<uint32_t> ccount;
+  std::vector<uint64_t> fld[6];
+  std::vector<uint8_t> healthy;
+  HostNodes(const yoda_t* h, bool with_cards) {
+    const uint32_t N = h->n_nodes, K = (uint32_t)h->K;
+    nv.n_nodes = N;
+    nv.max_cards = 1;
+    nv.card_number = h->h_card_number.data();
+    nv.free_memory_sum = h->h_free_sum.data();
+    nv.total_memory_sum = h->h_total_sum.data();
+    nv.alloc_memory = h->h_alloc.data();
+    if (!with_cards) return;
+    const size_t stride = h->path == Path::N32 ? n32_stride(h->K) : node_stride(h->K);
+    ccount.resize(N);
+    healthy.resize((size_t)N * K);
+    for (auto& v : fld) v.resize((size_t)N * K);
+    for (uint32_t n = 0; n < N; ++n) {
+      const unsigned char* r = h->host_records.data() + (size_t)n * stride;
+      const NodeHdrG* hd = reinterpret_cast<const NodeHdrG*>(r);
+      ccount[n] = (uint32_t)__builtin_popcount(hd->real_mask);
+      for (uint32_t j = 0; j < K; ++j) {
+        healthy[(size_t)n * K + j] = (hd->healthy_mask >> j) & 1u;
+        for (int f = 0; f < 6; ++f)
+          fld[f][(size_t)n * K + j] =
+              h->path == Path::N32
+                  ? reinterpret_cast<const uint32_t*>(r + n32_u32_off(f, h->K))[j]
+                  : (uint64_t) reinterpret_cast<const double*>(r + 32 + 8 * (size_t)f * K)[j];
+        if (h->path == Path::N32) {  // memory values from the f64 groups (the u32 ones may be ranks)
+          fld[kFree][(size_t)n * K + j] =
+              (uint64_t) reinterpret_cast<const double*>(r + n32_f64_off(kF64Free, h->K))[j];
+          fld[kTotal][(size_t)n * K + j] =
+              (uint64_t) reinterpret_cast<const double*>(r + n32_f64_off(kF64Total, h->K))[j];
+        }
+      }
+    }
+    nv.max_cards = K;
+    nv.card_count = ccount.data();
+    nv.card_free_memory = fld[kFree].data();
+    nv.card_clock = fld[kClock].data();
+    nv.card_total_memory = fld[kTotal].data();
+    nv.card_bandwidth = fld[kBandwidth].data();
+    nv.card_core = fld[kCore].data();
+    nv.card_power = fld[kPower].data();
+    nv.card_healthy = healthy.data();
+  }
+};
+
+// One batch: the handle with its node ids local (node_offset 0 until the batch ends), the
+// session, and the one push -- the nodes the session changed since the last push, or
+// (original) every node it touched as the snapshot had it, to the device.
+struct GreedyBatch {
+  yoda_t* h;
+  const uint32_t node_offset;
+  yoda_gs_t* g = nullptr;
+  std::vector<uint32_t> ids;
+  std::vector<uint64_t> al, cn;
+  static constexpr bool kMapped = true;  // (push_node_state)
+  explicit GreedyBatch(yoda_t* x) : h(x), node_offset(x->node_offset) { h->node_offset = 0; }
+  ~GreedyBatch() {
+    h->node_offset = node_offset;
+    if (g) yoda_gs_destroy(g);
+  }
+  int push(bool original = false) {
+    const uint32_t cap = (uint32_t)(original ? g->ever_list.size() : g->dirty_list.size());
+    if (cap == 0) return YODA_OK;
+    ids.resize(cap), al.resize(cap), cn.resize(cap);
+    uint32_t got = 0;
+    const int r = original
+                      ? yoda_gs_touched_original(g, cap, ids.data(), al.data(), cn.data(), &got)
+                      : yoda_gs_take_dirty(g, cap, ids.data(), al.data(), cn.data(), &got);
+    if (r) return fail(h, r, "greedy: node state");
+    for (uint32_t t = 0; t < got; ++t) {  // Allocate -> the static score
+      bool z;
+      al[t] = static_score(h->h_free_sum[ids[t]], h->h_total_sum[ids[t]], al[t], &z);
+    }
+    return push_node_state(h, got, ids.data(), al.data(), cn.data(), kMapped);
+  }
+};
+
+FILE* greedy_trace_file() {
   static FILE* f = [] {
     const char* p = std::getenv("YODA_GREEDY_TRACE");
     return p && *p ? std::fopen(p, "w") : nullptr;
@@ -5734,102 +4794,68 @@ static FILE* greedy_trace_file() {
   return f;
 }
 
-static int greedy_capacity(yoda_t* h, const yoda_pod_soa* pods, int32_t* pick) {
+// The windowed resolve of the fast record paths.  Each window is evaluated on the device against
+// the state at its start and resolved by the session in queue order; what happens to a pod the
+// session cannot certify is the mode's policy:
+//   flags 0   it is evaluated exactly against the current state, reusing the window's
+//             feasibility bits and maxima (greedy_eval_fast: only static scores change inside a
+//             window) -- after a mid-window list refresh when the window's lists went stale
+//             (greedy_refresh()); once Allocate has wrapped past 2^64 in a window no list
+//             certifies any more and the rest of the window is evaluated that way;
+//   capacity  it is scheduled exactly (k_one_*) while such pods stay rare in the window, else it
+//             opens the next window, so it is evaluated against the current state there; the
+//             window size adapts to how far the last window got.
+int greedy_windows(GreedyBatch& b, const yoda_pod_soa* pods, bool capacity) {
   using Clock = std::chrono::steady_clock;
   auto ms_since = [](Clock::time_point t0) {
     return std::chrono::duration<double, std::milli>(Clock::now() - t0).count();
   };
-  // the chunks' list depth: 8 where the lists are merged deeper (k_topk_merge_deep: the same
-  // 64-deep lists as from 16, and a cheaper K2 -- 1.00-1.02 vs 1.07-1.09 s,
-  // profiles/r05/pqr/tk_ab.txt), else 16
-  const uint32_t kt_cap = !topk_block_ok(h) ? (uint32_t)topk_k_capacity() : (uint32_t)topk_k();
-  const uint32_t P = pods->n_pods, N = h->n_nodes, KT = kt_cap;
-  yoda_node_soa nv{};
-  nv.n_nodes = N;
-  nv.max_cards = 1;
-  nv.card_number = h->h_card_number.data();
-  nv.free_memory_sum = h->h_free_sum.data();
-  nv.total_memory_sum = h->h_total_sum.data();
-  nv.alloc_memory = h->h_alloc.data();
-  // the cards, decoded from the host copy of the records, for the session's exact witness
-  // accounting (CardField order: free, clock, total, bandwidth, core, power)
-  const uint32_t K = (uint32_t)h->K;
-  const size_t stride = h->path == Path::N32 ? n32_stride(h->K) : node_stride(h->K);
-  std::vector<uint32_t> ccount(N);
-  std::vector<uint64_t> fld[6];
-  std::vector<uint8_t> healthy((size_t)N * K);
-  for (auto& v : fld) v.resize((size_t)N * K);
-  for (uint32_t n = 0; n < N; ++n) {
-    const unsigned char* r = h->host_records.data() + (size_t)n * stride;
-    const NodeHdrG* hd = reinterpret_cast<const NodeHdrG*>(r);
-    ccount[n] = (uint32_t)__builtin_popcount(hd->real_mask);
-    for (uint32_t j = 0; j < K; ++j) {
-      healthy[(size_t)n * K + j] = (hd->healthy_mask >> j) & 1u;
-      for (int f = 0; f < 6; ++f)
-        fld[f][(size_t)n * K + j] =
-            h->path == Path::N32
-                ? reinterpret_cast<const uint32_t*>(r + n32_u32_off(f, h->K))[j]
-                : (uint64_t) reinterpret_cast<const double*>(r + 32 + 8 * (size_t)f * K)[j];
-      if (h->path == Path::N32) {  // memory values from the f64 groups (the u32 ones may be ranks)
-        fld[kFree][(size_t)n * K + j] =
-            (uint64_t) reinterpret_cast<const double*>(r + n32_f64_off(kF64Free, h->K))[j];
-        fld[kTotal][(size_t)n * K + j] =
-            (uint64_t) reinterpret_cast<const double*>(r + n32_f64_off(kF64Total, h->K))[j];
-      }
-    }
-  }
-  nv.max_cards = K;
-  nv.card_count = ccount.data();
-  nv.card_free_memory = fld[kFree].data();
-  nv.card_clock = fld[kClock].data();
-  nv.card_total_memory = fld[kTotal].data();
-  nv.card_bandwidth = fld[kBandwidth].data();
-  nv.card_core = fld[kCore].data();
-  nv.card_power = fld[kPower].data();
-  nv.card_healthy = healthy.data();
-  yoda_gs_t* g = nullptr;
-  int rc = yoda_gs_create(&nv, pods, YODA_GREEDY_CARD_CAPACITY, &g);
-  if (rc) return fail(h, rc, "greedy: session setup failed");
-  struct Guard {
-    yoda_gs_t* g;
-    ~Guard() { yoda_gs_destroy(g); }
-  } guard{g};
+  yoda_t* h = b.h;
+  yoda_gs_t* g = b.g;
+  const uint32_t P = pods->n_pods, N = h->n_nodes;
+  // the chunks' list depth.  Capacity: 8 where the lists are merged deeper (k_topk_merge_deep:
+  // the same 64-deep lists as from 16, and a cheaper K2 -- 1.00-1.02 vs 1.07-1.09 s,
+  // profiles/r05/pqr/tk_ab.txt), else 16.  Flags 0: 8 (YODA_GREEDY_TOPK=16, A/B knob: 16)
+  static const uint32_t kt_env = YODA_KNOB("YODA_GREEDY_TOPK", 0);
+  const bool kt_cap = capacity ? !topk_block_ok(h) : kt_env == (uint32_t)topk_k_capacity();
+  const uint32_t KT = (uint32_t)(kt_cap ? topk_k_capacity() : topk_k());
+  // the capacity lists' depth: KT from the chunks, merged deeper where the block kernels run
+  // (k_topk_merge_deep: exact as far as they reach; YODA_GREEDY_CAP_DEPTH, A/B knob: 32 /
+  // 64 / 128, 0 = KT).  128 with the exact-fallback scan below (windows 1558 -> 822,
+  // capacity 0.97 -> 0.89-0.90 s; 128 alone 0.98 s, the scan alone 0.92-0.93 s;
+  // profiles/r06/greedy_scan/)
+  static const uint32_t cap_depth = YODA_KNOB("YODA_GREEDY_CAP_DEPTH", 128);
+  const uint32_t deep = capacity ? cap_depth : 0u;
+  const GreedyRefresh& rf = greedy_refresh();
+  // Small windows: the GPU work is the same P x N in total, while fewer nodes are touched per
+  // window, so fewer candidate lists lose certification.
   const uint32_t Wmax = greedy_window();
-  uint32_t W = Wmax;
-  std::vector<uint32_t> ids, cnt_w, ti_w, wc_w;
-  std::vector<uint64_t> al, cn, mx_w;
-  std::vector<double> ts_w;
-  auto push = [&]() -> int {  // nodes the session changed -> the device
-    const uint32_t d = (uint32_t)g->dirty_list.size();
-    if (d == 0) return YODA_OK;
-    ids.resize(d), al.resize(d), cn.resize(d);
-    uint32_t got = 0;
-    int r = yoda_gs_take_dirty(g, d, ids.data(), al.data(), cn.data(), &got);
-    if (r) return fail(h, r, "greedy: take_dirty");
-    for (uint32_t t = 0; t < got; ++t) ids[t] += h->node_offset;
-    return yoda_set_node_state(h, got, ids.data(), al.data(), cn.data());
-  };
+  uint32_t W = Wmax, ws = 0;
   PodGather win;
-  uint32_t ws = 0;
+  std::vector<uint32_t> pos, cnt_w, ti_w, wc_w, ti_s, ti_r;
+  std::vector<uint64_t> mx_w;
+  std::vector<double> ts_w, ts_s, ts_r;
+  int rc;
   while (ws < P) {
     const auto tw = Clock::now();
-    if ((rc = push())) return rc;
+    if ((rc = b.push())) return rc;
     const uint32_t wn = std::min(W, P - ws);
     win.build(pods, g->order.data() + ws, wn);
     if ((rc = yoda_upload_pods(h, &win.soa))) return rc;
     const double t_up = ms_since(tw);
     if ((rc = prepare_run(h, YODA_MODE_SCV))) return rc;
+    // sort the window like any batch (whole waves skip nodes); k_window_out brings the outputs
+    // back to window order
     if ((rc = order_pods(h, YODA_MODE_SCV))) return rc;
-    HIP_TRY(h, h->wit.ensure(12 * (size_t)wn * 4));
-    if ((rc = phase1_witness(h, h->maxima.as<uint64_t>(), h->counts.as<uint32_t>(),
-                             h->wit.as<uint32_t>(), 0)))
-      return rc;
-    // the lists' depth: KT from the chunks, merged deeper where the block kernels run
-    // (k_topk_merge_deep: exact as far as they reach; YODA_GREEDY_CAP_DEPTH, A/B knob: 32 /
-    // 64 / 128, 0 = KT).  128 with the exact-fallback scan below (windows 1558 -> 822,
-    // capacity 0.97 -> 0.89-0.90 s; 128 alone 0.98 s, the scan alone 0.92-0.93 s;
-    // profiles/r06/greedy_scan/)
-    static const uint32_t cap_depth = YODA_KNOB("YODA_GREEDY_CAP_DEPTH", 128);
+    h->greedy_prep_ms += ms_since(tw);
+    HIP_TRY(h, h->wit.ensure(12 * (size_t)wn * 4));  // (flags 0: staged with the rest, unread)
+    if (capacity)
+      rc = phase1_witness(h, h->maxima.as<uint64_t>(), h->counts.as<uint32_t>(),
+                          h->wit.as<uint32_t>(), 0);
+    else if (N > 0)
+      rc = phase1(h, YODA_MODE_SCV, h->maxima.as<uint64_t>(), h->counts.as<uint32_t>(),
+                  Maxima::Own);
+    if (rc) return rc;
     uint32_t KD = KT;
     // pinned staging of the window's outputs, in window order (k_window_out writes them there
     // from the sorted order in one launch): counts | maxima | wit | top scores | top nodes
@@ -5839,7 +4865,7 @@ static int greedy_capacity(yoda_t* h, const yoda_pod_soa* pods, int32_t* pick) {
       o_ts = o_wit + 48 * (size_t)wn, o_ti = o_ts + 8 * (size_t)kd * wn,
       total = o_ti + 4 * (size_t)kd * wn;
     };
-    layout(std::max(KT, cap_depth));
+    layout(std::max(KT, deep));
     HIP_TRY(h, h->win_stage.ensure(total));
     unsigned char* st = static_cast<unsigned char*>(h->win_stage.p);
     const uint32_t *cnt_p, *wc_p, *ti_p;
@@ -5849,12 +4875,7 @@ static int greedy_capacity(yoda_t* h, const yoda_pod_soa* pods, int32_t* pick) {
     if (N > 0) {
       HIP_TRY(h, launch_prep2(h->maxima.as<uint64_t>(), wn, h->rcp.as<double>(),
                                h->stream));
-      // (node ids local here: the session works on this handle's nodes)
-      const uint32_t off = h->node_offset;
-      h->node_offset = 0;
-      rc = topk_lists(h, wn, KT, h->counts.as<uint32_t>(), cap_depth, &KD);
-      h->node_offset = off;
-      if (rc) return rc;
+      if ((rc = topk_lists(h, wn, KT, h->counts.as<uint32_t>(), deep, &KD))) return rc;
       layout(KD);
       // (YODA_WIN_DMA=0, A/B knob: k_window_out writes the pinned pages directly)
       static const bool win_dma = YODA_KNOB("YODA_WIN_DMA", 1) != 0;
@@ -5870,6 +4891,11 @@ static int greedy_capacity(yoda_t* h, const yoda_pod_soa* pods, int32_t* pick) {
       if (win_dma)
         HIP_TRY(h, hipMemcpyAsync(h->win_stage.p, h->win_dev.p, total, hipMemcpyDeviceToHost,
                                   h->stream));
+      if (!capacity) {  // pos[i] = sorted position of window pod i: k_greedy_one's address
+        pos.resize(wn);
+        HIP_TRY(h, hipMemcpyAsync(pos.data(), h->win_inv.p, (size_t)wn * 4,
+                                  hipMemcpyDeviceToHost, h->stream));
+      }
       t_issued = ms_since(tw);
       HIP_TRY(h, hipStreamSynchronize(h->stream));
       t_sync = ms_since(tw);
@@ -5897,53 +4923,90 @@ static int greedy_capacity(yoda_t* h, const yoda_pod_soa* pods, int32_t* pick) {
     const auto tr = Clock::now();
     if ((rc = gs_begin_window_at(g, ws, wn, KD, cnt_p, const_cast<double*>(ts_p),
                                  const_cast<uint32_t*>(ti_p), true, N > 0)) ||
-        (rc = yoda_gs_set_witness(g, mx_p, wc_p, wc_p + 6 * (size_t)wn)))
+        (capacity && (rc = yoda_gs_set_witness(g, mx_p, wc_p, wc_p + 6 * (size_t)wn))))
       return fail(h, rc, "greedy: session window");
-    // resolve; an uncertified pod is scheduled exactly against the current state (k_one_*)
-    // while such pods stay rare in the window, else it opens the next window
-    uint32_t next = 0, fails = 0;
+    uint32_t next = 0, fails = 0, fb_since = 0;
     double fb_ms = 0;
     uint64_t why0[6];
     std::copy(std::begin(g->why), std::end(g->why), why0);
     for (;;) {
       if ((rc = yoda_gs_resolve(g, &next))) return fail(h, rc, "greedy: resolve");
-      // YODA_GREEDY_FAIL_DIV (A/B knob): one exact evaluation allowed per that many resolved pods
-      static const uint32_t rate = YODA_KNOB("YODA_GREEDY_FAIL_DIV", 0);
-      // fall back exactly (instead of restarting the window) when at most
-      // YODA_GREEDY_CAP_SCAN_MAX of the next YODA_GREEDY_CAP_SCAN window pods are uncertified
-      // already (A/B knobs; 64 / 1: a restart re-runs the window's kernels for one pod whose
-      // witness was lost while its successors still hold theirs; 32 / 128 / 256: 0.97 / 0.92 /
-      // 0.91 s, 0: 0.97 s)
-      static const uint32_t scan_n = YODA_KNOB("YODA_GREEDY_CAP_SCAN", 64);
-      static const uint32_t scan_max = YODA_KNOB("YODA_GREEDY_CAP_SCAN_MAX", 1);
       if (next >= wn) break;
-      bool fallback = false;
-      if (rate) {
-        fallback = ++fails <= next / rate;
-      } else if (scan_n && wn - next > scan_n) {
-        uint64_t saved[6];
-        std::copy(std::begin(g->why), std::end(g->why), saved);
-        uint32_t unc = 0;
-        int32_t dummy;
-        for (uint32_t j = next + 1; j <= next + scan_n && unc <= scan_max; ++j)
-          unc += g->resolve_capacity(j, g->order[ws + j], &dummy) ? 0u : 1u;
-        std::copy(std::begin(saved), std::end(saved), std::begin(g->why));
-        fallback = unc <= scan_max;
-      }
-      if (!fallback) break;
       const auto tf = Clock::now();
-      if ((rc = push())) return rc;
       int32_t pk = YODA_PICK_NONE;
-      if ((rc = greedy_eval_exact(h, pods, g->order[ws + next], &pk))) return rc;
+      if (capacity) {
+        // YODA_GREEDY_FAIL_DIV (A/B knob): one exact evaluation allowed per that many resolved pods
+        static const uint32_t rate = YODA_KNOB("YODA_GREEDY_FAIL_DIV", 0);
+        // fall back exactly (instead of restarting the window) when at most
+        // YODA_GREEDY_CAP_SCAN_MAX of the next YODA_GREEDY_CAP_SCAN window pods are uncertified
+        // already (A/B knobs; 64 / 1: a restart re-runs the window's kernels for one pod whose
+        // witness was lost while its successors still hold theirs; 32 / 128 / 256: 0.97 / 0.92 /
+        // 0.91 s, 0: 0.97 s)
+        static const uint32_t scan_n = YODA_KNOB("YODA_GREEDY_CAP_SCAN", 64);
+        static const uint32_t scan_max = YODA_KNOB("YODA_GREEDY_CAP_SCAN_MAX", 1);
+        bool fallback = false;
+        if (rate) {
+          fallback = ++fails <= next / rate;
+        } else if (scan_n && wn - next > scan_n) {
+          uint64_t saved[6];
+          std::copy(std::begin(g->why), std::end(g->why), saved);
+          uint32_t unc = 0;
+          int32_t dummy;
+          for (uint32_t j = next + 1; j <= next + scan_n && unc <= scan_max; ++j)
+            unc += g->resolve_capacity(j, g->order[ws + j], &dummy) ? 0u : 1u;
+          std::copy(std::begin(saved), std::end(saved), std::begin(g->why));
+          fallback = unc <= scan_max;
+        }
+        if (!fallback) break;
+        if ((rc = b.push()) || (rc = greedy_eval_exact(h, pods, g->order[ws + next], &pk)))
+          return rc;
+      } else {
+        if (!g->wrapped && ++fb_since >= rf.every && wn - next >= 2 * rf.scan) {
+          fb_since = 0;
+          uint32_t unc = 0;
+          if ((rc = yoda_gs_uncertified(g, next + 1, rf.scan, &unc)))
+            return fail(h, rc, "greedy: scan");
+          if (unc >= rf.min) {
+            // the window's top-k K2 again, against the current state (its K1 masks and maxima
+            // stay valid: only static scores change in this mode); the lists come back in
+            // sorted order and go to the session in window order
+            if ((rc = b.push()) || (rc = topk_lists(h, wn, KT, h->counts.as<uint32_t>())))
+              return rc;
+            const size_t ln = (size_t)KT * wn;
+            ts_s.resize(ln), ti_s.resize(ln), ts_r.resize(ln), ti_r.resize(ln);
+            HIP_TRY(h, hipMemcpyAsync(ts_s.data(), h->tk_s.p, ln * 8, hipMemcpyDeviceToHost,
+                                      h->stream));
+            HIP_TRY(h, hipMemcpyAsync(ti_s.data(), h->tk_i.p, ln * 4, hipMemcpyDeviceToHost,
+                                      h->stream));
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+            for (uint32_t kk = 0; kk < KT; ++kk)
+              for (uint32_t j = next; j < wn; ++j) {
+                ts_r[(size_t)kk * wn + j] = ts_s[(size_t)kk * wn + pos[j]];
+                ti_r[(size_t)kk * wn + j] = ti_s[(size_t)kk * wn + pos[j]];
+              }
+            if ((rc = yoda_gs_refresh(g, next, ts_r.data(), ti_r.data())))
+              return fail(h, rc, "greedy: refresh");
+            ++h->greedy_refreshes;
+            const uint32_t stuck = next;
+            if ((rc = yoda_gs_resolve(g, &next))) return fail(h, rc, "greedy: resolve");
+            if (next != stuck) {  // certified now: the resolve went on to a later pod
+              fb_ms += ms_since(tf);
+              continue;
+            }
+          }
+        }
+        if ((rc = b.push()) || (rc = greedy_eval_fast(h, pos[next], &pk))) return rc;
+      }
       if ((rc = yoda_gs_assign(g, ws + next, pk))) return fail(h, rc, "greedy: assign");
       ++h->greedy_fallbacks;
       fb_ms += ms_since(tf);
     }
     h->greedy_fallback_ms += fb_ms;
     h->greedy_resolve_ms += ms_since(tr) - fb_ms;
-    // YODA_GREEDY_TRACE=<file> (diagnostic): one line per window -- start, size, pods
+    // YODA_GREEDY_TRACE=<file> (diagnostic, capacity): one line per window -- start, size, pods
     // resolved, the failed certificate (index into why[], -1 = none), pods assigned so far
-    if (FILE* tf = greedy_trace_file()) {
+    FILE* tf = capacity ? greedy_trace_file() : nullptr;
+    if (tf) {
       int reason = -1;
       for (int r = 0; r < 6; ++r)
         if (g->why[r] != why0[r]) reason = r;
@@ -5963,12 +5026,8 @@ static int greedy_capacity(yoda_t* h, const yoda_pod_soa* pods, int32_t* pick) {
     }
     if (next < wn) {
       // pod ws + next could not be certified: it opens the next window (evaluated against the
-      // current state, so it is always resolved there); size it after this one's progress
+      // current state, so it is always resolved there), sized after this one's progress
       ++h->greedy_restarts;
-      // the next window holds 130 % of this one's progress, in whole waves: small windows cost
-      // less (K1 / K2 time grows with the pods) and most restart near where the last one did;
-      // profiles/r03/greedy_capacity/grow_ab.txt (1.81-1.91 s with the earlier power of two >=
-      // twice the progress, 1.57-1.64 s at 130 %).  YODA_GREEDY_GROW_PCT: A/B knob
       W = yoda_greedy_next_window(next, Wmax);
       ws += next;
     } else {
@@ -5976,8 +5035,7 @@ static int greedy_capacity(yoda_t* h, const yoda_pod_soa* pods, int32_t* pick) {
       W = std::min(2 * W, Wmax);
     }
   }
-  if ((rc = yoda_gs_picks(g, pick, nullptr, nullptr))) return fail(h, rc, "greedy: picks");
-  if (std::getenv("YODA_GREEDY_DEBUG"))
+  if (capacity && std::getenv("YODA_GREEDY_DEBUG"))
     std::fprintf(stderr,
                  "greedy capacity: windows %u restarts %u; failed certificates: wrap %llu, "
                  "few-left %llu, zero-total %llu, maxima %llu, list-lost %llu, threshold %llu; "
@@ -5987,16 +5045,46 @@ static int greedy_capacity(yoda_t* h, const yoda_pod_soa* pods, int32_t* pick) {
                  (unsigned long long)g->why[3], (unsigned long long)g->why[4],
                  (unsigned long long)g->why[5], (unsigned long long)g->n_resolve,
                  (unsigned long long)g->n_scan, (unsigned long long)g->n_scan_nodes);
-  for (uint32_t p = 0; p < P; ++p)
-    if (pick[p] >= 0) pick[p] += (int32_t)h->node_offset;
+  return YODA_OK;
+}
+
+}  // namespace
+
+static int greedy_batch(yoda_t* h, const yoda_pod_soa* pods, int mode, uint32_t flags,
+                        int32_t* pick) {
+  const bool capacity = (flags & YODA_GREEDY_CARD_CAPACITY) != 0;
+  const uint32_t P = pods->n_pods;
+  int rc;
+  GreedyBatch b(h);
+  {
+    const HostNodes hn(h, capacity && !h->generic);
+    // (the pods' arrays outlive the batch: the session reads them in place)
+    if ((rc = gs_create(&hn.nv, pods, capacity ? YODA_GREEDY_CARD_CAPACITY : 0u, true, &b.g)))
+      return fail(h, rc, "greedy: session setup failed");
+  }
+  yoda_gs_t* g = b.g;
+  if (h->generic) {
+    // The U64 normalize check can change after every pick: every pod is evaluated exactly
+    // against the current state, in queue order.
+    for (uint32_t i = 0; i < P; ++i) {
+      int32_t pk = YODA_PICK_NONE;
+      if ((rc = b.push()) || (rc = greedy_eval_one(h, pods, g->order[i], mode, &pk))) return rc;
+      if ((rc = yoda_gs_assign(g, i, pk))) return fail(h, rc, "greedy: assign");
+      ++h->greedy_fallbacks;
+    }
+  } else if ((rc = greedy_windows(b, pods, capacity))) {
+    return rc;
+  }
+  if ((rc = yoda_gs_picks(g, pick, nullptr, nullptr))) return fail(h, rc, "greedy: picks");
+  for (uint32_t p = 0; p < P; ++p)  // the one place the local ids become the caller's
+    if (pick[p] >= 0) pick[p] += (int32_t)b.node_offset;
+  if (std::getenv("YODA_GREEDY_DEBUG"))
+    std::fprintf(stderr, "greedy: windows %u (%.1f ms, of which host prep %.1f ms), fallbacks %u "
+                 "(%.1f ms), resolve %.1f ms; mid-window list refreshes %u\n", h->greedy_windows,
+                 h->greedy_window_ms, h->greedy_prep_ms, h->greedy_fallbacks,
+                 h->greedy_fallback_ms, h->greedy_resolve_ms, h->greedy_refreshes);
   // leave the uploaded snapshot as it was
-  const uint32_t ne = (uint32_t)g->ever_list.size();
-  ids.resize(ne), al.resize(ne), cn.resize(ne);
-  uint32_t got = 0;
-  if ((rc = yoda_gs_touched_original(g, ne, ids.data(), al.data(), cn.data(), &got)))
-    return fail(h, rc, "greedy: restore");
-  for (uint32_t t = 0; t < got; ++t) ids[t] += h->node_offset;
-  if ((rc = yoda_set_node_state(h, got, ids.data(), al.data(), cn.data()))) return rc;
+  if ((rc = b.push(true))) return rc;
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   h->ran = false;
   return YODA_OK;
@@ -6411,53 +5499,6 @@ struct Coll {
 static int comm_step(yoda_t* const* hs, int n, int world, int mode, bool local,
                      bool draw = false);
 
-// The sharded greedy's list merge (window exchange 2), shared by comm_greedy and the caller-
-// driven protocol (yoda_merge_shard_lists, dist.sharded_greedy): shard rk's list of window pod
-// p is (sc[rk][l*wn + p], nd[rk][l*wn + p]), l < kl, sorted score desc / node asc and ended by
-// a 0xFFFFFFFF node.  ts/ti [kl][wn] receive the first kl of the union in that order (pods
-// [from, wn) only).  Deep lists (exact down to their last entry only): every node a shard left
-// out scores at most the shard's last entry, so the union is certain only above the latest of
-// those -- and for its first topk_k(), which lie within their shards' exact prefixes.
-static void merge_shard_lists(int world, uint32_t wn, uint32_t kl, bool deep, uint32_t from,
-                              const double* const* sc, const uint32_t* const* nd, double* ts,
-                              uint32_t* ti) {
-  auto before = [](const std::pair<double, uint32_t>& a, const std::pair<double, uint32_t>& b) {
-    return a.first > b.first || (a.first == b.first && a.second < b.second);
-  };
-  std::vector<uint32_t> head(world), len(world);
-  for (uint32_t p = from; p < wn; ++p) {
-    bool any_last = false;
-    std::pair<double, uint32_t> last_max{-1.0, 0xffffffffu};
-    for (int rk = 0; rk < world; ++rk) {
-      uint32_t l = 0;
-      while (l < kl && nd[rk][(size_t)l * wn + p] != 0xffffffffu) ++l;
-      len[rk] = l;
-      head[rk] = 0;
-      if (deep && l > 0) {
-        const std::pair<double, uint32_t> last{sc[rk][(size_t)(l - 1) * wn + p],
-                                               nd[rk][(size_t)(l - 1) * wn + p]};
-        if (!any_last || before(last_max, last)) last_max = last;
-        any_last = true;
-      }
-    }
-    for (uint32_t k = 0; k < kl; ++k) {
-      int best = -1;
-      std::pair<double, uint32_t> bv{-1.0, 0xffffffffu};
-      for (int rk = 0; rk < world; ++rk) {
-        if (head[rk] >= len[rk]) continue;
-        const size_t o = (size_t)head[rk] * wn + p;
-        const std::pair<double, uint32_t> v{sc[rk][o], nd[rk][o]};
-        if (best < 0 || before(v, bv)) best = rk, bv = v;
-      }
-      if (best < 0) break;
-      if (any_last && k >= (uint32_t)topk_k() && !before(bv, last_max)) break;
-      ++head[best];
-      ts[(size_t)k * wn + p] = bv.first;
-      ti[(size_t)k * wn + p] = bv.second;
-    }
-  }
-}
-
 // the capacity windows' list depth across shards (YODA_GREEDY_CAP_DEPTH, as yoda_greedy's)
 static uint32_t greedy_cap_depth() {
   static const uint32_t d = YODA_KNOB("YODA_GREEDY_CAP_DEPTH", 64);
@@ -6677,10 +5718,10 @@ static int comm_greedy(yoda_t* const* hs, int n, int world, bool local, const yo
         }
         continue;
       }
-      // mid-window list refresh (yoda_greedy's): every kFbCheck exact pods,
-      // when >= kScanMin of the next kScan window pods are uncertified already, every shard's
-      // top-k runs again against the current state and the merged lists replace the old ones
-      constexpr uint32_t kFbCheck = 8, kScan = 256, kScanMin = 16;
+      // mid-window list refresh (yoda_greedy's, greedy_refresh()): every shard's top-k runs
+      // again against the current state and the merged lists replace the old ones
+      const uint32_t kFbCheck = greedy_refresh().every, kScan = greedy_refresh().scan,
+                     kScanMin = greedy_refresh().min;
       uint32_t fb_since = 0;
       for (;;) {
         uint32_t nxt = 0;
@@ -6759,31 +5800,6 @@ int yoda_shard_topk_deep(yoda_t* h, const uint64_t* d_maxima, const uint32_t* d_
   if (!h) return YODA_ERR_INVALID_ARG;
   if (deep > 1024) return fail(h, YODA_ERR_INVALID_ARG, "yoda_shard_topk_deep: deep > 1024");
   return shard_topk_impl(h, d_maxima, d_counts, k, deep, counts, top_score, top_node);
-}
-
-int yoda_merge_shard_lists(uint32_t world, uint32_t wn, uint32_t kl, uint32_t from,
-                           const double* scores, const uint32_t* nodes, double* out_score,
-                           uint32_t* out_node) {
-  if (world < 1 || kl < 1 || from > wn || !scores || !nodes || !out_score || !out_node)
-    return YODA_ERR_INVALID_ARG;
-  try {
-    std::vector<const double*> sc(world);
-    std::vector<const uint32_t*> nd(world);
-    for (uint32_t rk = 0; rk < world; ++rk) {
-      sc[rk] = scores + (size_t)rk * kl * wn;
-      nd[rk] = nodes + (size_t)rk * kl * wn;
-    }
-    for (uint32_t k = 0; k < kl; ++k)
-      for (uint32_t p = from; p < wn; ++p) {
-        out_score[(size_t)k * wn + p] = -1.0;
-        out_node[(size_t)k * wn + p] = 0xffffffffu;
-      }
-    merge_shard_lists((int)world, wn, kl, kl > (uint32_t)topk_k_capacity(), from, sc.data(),
-                      nd.data(), out_score, out_node);
-    return YODA_OK;
-  } catch (...) {
-    return YODA_ERR_INVALID_ARG;
-  }
 }
 
 int yoda_comm_greedy_stats(const yoda_t* h, uint32_t* out) {

@@ -138,6 +138,8 @@ def test_config5_generator_several_windows_vs_oracle(flags):
     pick = y.greedy(pods, MODE_SCV, flags)
     windows, _ = y.greedy_stats()
     assert windows >= 3
+    if flags == 0:  # the mid-window list refresh ran (5 times at this shape)
+        assert y.greedy_refreshes() > 0
     want, _ = oracle.greedy(nodes, pods, MODE_SCV, flags)
     np.testing.assert_array_equal(pick, want)
     y.close()

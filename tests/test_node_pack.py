@@ -23,3 +23,17 @@ def test_pack_node_rows(tmp_path):
     out = subprocess.run([exe], capture_output=True, text=True)
     assert out.returncode == 0, out.stdout + out.stderr
     assert "check_node_pack ok" in out.stdout, out.stdout
+
+
+def test_greedy_session_host_check(tmp_path):
+    """tools/check_greedy_session.cpp: the host-only greedy session (yoda_greedy_session.cpp, no
+    HIP header), built with AddressSanitizer and UBSan as an ordinary executable and driven on
+    random small clusters -- zero-total nodes, Allocate wrapping past 2^64 mid-window, lists
+    shorter than the feasible counts, refreshes -- against a plain sequential loop."""
+    exe = str(tmp_path / "check_greedy_session")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=all", "-o", exe,
+                    os.path.join(REPO, "tools", "check_greedy_session.cpp")], check=True)
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "check_greedy_session ok" in out.stdout, out.stdout

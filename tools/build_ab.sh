@@ -12,5 +12,6 @@ T=$(mktemp -d)
 /opt/rocm/bin/hipcc $F -DYODA_AB_KNOBS "$@" -c -o $T/k.o $SRC/yoda_kernels.hip
 /opt/rocm/bin/hipcc $F -c -o $T/o.o $SRC/yoda_order.hip
 /opt/rocm/bin/hipcc $F -DYODA_AB_KNOBS -c -o $T/c.o $SRC/yoda_capi.cpp
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $ROOT/abl/$NAME.so $T/k.o $T/o.o $T/c.o
+/opt/rocm/bin/hipcc $F -DYODA_AB_KNOBS -c -o $T/g.o $SRC/yoda_greedy_session.cpp
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $ROOT/abl/$NAME.so $T/k.o $T/o.o $T/c.o $T/g.o
 rm -rf $T
