@@ -508,7 +508,7 @@ int yoda_update_node_cards(yoda_t* h, uint32_t count, const uint32_t* nodes, uin
  * when it returns.  yoda_greedy* leaves the presence as it found it.
  *   Mode B (YODA_MODE_DISKIO) has no Filter and does not read the bit: while any node is absent
  * its entry points return YODA_ERR_STATE and do nothing else; with every node present it is
- * untouched.
+ * untouched.  yoda_mode_b_follow (below) makes its single-handle batch path follow the node set.
  *   This is NOT a per-cycle candidate mask for other plugins' Filter results (cordon, taints,
  * nodeSelector): in the reference such a node's SCV still feeds CollectMaxValues, an absent
  * node's does not.  That mask is yoda_set_candidates (below).
@@ -545,7 +545,8 @@ int yoda_nodes_absent(const yoda_t* h, uint32_t* n_absent);
  * witness and draw calls included; only the settings (yoda_shard_tie_draw,
  * yoda_shard_exchange_order) and the host queries (yoda_shard_topk_depth,
  * yoda_shard_overflow_count) answer.  A change of the candidate state also drops a sharded
- * step's pending exact merge.  With candidates off they run as they always did.
+ * step's pending exact merge.  With candidates off they run as they always did.  Mode B's
+ * single-handle batch path honours the classes once yoda_mode_b_follow (below) is on.
  *   The calls are ordered on the handle's stream and invalidate pending run, phase-1 and top-k
  * state, as yoda_set_node_present does; each validates its arguments before it writes anything.
  *   Cost: one pass over K1's masks after the Filter kernel (k_cand_narrow); the K2 pruning seeds
@@ -577,6 +578,45 @@ int yoda_candidates_info(const yoda_t* h, uint32_t* out);
 /* Diagnostic: the narrowing pass's time (HIP events, ms) summed over the runs that the
  * yoda_profile_read calls since the last call of this one have read (yoda_profile on). */
 int yoda_candidates_profile(yoda_t* h, double* narrow_ms);
+/* ---- Mode B follows the absent nodes and the candidate classes (opt-in) ----
+ * Mode B's Filter is a pass-through (scheduler.go:96-99), so the nodes a Mode B pod may land on
+ * are decided by the node set and the other plugins' Filter alone.  With the setting on,
+ * E(p) = {n : n present and cand(p, n)} -- cand always true while candidates are off or for a
+ * YODA_CAND_ANY pod; an absent node is in no E whatever its word says -- and pod p's cycle is
+ * exactly the reference's Mode B cycle on the sub-snapshot holding only the nodes of E(p), picks
+ * reported as ids of the uploaded snapshot (n_nodes, the ids and node_offset do not change):
+ * n_feasible = |E|; |E| = 0 is YODA_STATUS_UNSCHEDULABLE with no pick, n_ties 0 and top_score 0;
+ * |E| = 1 is that node with n_ties 1 and its raw score; otherwise top_score is the best level
+ * over E, n_ties the nodes of E at it, the pick the lowest of them, or with yoda_set_tie_draw the
+ * one with the smallest yoda_tie_hash.  There is no DIV_ZERO in Mode B.  In the score rows a node
+ * outside E has feasibility bit 0 and raw and normalized scores of -1, a node of E scores what it
+ * scores without the setting, and NormalizeScore takes highest and lowest over E.
+ *   Followed by yoda_eval, yoda_run, yoda_download, yoda_score_rows and yoda_score_rows_norm
+ * (their bitmask_out included), the single-handle draw, and yoda_greedy in Mode B while nodes are
+ * absent (it keeps refusing candidate classes, as every greedy call does).  Unchanged with the
+ * setting on: yoda_shard_* and yoda_comm_* in Mode B, the shard draw calls included, keep
+ * returning YODA_ERR_STATE while a node is absent or candidates are on, and
+ * yoda_run(YODA_MODE_DISKIO, YODA_RUN_BITMASK) + yoda_download_bitmask keeps its "run Mode A"
+ * refusal.  A run with candidates on needs a class array as long as the batch, as in Mode A.
+ *   Off (the default): Mode B refuses with YODA_ERR_STATE while a node is absent or candidates
+ * are on, exactly as before.  A setting: it stays across uploads until changed.
+ *   Cost: nothing while every E is the whole snapshot (no node absent, and candidates off or
+ * every pod YODA_CAND_ANY): the unrestricted kernels run.  Otherwise sibling kernels read one
+ * 16-byte eligibility record per node beside its 16-byte Mode B record, rebuilt (one small
+ * kernel, with the 65 class counts) on the first Mode B run after yoda_upload_nodes,
+ * yoda_set_node_present, yoda_set_candidates or yoda_update_candidates; the batch's pod classes
+ * are then the distinct (alpha, beta, candidate class) triples.  Measured at 100k pods x 100k
+ * nodes (profiles/modebfollow/timing.txt) against the unrestricted step for the same pods: one
+ * pod spec 0.018 ms -> 0.021 ms with 1,024 absent nodes (x1.2) and 0.029 ms with 8 classes lacking
+ * 1 % or 30 % of the nodes (x1.65: 9 effective classes instead of 1); a distinct request per pod
+ * 2.29 ms -> 4.85 ms (x2.1) in each of those states -- the test and the masked step roughly double
+ * the per-pair instructions of an FP64-issue-bound kernel.  Never enabled, or enabled with every
+ * E whole, the step is inside the parent's run-to-run spread (profiles/modebfollow/ab.txt). */
+int yoda_mode_b_follow(yoda_t* h, int enable);
+/* Diagnostic, host only: out[4] = {enabled, effective classes D' of the last Mode B batch run,
+ * 1 if that run took the eligibility kernels (0: the unchanged ones), eligibility-table builds
+ * since the upload}. */
+int yoda_mode_b_info(const yoda_t* h, uint32_t* out);
 /* Diagnostic (synchronizes).  digest[8]: a 64-bit hash per table over its words as the device
  * holds them -- records, K1 summaries, K2 summaries, per-card model rows, K1 mixed tiles, block
  * summaries, G table, G maxima + reciprocals (0 where the record path has none).  mismatch[4]:

@@ -28,6 +28,7 @@
 #include "../../include/yoda.h"
 #include "yoda_layout.h"
 #include "yoda_launch.h"
+#include "yoda_modeb.h"
 #include "yoda_node_pack.h"
 #include "yoda_greedy_session.h"
 
@@ -423,6 +424,18 @@ struct yoda_handle {
   bool b_cls_ready = false;
   uint32_t b_ncls = 0;
   DevBuf b_cab, b_cls, b_part;
+  // yoda_mode_b_follow: Mode B's batch path honours the absent nodes and the candidate classes.
+  // The classes are then keyed by (alpha, beta, candidate class) -- b_cls_keyed: the ready ones
+  // are -- with their selectors in b_csel [D].  b_elig [n_nodes] DiskElig and b_ecnt [65] are
+  // rebuilt on the first Mode B run after the node set or the words changed (b_elig_dirty;
+  // b_elig_builds: since the upload).  b_last_*: the last Mode B batch run (yoda_mode_b_info).
+  bool b_follow = false;
+  bool b_cls_keyed = false;
+  bool b_elig_dirty = true;
+  uint32_t b_elig_builds = 0;
+  bool b_last_elig = false;
+  uint32_t b_last_ncls = 0;
+  DevBuf b_csel, b_elig, b_ecnt, b_pres;
   uint32_t k3_nfl = 0;
   // profiling: event pairs around K1 / K2
   bool profiling = false;
@@ -877,8 +890,11 @@ int pods_complete(yoda_t* h) {
 
 // Mode B has no Filter and kernels of its own, none of which reads the presence bits
 // (yoda_set_node_present): while a node is absent its entry points refuse to run.
-int mode_b_absent(yoda_t* h, int mode) {
+// batch: the single-handle batch path (yoda_run, yoda_eval, the row calls, yoda_greedy), which
+// follows both once yoda_mode_b_follow is on; the shard and communicator calls keep refusing.
+int mode_b_absent(yoda_t* h, int mode, bool batch = false) {
   if (mode != YODA_MODE_DISKIO) return YODA_OK;
+  if (batch && h->b_follow) return YODA_OK;
   if (h->cand_classes)
     return fail(h, YODA_ERR_STATE,
                 "Mode B does not honour candidate classes (yoda_set_candidates): turn them off");
@@ -907,7 +923,7 @@ int cand_ready(yoda_t* h) {
   return YODA_OK;
 }
 
-int check_ready(yoda_t* h, int mode) {
+int check_ready(yoda_t* h, int mode, bool batch = false) {
   if (!h) return YODA_ERR_INVALID_ARG;
   if (mode != YODA_MODE_SCV && mode != YODA_MODE_DISKIO)
     return fail(h, YODA_ERR_INVALID_ARG, "mode must be YODA_MODE_SCV or YODA_MODE_DISKIO");
@@ -915,7 +931,7 @@ int check_ready(yoda_t* h, int mode) {
   if (!h->has_pods) return fail(h, YODA_ERR_NO_PODS, "no pods uploaded");
   if (mode == YODA_MODE_DISKIO && !(h->nodes_diskio && h->pods_diskio))
     return fail(h, YODA_ERR_INVALID_ARG, "Mode B needs node cpu/disk_io and pod rio/rcpu");
-  if (int rc = mode_b_absent(h, mode)) return rc;
+  if (int rc = mode_b_absent(h, mode, batch)) return rc;
   if (int rc = cand_ready(h)) return rc;
   HIP_TRY(h, hipSetDevice(h->device));
   return h->fast_run ? YODA_OK : pods_complete(h);
@@ -1142,44 +1158,69 @@ static const DiskLevels& diskio_levels() {
   return lv;
 }
 
+// Mode B runs with eligibility (yoda_mode_b_follow on) when E(p) is not every node for some pod:
+// a node is absent, or candidates are on and some pod names a class.  Otherwise the unrestricted
+// kernels run, exactly as without the setting.
+bool modeb_keyed(const yoda_t* h) {
+  return h->b_follow && h->cand_classes && !h->h_cls.empty() && h->cls_top >= 0;
+}
+bool modeb_elig_on(const yoda_t* h) { return h->b_follow && (h->n_absent > 0 || modeb_keyed(h)); }
+// The pods' class bytes on the device for the eligibility kernels (nullptr: every pod ANY).
+const uint8_t* modeb_cls_bytes(const yoda_t* h) {
+  return modeb_keyed(h) ? h->cand_cls.as<uint8_t>() : nullptr;
+}
+
 // The batch's Mode B pod classes, from the staged (alpha, beta) of the last upload: pods with
-// bit-identical (alpha, beta) score every node alike (algorithm.go:105-111).
+// bit-identical (alpha, beta) score every node alike (algorithm.go:105-111); with eligibility
+// the pod's candidate class is part of the key (yoda_modeb.h disk_build_classes).  The device
+// copy: [2][D] f64 (alpha, beta), then the [D] u32 selectors.
 int ensure_diskio_classes(yoda_t* h) {
-  if (h->b_cls_ready) return YODA_OK;
+  const bool keyed = modeb_keyed(h);
+  if (h->b_cls_ready && h->b_cls_keyed == keyed) return YODA_OK;
   pods_pack_rest(h);
   const uint32_t P = h->n_pods;
   const unsigned char* st = static_cast<const unsigned char*>(h->pod_stage.p);
   const uint64_t* al = reinterpret_cast<const uint64_t*>(st + h->pod_off[kPodAlpha]);
   const uint64_t* be = reinterpret_cast<const uint64_t*>(st + h->pod_off[kPodBeta]);
-  size_t cap = 64;
-  while (cap < 2 * (size_t)P) cap <<= 1;
-  std::vector<uint32_t> slot(cap, 0xffffffffu);  // class id, or empty
-  std::vector<uint64_t> ca, cb;
-  std::vector<uint32_t> cls(P);
-  for (uint32_t p = 0; p < P; ++p) {
-    const uint64_t a = al[p], b = be[p];
-    size_t i = (size_t)((a * 0x9e3779b97f4a7c15ull ^ b * 0xc2b2ae3d27d4eb4full) >> 20) & (cap - 1);
-    while (slot[i] != 0xffffffffu && !(ca[slot[i]] == a && cb[slot[i]] == b)) i = (i + 1) & (cap - 1);
-    if (slot[i] == 0xffffffffu) {
-      slot[i] = (uint32_t)ca.size();
-      ca.push_back(a);
-      cb.push_back(b);
-    }
-    cls[p] = slot[i];
-  }
-  const uint32_t D = (uint32_t)ca.size();
-  std::vector<uint64_t> cab(2 * (size_t)D);
-  std::copy(ca.begin(), ca.end(), cab.begin());
-  std::copy(cb.begin(), cb.end(), cab.begin() + D);
+  DiskClasses dc;
+  disk_build_classes(al, be, keyed ? h->h_cls.data() : nullptr, P, dc);
+  const uint32_t D = (uint32_t)dc.alpha.size();
+  std::vector<uint64_t> cab(2 * (size_t)D + ((size_t)D + 1) / 2, 0);
+  std::copy(dc.alpha.begin(), dc.alpha.end(), cab.begin());
+  std::copy(dc.beta.begin(), dc.beta.end(), cab.begin() + D);
+  if (D) std::memcpy(cab.data() + 2 * (size_t)D, dc.sel.data(), (size_t)D * 4);
   HIP_TRY(h, h->b_cab.ensure(std::max<size_t>(cab.size(), 1) * 8));
   HIP_TRY(h, h->b_cls.ensure(std::max<size_t>(P, 1) * 4));
   HIP_TRY(h, hipMemcpyAsync(h->b_cab.p, cab.data(), cab.size() * 8, hipMemcpyHostToDevice,
                             h->stream));
-  HIP_TRY(h, hipMemcpyAsync(h->b_cls.p, cls.data(), (size_t)P * 4, hipMemcpyHostToDevice,
+  HIP_TRY(h, hipMemcpyAsync(h->b_cls.p, dc.cls.data(), (size_t)P * 4, hipMemcpyHostToDevice,
                             h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));  // the host vectors go out of scope
   h->b_ncls = D;
   h->b_cls_ready = true;
+  h->b_cls_keyed = keyed;
+  return YODA_OK;
+}
+
+// The eligibility table and its counts, rebuilt when the node set or the candidate words changed
+// since the last build (b_elig_dirty), on the handle's stream ahead of the run's kernels.
+int ensure_modeb_elig(yoda_t* h) {
+  if (!h->b_elig_dirty) return YODA_OK;
+  const uint32_t N = h->n_nodes;
+  const size_t words = std::max<size_t>(((size_t)N + 63) / 64, 1);
+  std::vector<uint64_t> pres(words, 0);
+  for (uint32_t n = 0; n < N; ++n)
+    if (n >= h->h_absent.size() || !h->h_absent[n]) pres[n >> 6] |= 1ull << (n & 63u);
+  HIP_TRY(h, h->b_pres.ensure(words * 8));
+  HIP_TRY(h, h->b_elig.ensure(std::max<size_t>(N, 1) * sizeof(DiskElig)));
+  HIP_TRY(h, h->b_ecnt.ensure(kDiskSelCount * 4));
+  HIP_TRY(h, hipMemcpyAsync(h->b_pres.p, pres.data(), words * 8, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, launch_modeb_elig_build(h->cand_classes ? h->cand_w.as<uint64_t>() : nullptr,
+                                     h->b_pres.as<uint64_t>(), N, h->b_elig.as<DiskElig>(),
+                                     h->b_ecnt.as<uint32_t>(), h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));  // (the copy's source is pageable)
+  h->b_elig_dirty = false;
+  ++h->b_elig_builds;
   return YODA_OK;
 }
 
@@ -1302,6 +1343,12 @@ int phase1(yoda_t* h, int mode, uint64_t* maxima, uint32_t* counts,
   const uint32_t P = h->n_work;  // sorted positions of this run
   if (P == 0) return YODA_OK;
   if (mode == YODA_MODE_DISKIO) {
+    if (modeb_elig_on(h)) {  // n_feasible = |E|: the count of the pod's class, or of the present
+      if (int rc = ensure_modeb_elig(h)) return rc;
+      HIP_TRY(h, launch_fill_diskio_state_elig(P, modeb_cls_bytes(h), h->b_ecnt.as<uint32_t>(),
+                                               maxima, counts, h->stream));
+      return YODA_OK;
+    }
     HIP_TRY(h, launch_fill_diskio_state(P, h->n_nodes, maxima, counts, h->stream));
     return YODA_OK;
   }
@@ -1501,15 +1548,29 @@ int phase2(yoda_t* h, int mode, const uint64_t* maxima, const uint32_t* counts, 
     HIP_TRY(h, h->b_part.ensure(2 * (size_t)pl.C * D * 4));
     uint32_t* plc = h->b_part.as<uint32_t>();
     uint32_t* pix = plc + (size_t)pl.C * D;
+    const bool elig = modeb_elig_on(h);  // (its table: phase 1 of this run built it)
+    h->b_last_elig = elig;
+    h->b_last_ncls = D;
     if (e0) HIP_TRY(h, hipEventRecord(e0, h->stream));
-    HIP_TRY(h, launch_k2b(h->nodes_b.as<NodeRecB>(), h->n_nodes, h->b_cab.as<double>(), D,
-                          diskio_levels(), pl, plc, pix, h->stream));
+    if (elig) {
+      const uint32_t* csel = reinterpret_cast<const uint32_t*>(h->b_cab.as<double>() + 2 * (size_t)D);
+      HIP_TRY(h, launch_k2b_elig(h->nodes_b.as<NodeRecB>(), h->n_nodes, h->b_cab.as<double>(),
+                                 csel, D, diskio_levels(), pl, h->b_elig.as<DiskElig>(), plc, pix,
+                                 h->stream));
+    } else {
+      HIP_TRY(h, launch_k2b(h->nodes_b.as<NodeRecB>(), h->n_nodes, h->b_cab.as<double>(), D,
+                            diskio_levels(), pl, plc, pix, h->stream));
+    }
     if (e1) {
       HIP_TRY(h, hipEventRecord(e1, h->stream));
       h->ev_k2.emplace_back(e0, e1);
     }
-    HIP_TRY(h, launch_reduce2b(plc, pix, pl.C, D, h->b_cls.as<uint32_t>(), P, h->node_offset,
-                               best, idx, ties, low, h->stream));
+    if (elig)
+      HIP_TRY(h, launch_reduce2b_elig(plc, pix, pl.C, D, h->b_cls.as<uint32_t>(), P,
+                                      h->node_offset, best, idx, ties, low, h->stream));
+    else
+      HIP_TRY(h, launch_reduce2b(plc, pix, pl.C, D, h->b_cls.as<uint32_t>(), P, h->node_offset,
+                                 best, idx, ties, low, h->stream));
     return YODA_OK;
   }
   if (mode == YODA_MODE_SCV && !rows && (h->kbub_dirty || (h->kbub_loose && !h->greedy_active)) &&
@@ -1526,8 +1587,13 @@ int phase2(yoda_t* h, int mode, const uint64_t* maxima, const uint32_t* counts, 
     HIP_TRY(h, h->p_idx.ensure(cp * 4));
     HIP_TRY(h, h->p_ties.ensure(cp * 4));
     part = partials(h);
-    HIP_TRY(h, launch_k2b_rows(h->nodes_b.as<NodeRecB>(), h->n_nodes, pod_params(h), P, part,
-                               rows, h->stream));
+    if (modeb_elig_on(h))
+      HIP_TRY(h, launch_k2b_rows_elig(h->nodes_b.as<NodeRecB>(), h->n_nodes, pod_params(h),
+                                      modeb_cls_bytes(h), h->b_elig.as<DiskElig>(), P, part, rows,
+                                      h->stream));
+    else
+      HIP_TRY(h, launch_k2b_rows(h->nodes_b.as<NodeRecB>(), h->n_nodes, pod_params(h), P, part,
+                                 rows, h->stream));
   } else {
     // the block argmax K2 (N32 with summaries) marks the chunks it wrote (PodParams::cmask2)
     if (h->path == Path::N32 && h->has_k2sum && !rows) cmask2 = pod_params(h).cmask2;
@@ -2398,6 +2464,8 @@ int yoda_upload_nodes(yoda_t* h, const yoda_node_soa* nd, uint32_t node_offset, 
     h->n_absent = 0;
     h->cand_classes = 0;  // ... and a candidate of every pod (yoda_set_candidates: off)
     h->h_cand.clear();
+    h->b_elig_dirty = true;  // (Mode B's eligibility table is the old snapshot's)
+    h->b_elig_builds = 0;
     h->nodes_diskio = diskio;
     h->all_one_model = rows.n_one_model == N;
     h->all_uni4 = rows.n_uni4 == N;
@@ -2749,8 +2817,9 @@ int yoda_upload_pods(yoda_t* h, const yoda_pod_soa* pd) {
 // pad: a private run (yoda_run without the bitmask) -- it may take the counting sort and pad
 // the order's groups to whole waves; every other entry point keeps the radix order, one
 // sorted position per caller pod, reproducible across the shards of a batch.
-static int prepare_run(yoda_t* h, int mode, bool pad = false) {
-  int rc = check_ready(h, mode);
+// batch: a single-handle batch entry point (mode_b_absent).
+static int prepare_run(yoda_t* h, int mode, bool pad = false, bool batch = false) {
+  int rc = check_ready(h, mode, batch);
   if (rc) return rc;
   h->topk_ready = false;  // this run overwrites the bitmask and reciprocals
   h->draw_stage = 0;      // ... and the outcome a sharded draw would read
@@ -2836,6 +2905,12 @@ static int draw_pass(yoda_t* h, int mode) {
   a.pod_base = h->tie_pod_base;
   a.node_offset = h->node_offset;
   const bool diskio = mode == YODA_MODE_DISKIO;
+  if (diskio && modeb_elig_on(h)) {  // the draw among the top-scored nodes of E
+    HIP_TRY(h, launch_draw_diskio_elig(h->nodes_b.as<NodeRecB>(), h->n_nodes, pod_params(h),
+                                       modeb_cls_bytes(h), h->b_elig.as<DiskElig>(), a,
+                                       h->stream));
+    return YODA_OK;
+  }
   // (the U64 path's finalize scattered the maxima to the caller's order: unpermute_outputs)
   if (!diskio && h->generic && h->maxima_sorted)
     return fail(h, YODA_ERR_STATE, "draw pass: generic maxima still in sorted order");
@@ -2860,7 +2935,7 @@ static int run_private(yoda_t* h, int mode, uint32_t flags, bool draw) {
   const bool fast = mode == YODA_MODE_SCV && !(flags & YODA_RUN_BITMASK) &&
                     h->path == Path::N32 && h->has_k1sum && h->has_k2sum && !h->mem_ranks;
   h->fast_run = fast;
-  int rc = prepare_run(h, mode, (flags & YODA_RUN_BITMASK) == 0);
+  int rc = prepare_run(h, mode, (flags & YODA_RUN_BITMASK) == 0, true);
   h->fast_run = false;
   if (rc) return rc;
   const bool defer = fast && h->count_order;
@@ -2986,7 +3061,7 @@ int yoda_score_rows(yoda_t* h, int mode, uint32_t* bitmask_out, uint64_t n_bitma
 int yoda_score_rows_norm(yoda_t* h, int mode, uint32_t* bitmask_out, uint64_t n_bitmask_words,
                          int64_t* scores_out, uint64_t n_scores, int64_t* norm_out,
                          uint64_t n_norm) {
-  int rc = prepare_run(h, mode);
+  int rc = prepare_run(h, mode, false, true);
   if (rc) return rc;
   try {
     const uint32_t P = h->n_pods, N = h->n_nodes;
@@ -3041,7 +3116,17 @@ int yoda_score_rows_norm(yoda_t* h, int mode, uint32_t* bitmask_out, uint64_t n_
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (bitmask_out && W * P > 0) {
-      if (mode == YODA_MODE_DISKIO) {  // Filter is a pass-through: every node feasible
+      if (mode == YODA_MODE_DISKIO && modeb_elig_on(h)) {  // E, from the host mirrors
+        const bool keyed = modeb_keyed(h);
+        std::memset(bitmask_out, 0, (size_t)(W * P) * 4);
+        for (uint64_t p = 0; p < P; ++p) {
+          const uint32_t sel = keyed ? disk_sel(h->h_cls[p]) : kDiskSelAny;
+          for (uint32_t n = 0; n < N; ++n) {
+            const DiskElig e = disk_elig_of(!h->h_absent[n], h->cand_classes ? h->h_cand[n] : ~0ull);
+            if (disk_eligible(e, sel)) bitmask_out[p * W + (n >> 5)] |= 1u << (n & 31u);
+          }
+        }
+      } else if (mode == YODA_MODE_DISKIO) {  // Filter is a pass-through: every node feasible
         for (uint64_t p = 0; p < P; ++p)
           for (uint64_t w = 0; w < W; ++w) {
             const uint32_t bits = (w + 1) * 32 <= N ? 0xffffffffu : ((1u << (N % 32)) - 1);
@@ -3059,7 +3144,7 @@ int yoda_score_rows_norm(yoda_t* h, int mode, uint32_t* bitmask_out, uint64_t n_
 
 int yoda_eval(yoda_t* h, const yoda_pod_soa* pods, int mode, yoda_eval_out* out) {
   if (!h) return YODA_ERR_INVALID_ARG;
-  int rc = mode_b_absent(h, mode);  // (before the pods are replaced)
+  int rc = mode_b_absent(h, mode, true);  // (before the pods are replaced)
   if (rc) return rc;
   if ((rc = yoda_upload_pods(h, pods))) return rc;
   if ((rc = yoda_run(h, mode, 0))) return rc;
@@ -3646,7 +3731,7 @@ int yoda_greedy(yoda_t* h, const yoda_pod_soa* pods, int mode, uint32_t flags, i
   if (!pods || !pick) return fail(h, YODA_ERR_INVALID_ARG, "NULL pods or pick");
   if (!h->has_nodes) return fail(h, YODA_ERR_NO_NODES, "no node snapshot uploaded");
   if (int rc = cand_refuse(h, "yoda_greedy")) return rc;
-  if (int rc = mode_b_absent(h, mode)) return rc;
+  if (int rc = mode_b_absent(h, mode, true)) return rc;
   try {
     HIP_TRY(h, hipSetDevice(h->device));
     GreedyScope scope(h);
@@ -4153,6 +4238,7 @@ int yoda_set_node_present(yoda_t* h, uint32_t count, const uint32_t* nodes,
       h->h_absent[loc[ti]] = gone[ti];
       if (gone[ti]) ++h->n_absent; else --h->n_absent;
     }
+    h->b_elig_dirty = true;
     if (!n32) return YODA_OK;
     // The G maxima are those of the present nodes (a wave whose maxima are G's takes the G-table
     // K2; with a stale G none would).  A returning node can only raise them (above); a field
@@ -4193,6 +4279,7 @@ namespace {
 // A change of the candidate state: the pending outcomes are the old candidates', a sharded
 // step's pending exact merge included.
 void cand_invalidate(yoda_t* h) {
+  h->b_cls_ready = false;  // (Mode B's classes are keyed by the pods' candidate classes)
   h->k3_pending = false;
   h->ran = false;
   h->phase1_done = false;
@@ -4220,7 +4307,10 @@ int yoda_set_candidates(yoda_t* h, uint32_t n_classes, const uint64_t* words) {
   if (n_classes > YODA_MAX_CAND_CLASSES)
     return fail(h, YODA_ERR_INVALID_ARG, "n_classes above YODA_MAX_CAND_CLASSES");
   if (n_classes == 0) {
-    if (h->cand_classes) cand_invalidate(h);
+    if (h->cand_classes) {
+      cand_invalidate(h);
+      h->b_elig_dirty = true;
+    }
     h->cand_classes = 0;
     h->h_cand.clear();
     return YODA_OK;
@@ -4240,6 +4330,7 @@ int yoda_set_candidates(yoda_t* h, uint32_t n_classes, const uint64_t* words) {
       HIP_TRY(h, h->cand_zt_p.ensure(nb * 8));
     }
     cand_invalidate(h);
+    h->b_elig_dirty = true;
     h->cand_classes = 0;  // (off until the tables are whole)
     h->h_cand.assign(words, words + N);
     if (N) {
@@ -4296,6 +4387,7 @@ int yoda_update_candidates(yoda_t* h, uint32_t count, const uint32_t* nodes,
     std::memcpy(st, loc.data(), (size_t)cnt * 4);
     std::memcpy(st + o_val, val.data(), (size_t)cnt * 8);
     for (uint32_t t = 0; t < cnt; ++t) h->h_cand[loc[t]] = val[t];
+    h->b_elig_dirty = true;
     HIP_TRY(h, hipMemcpyAsync(h->upd_node.p, st, bytes, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipEventRecord(h->upd_event, h->stream));
     h->upd_pending = true;
@@ -4349,6 +4441,23 @@ int yoda_set_pod_classes(yoda_t* h, uint32_t n_pods, const uint8_t* cls) {
   } catch (...) {
     return fail(h, YODA_ERR_INVALID_ARG, "unexpected exception");
   }
+}
+
+int yoda_mode_b_follow(yoda_t* h, int enable) {
+  if (!h) return YODA_ERR_INVALID_ARG;
+  const bool on = enable != 0;
+  if (on != h->b_follow) cand_invalidate(h);  // the pending outcomes are the other reading's
+  h->b_follow = on;
+  return YODA_OK;
+}
+
+int yoda_mode_b_info(const yoda_t* h, uint32_t* out) {
+  if (!h || !out) return YODA_ERR_INVALID_ARG;
+  out[0] = h->b_follow ? 1u : 0u;
+  out[1] = h->b_last_ncls;
+  out[2] = h->b_last_elig ? 1u : 0u;
+  out[3] = h->b_elig_builds;
+  return YODA_OK;
 }
 
 int yoda_candidates_profile(yoda_t* h, double* narrow_ms) {

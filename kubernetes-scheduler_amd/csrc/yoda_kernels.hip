@@ -25,6 +25,7 @@
 
 #include "yoda_layout.h"
 #include "yoda_launch.h"
+#include "yoda_modeb.h"
 
 // The YODA_ABL_* ablations remove work whose results the path needs (written masks, summaries,
 // whole classes): counter and timing builds only.  They compile only beside the A/B knobs
@@ -4345,32 +4346,7 @@ __global__ __launch_bounds__(kBlock) void k2b_rows(const NodeRecB* __restrict__ 
 // operations, two compares.  A lane keeps, over nodes in increasing order, the best level
 // seen, its node count and its first (lowest) node; level 0 counts nothing while running
 // (every node is >= 0, NaN included) and is settled at the end.
-struct DiskAcc {
-  uint32_t lev, cnt, idx;
-  double tc, tu;  // count threshold of the current level (-1 at level 0), the next level's
-};
-
-__device__ __forceinline__ void disk_init(DiskAcc& s, const double* lv) {
-  s.lev = 0;
-  s.cnt = 0;
-  s.idx = 0xffffffffu;
-  s.tc = -1.0;
-  s.tu = lv[1];
-}
-
-__device__ __forceinline__ void disk_step(DiskAcc& s, double ad, uint32_t n, const double* lv) {
-  s.cnt += (ad <= s.tc) ? 1u : 0u;
-  if (ad <= s.tu) {  // a higher level (rare once the first nodes are seen)
-    uint32_t L = 1;  // the levels are nested: |d| <= t[k] for every k up to its level
-#pragma unroll
-    for (int k = 2; k <= 10; ++k) L += (ad <= lv[k]) ? 1u : 0u;
-    s.lev = L;
-    s.cnt = 1;
-    s.idx = n;
-    s.tc = lv[L];
-    s.tu = lv[L + 1];
-  }
-}
+// (DiskAcc, disk_init, disk_step: yoda_modeb.h, shared with the host.)
 
 // Lane = class: each lane runs CPL classes over the chunk's nodes, one node record per
 // iteration read by a scalar (wave-uniform) load.
@@ -4534,6 +4510,281 @@ __global__ __launch_bounds__(kBlock) void k_reduce2b(const uint32_t* __restrict_
   idx_out[p] = bi == 0xffffffffu ? bi : bi + node_offset;
   ties_out[p] = bc;
   low_out[p] = 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// K2B with eligibility (yoda_mode_b_follow): pod class c walks only the nodes of
+// E = present and candidates of its selector csel[c] (yoda_modeb.h DiskElig).  Siblings of the
+// kernels above, launched only while a node is absent or a pod names a candidate class: the
+// unrestricted kernels stay as they are.  A lane keeps, beside its accumulator, the eligible
+// nodes it stepped over and the first of them (DiskSeen): level 0 settles from those, and a
+// (chunk, class) with no eligible node writes count 0, which every merge skips.
+
+// The eligibility table and its 65 counts (nodes of each class, present nodes) from the candidate
+// words (upload order; nullptr: candidates off) and the presence bitmap.  cnt is zeroed by the
+// caller; integer sums, so the table is the same whatever the order of the atomics.
+__global__ __launch_bounds__(kBlock) void k_modeb_elig_build(const uint64_t* __restrict__ words,
+                                                             const uint64_t* __restrict__ pres,
+                                                             uint32_t n_nodes,
+                                                             DiskElig* __restrict__ elig,
+                                                             uint32_t* __restrict__ cnt) {
+  const uint32_t lane = lane_id();
+  uint32_t mine = 0, any = 0;  // lane c: nodes of class c seen by this wave; lane 0: present ones
+  // (the bound is wave-uniform: every lane of a wave takes part in each ballot)
+  for (uint32_t base = blockIdx.x * kBlock + (threadIdx.x & ~(kWave - 1u)); base < n_nodes;
+       base += gridDim.x * kBlock) {
+    const uint32_t n = base + lane;
+    DiskElig e{0ull, 0ull};
+    if (n < n_nodes) {
+      const bool present = ((pres[n >> 6] >> (n & 63u)) & 1ull) != 0ull;
+      e = disk_elig_of(present, words ? words[n] : ~0ull);
+      elig[n] = e;
+    }
+    for (uint32_t c = 0; c < 64u; ++c) {
+      const uint32_t k = (uint32_t)__builtin_popcountll(ballot(((e.lo >> c) & 1ull) != 0ull));
+      mine += lane == c ? k : 0u;
+    }
+    any += (uint32_t)__builtin_popcountll(ballot(e.hi != 0ull));
+  }
+  if (mine) atomicAdd(&cnt[lane], mine);
+  if (lane == 0 && any) atomicAdd(&cnt[kDiskSelAny], any);
+}
+
+// Lane = class: the lanes of a wave walk the same nodes under different selectors, so the step
+// is branch-free (disk_step_masked) and the level-0 settle walks the words again when it must.
+template <int CPL>
+__global__ __launch_bounds__(kBlock) void k2b_class_lanes_elig(
+    const NodeRecB* __restrict__ nodes, uint32_t n_nodes, uint32_t chunk_nodes,
+    const double* __restrict__ cab, const uint32_t* __restrict__ csel, uint32_t n_cls,
+    DiskLevels lvs, const DiskElig* __restrict__ elig, uint32_t* __restrict__ plc,
+    uint32_t* __restrict__ pidx) {
+#pragma clang fp contract(off)
+  __shared__ double lv[12];
+  if (threadIdx.x < 12) lv[threadIdx.x] = lvs.t[threadIdx.x];
+  __syncthreads();
+  const uint32_t chunk = blockIdx.y;
+  const uint32_t n0 = chunk * chunk_nodes;
+  const uint32_t n1 = min(n0 + chunk_nodes, n_nodes);
+  const uint32_t c0 = blockIdx.x * (kBlock * CPL) + threadIdx.x;
+  double al[CPL], be[CPL];
+  DiskSelMask sm[CPL];
+  DiskAcc s[CPL];
+#pragma unroll
+  for (int j = 0; j < CPL; ++j) {
+    const uint32_t c = c0 + j * kBlock;
+    al[j] = c < n_cls ? cab[c] : 0.0;
+    be[j] = c < n_cls ? cab[(size_t)n_cls + c] : 0.0;
+    sm[j] = disk_sel_mask(c < n_cls ? csel[c] : kDiskSelAny);
+    disk_init(s[j], lv);
+  }
+  // 8 node records and their eligibility words per trip: wave-uniform loads issued together
+  constexpr int kTrip = 8;
+  uint32_t n = n0;
+  for (; n + kTrip <= n1; n += kTrip) {
+    NodeRecB r[kTrip];
+    DiskElig e[kTrip];
+#pragma unroll
+    for (int i = 0; i < kTrip; ++i) {
+      r[i] = nodes[n + i];
+      e[i] = elig[n + i];
+    }
+#pragma unroll
+    for (int i = 0; i < kTrip; ++i) {
+#pragma unroll
+      for (int j = 0; j < CPL; ++j) {
+        const double a = al[j] * r[i].v;
+        const double b = be[j] * r[i].u;
+        disk_step_masked(s[j], disk_eligible(e[i], sm[j]), fabs(a - b), n + i, lv);
+      }
+    }
+  }
+  for (; n < n1; ++n) {
+    const NodeRecB r = nodes[n];
+    const DiskElig e = elig[n];
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) {
+      const double a = al[j] * r.v;
+      const double b = be[j] * r.u;
+      disk_step_masked(s[j], disk_eligible(e, sm[j]), fabs(a - b), n, lv);
+    }
+  }
+  // level 0 is settled from the eligible nodes of the chunk and the first of them
+  DiskSeen sn[CPL];
+  bool zero = false;
+#pragma unroll
+  for (int j = 0; j < CPL; ++j) {
+    disk_seen_init(sn[j]);
+    zero = zero || s[j].lev == 0u;
+  }
+  if (ballot(zero) != 0ull) {  // (wave-uniform: the words stay wave-uniform loads)
+    for (n = n0; n < n1; ++n) {
+      const DiskElig e = elig[n];
+#pragma unroll
+      for (int j = 0; j < CPL; ++j) disk_seen_add(sn[j], disk_eligible(e, sm[j]), n);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < CPL; ++j) {
+    const uint32_t c = c0 + j * kBlock;
+    if (c >= n_cls) continue;
+    uint32_t cnt, idx;
+    disk_settle(s[j], sn[j], cnt, idx);
+    plc[(size_t)chunk * n_cls + c] = disk_pack(s[j].lev, cnt);
+    pidx[(size_t)chunk * n_cls + c] = idx;
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void k2b_node_lanes_elig(
+    const NodeRecB* __restrict__ nodes, uint32_t n_nodes, uint32_t chunk_nodes,
+    const double* __restrict__ cab, const uint32_t* __restrict__ csel, uint32_t n_cls,
+    DiskLevels lvs, const DiskElig* __restrict__ elig, uint32_t* __restrict__ plc,
+    uint32_t* __restrict__ pidx) {
+#pragma clang fp contract(off)
+  __shared__ double lv[12];
+  __shared__ uint32_t red[3][kBlock / kWave];
+  if (threadIdx.x < 12) lv[threadIdx.x] = lvs.t[threadIdx.x];
+  __syncthreads();
+  const uint32_t chunk = blockIdx.x, c = blockIdx.y;
+  const uint32_t n0 = chunk * chunk_nodes;
+  const uint32_t n1 = min(n0 + chunk_nodes, n_nodes);
+  const double al = cab[c], be = cab[(size_t)n_cls + c];
+  const uint32_t sel = csel[c];
+  DiskAcc s;
+  DiskSeen sn;
+  disk_init(s, lv);
+  disk_seen_init(sn);
+  for (uint32_t n = n0 + threadIdx.x; n < n1; n += kBlock) {
+    if (!disk_eligible(elig[n], sel)) continue;
+    const NodeRecB r = nodes[n];
+    const double a = al * r.v;
+    const double b = be * r.u;
+    disk_step_elig(s, sn, fabs(a - b), n, lv);
+  }
+  uint32_t mc, mi;
+  disk_settle(s, sn, mc, mi);
+  // the wave's best level among the lanes that hold an eligible node
+  const uint32_t L = wave_max_u32(mc ? s.lev : 0u);
+  uint32_t cnt = s.lev == L ? mc : 0u;
+  uint32_t idx = (s.lev == L && mc) ? mi : 0xffffffffu;
+#pragma unroll
+  for (int o = kWave / 2; o > 0; o >>= 1) {
+    cnt += (uint32_t)__shfl_xor((int)cnt, o, kWave);
+    idx = min(idx, (uint32_t)__shfl_xor((int)idx, o, kWave));
+  }
+  const uint32_t w = threadIdx.x / kWave;
+  if (lane_id() == 0) {
+    red[0][w] = L;
+    red[1][w] = cnt;
+    red[2][w] = idx;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  DiskBest b;
+  disk_best_init(b);
+  for (int i = 0; i < kBlock / kWave; ++i) disk_merge_any(b, red[0][i], red[1][i], red[2][i]);
+  // (no eligible node of this class in the chunk: count 0, skipped by the chunk merge)
+  plc[(size_t)chunk * n_cls + c] = b.cnt ? disk_pack((uint32_t)b.lev, b.cnt) : 0u;
+  pidx[(size_t)chunk * n_cls + c] = b.idx;
+}
+
+// k_reduce2b over partials that may be empty (count 0): disk_merge_chunk skips them, so a class
+// with no eligible node at all ends at best -1, no node, count 0.
+__global__ __launch_bounds__(kBlock) void k_reduce2b_elig(const uint32_t* __restrict__ plc,
+                                                          const uint32_t* __restrict__ pidx,
+                                                          uint32_t C, uint32_t n_cls,
+                                                          const uint32_t* __restrict__ cls,
+                                                          uint32_t n_pods, uint32_t node_offset,
+                                                          int64_t* __restrict__ best_out,
+                                                          uint32_t* __restrict__ idx_out,
+                                                          uint32_t* __restrict__ ties_out,
+                                                          int64_t* __restrict__ low_out) {
+  const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+  if (p >= n_pods) return;
+  const uint32_t c = cls[p];
+  DiskBest b;
+  disk_best_init(b);
+  for (uint32_t k = 0; k < C; ++k)
+    disk_merge_chunk(b, plc[(size_t)k * n_cls + c], pidx[(size_t)k * n_cls + c]);
+  best_out[p] = b.lev;
+  idx_out[p] = b.idx == 0xffffffffu ? b.idx : b.idx + node_offset;
+  ties_out[p] = b.cnt;
+  low_out[p] = 0;
+}
+
+// k_fill_diskio_state with eligibility: n_feasible[p] = the count of the pod's selector.
+// cls: the pods' candidate class bytes (caller order: Mode B runs are never reordered), or
+// nullptr: every pod YODA_CAND_ANY.
+__global__ __launch_bounds__(kBlock) void k_fill_diskio_state_elig(
+    uint32_t n_pods, const uint8_t* __restrict__ cls, const uint32_t* __restrict__ cnt,
+    uint64_t* __restrict__ maxima, uint32_t* __restrict__ counts) {
+  const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+  if (p >= n_pods) return;
+  for (int f = 0; f < 6; ++f) maxima[(size_t)f * n_pods + p] = 1;
+  counts[p] = cnt[cls ? disk_sel(cls[p]) : kDiskSelAny];
+  counts[(size_t)n_pods + p] = 0;
+}
+
+// k2b_rows with eligibility: a node outside the pod's E keeps the row's -1 (the caller's fill)
+// and stays out of best, low, idx and ties.
+__global__ __launch_bounds__(kBlock) void k2b_rows_elig(
+    const NodeRecB* __restrict__ nodes, uint32_t n_nodes, const double* __restrict__ alpha_in,
+    const double* __restrict__ beta_in, const uint8_t* __restrict__ cls,
+    const DiskElig* __restrict__ elig, uint32_t n_pods, double* __restrict__ pbest,
+    uint32_t* __restrict__ pidx, uint32_t* __restrict__ pties, double* __restrict__ plow,
+    int64_t* __restrict__ rows) {
+#pragma clang fp contract(off)
+  __shared__ double s_best[kBlock / kWave], s_low[kBlock / kWave];
+  __shared__ uint32_t s_idx[kBlock / kWave], s_ties[kBlock / kWave];
+  const uint32_t c = blockIdx.x, n = c * kBlock + threadIdx.x, w = threadIdx.x >> 6;
+  const bool in = n < n_nodes;
+  const NodeRecB r = in ? nodes[n] : NodeRecB{0.0, 0.0};
+  const DiskElig e = in ? elig[n] : DiskElig{0ull, 0ull};
+  for (uint32_t p = 0; p < n_pods; ++p) {
+    const bool v = disk_eligible(e, cls ? disk_sel(cls[p]) : kDiskSelAny);
+    const double alpha = alpha_in[p], beta = beta_in[p];
+    const double a = alpha * r.v;
+    const double b = beta * r.u;
+    const double l = fabs(a - b);  // algorithm.go:110
+    const double t = 10.0 * l;
+    const double sc = 10.0 - t;    // :111
+    const double score = (sc >= 1.0) ? __builtin_trunc(sc) : 0.0;
+    if (v) rows[(size_t)n * n_pods + p] = (int64_t)score;
+    double best = v ? score : -1.0, low = v ? score : 1.0e300;
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) {
+      best = fmax(best, __shfl_xor(best, o, kWave));
+      low = fmin(low, __shfl_xor(low, o, kWave));
+    }
+    const bool at = v && score == best;
+    const uint64_t bb = ballot(at);
+    if ((threadIdx.x & (kWave - 1)) == 0) {
+      s_best[w] = best;
+      s_low[w] = low;
+      s_idx[w] = bb ? (c * kBlock + w * kWave + (uint32_t)__builtin_ctzll(bb)) : 0xffffffffu;
+      s_ties[w] = (uint32_t)__builtin_popcountll(bb);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      double B = -1.0, L = 1.0e300;
+      uint32_t I = 0xffffffffu, T = 0;
+      for (int k = 0; k < kBlock / kWave; ++k) {  // waves in node order: strict '>' keeps lowest
+        if (s_best[k] > B) {
+          B = s_best[k];
+          I = s_idx[k];
+          T = s_ties[k];
+        } else if (s_best[k] == B && s_ties[k]) {
+          T += s_ties[k];
+        }
+        L = fmin(L, s_low[k]);
+      }
+      const size_t o = (size_t)c * n_pods + p;
+      pbest[o] = B;
+      pidx[o] = I;
+      pties[o] = T;
+      plow[o] = L;
+    }
+    __syncthreads();
+  }
 }
 
 // Per-pod merge of K2 chunk partials.  Chunks are in node order, so on equal scores the
@@ -5898,6 +6149,59 @@ hipError_t launch_reduce2b(const uint32_t* plc, const uint32_t* pidx, uint32_t C
   return hipGetLastError();
 }
 
+// The eligibility forms (yoda_mode_b_follow): the same plan and grids over the sibling kernels.
+hipError_t launch_modeb_elig_build(const uint64_t* words, const uint64_t* pres, uint32_t n_nodes,
+                                   DiskElig* elig, uint32_t* cnt, hipStream_t s) {
+  hipError_t e = hipMemsetAsync(cnt, 0, kDiskSelCount * 4, s);
+  if (e != hipSuccess || n_nodes == 0) return e;
+  const uint32_t blocks = std::min<uint32_t>((n_nodes + kBlock - 1) / kBlock, 128u);
+  hipLaunchKernelGGL(k_modeb_elig_build, dim3(blocks), dim3(kBlock), 0, s, words, pres, n_nodes,
+                     elig, cnt);
+  return hipGetLastError();
+}
+
+hipError_t launch_k2b_elig(const NodeRecB* nodes, uint32_t n_nodes, const double* cab,
+                           const uint32_t* csel, uint32_t n_cls, const DiskLevels& lv,
+                           const DiskPlan& pl, const DiskElig* elig, uint32_t* plc, uint32_t* pidx,
+                           hipStream_t s) {
+  if (pl.C == 0) return hipSuccess;
+  if (pl.node_lanes) {
+    hipLaunchKernelGGL(k2b_node_lanes_elig, dim3(pl.C, n_cls), dim3(kBlock), 0, s, nodes, n_nodes,
+                       pl.chunk, cab, csel, n_cls, lv, elig, plc, pidx);
+  } else {
+    const uint32_t cb = (n_cls + kBlock * kDiskCPL - 1) / (kBlock * kDiskCPL);
+    hipLaunchKernelGGL(k2b_class_lanes_elig<kDiskCPL>, dim3(cb, pl.C), dim3(kBlock), 0, s, nodes,
+                       n_nodes, pl.chunk, cab, csel, n_cls, lv, elig, plc, pidx);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_reduce2b_elig(const uint32_t* plc, const uint32_t* pidx, uint32_t C,
+                                uint32_t n_cls, const uint32_t* cls, uint32_t n_pods,
+                                uint32_t node_offset, int64_t* best, uint32_t* idx, uint32_t* ties,
+                                int64_t* low, hipStream_t s) {
+  hipLaunchKernelGGL(k_reduce2b_elig, pod_grid(n_pods), dim3(kBlock), 0, s, plc, pidx, C, n_cls,
+                     cls, n_pods, node_offset, best, idx, ties, low);
+  return hipGetLastError();
+}
+
+hipError_t launch_fill_diskio_state_elig(uint32_t n_pods, const uint8_t* cls, const uint32_t* cnt,
+                                         uint64_t* maxima, uint32_t* counts, hipStream_t s) {
+  hipLaunchKernelGGL(k_fill_diskio_state_elig, pod_grid(n_pods), dim3(kBlock), 0, s, n_pods, cls,
+                     cnt, maxima, counts);
+  return hipGetLastError();
+}
+
+hipError_t launch_k2b_rows_elig(const NodeRecB* nodes, uint32_t n_nodes, const PodParams& pp,
+                                const uint8_t* cls, const DiskElig* elig, uint32_t n_pods,
+                                const Partials& part, int64_t* rows, hipStream_t s) {
+  if (n_nodes == 0 || n_pods == 0) return hipSuccess;
+  hipLaunchKernelGGL(k2b_rows_elig, dim3((n_nodes + kBlock - 1) / kBlock), dim3(kBlock), 0, s,
+                     nodes, n_nodes, pp.alpha, pp.beta, cls, elig, n_pods, part.best_f, part.idx,
+                     part.ties, part.low_f, rows);
+  return hipGetLastError();
+}
+
 // rows [N][P] (coalesced for the kernels) -> [P][N] (host API layout).
 __global__ __launch_bounds__(kBlock) void k_rows_transpose(const int64_t* __restrict__ in,
                                                            uint32_t n_nodes, uint32_t n_pods,
@@ -6555,6 +6859,45 @@ __global__ __launch_bounds__(kBlock) void k_draw_diskio(const NodeRecB* __restri
   }
 }
 
+// k_draw_diskio of a single handle with eligibility (yoda_mode_b_follow): only the nodes of the
+// pod's E enter the MIN key.  cls: the pods' class bytes (caller order), nullptr: every pod ANY.
+__global__ __launch_bounds__(kBlock) void k_draw_diskio_elig(const NodeRecB* __restrict__ nodes,
+                                                             uint32_t n_nodes, uint32_t chunk_nodes,
+                                                             const double* __restrict__ alpha_in,
+                                                             const double* __restrict__ beta_in,
+                                                             const uint8_t* __restrict__ cls,
+                                                             const DiskElig* __restrict__ elig,
+                                                             DrawArgs a) {
+#pragma clang fp contract(off)
+  const uint32_t nl = min(*a.n_list, a.n_work);
+  const uint32_t n0 = blockIdx.y * chunk_nodes;
+  const uint32_t n1 = min(n0 + chunk_nodes, n_nodes);
+  for (uint32_t i = blockIdx.x; i < nl; i += gridDim.x) {
+    const uint32_t p = a.list[i];
+    const uint32_t o = a.perm ? a.perm[p] : p;
+    const double best = (double)a.best[o];
+    const double alpha = alpha_in[p], beta = beta_in[p];
+    const uint32_t sel = cls ? disk_sel(cls[o]) : kDiskSelAny;
+    const uint64_t st = tie_pod_state(a.seed, a.pod_base + o);
+    uint64_t key = ~0ull;
+    for (uint32_t n = n0 + threadIdx.x; n < n1; n += kBlock) {
+      if (!disk_eligible(elig[n], sel)) continue;
+      const NodeRecB r = nodes[n];
+      const double x = alpha * r.v;
+      const double y = beta * r.u;
+      const double l = fabs(x - y);  // :110
+      const double t = 10.0 * l;
+      const double s = 10.0 - t;     // :111
+      const double score = (s >= 1.0) ? __builtin_trunc(s) : 0.0;
+      if (score == best) {
+        const uint64_t k = tie_key(st, a.node_offset + n);
+        key = k < key ? k : key;
+      }
+    }
+    draw_fold(a.keys, i, key);
+  }
+}
+
 __global__ __launch_bounds__(kBlock) void k_draw_write(DrawArgs a) {
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= min(*a.n_list, a.n_work)) return;
@@ -6616,6 +6959,23 @@ hipError_t launch_draw(int K, Path path, int mode_diskio, const unsigned char* n
   e = launch_draw_keys<false>(K, path, mode_diskio, nodes, nodes_b, n_nodes, pp, rcp, maxima, low,
                               ms, a, s);
   if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_draw_write, pod_grid(a.n_work), dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+// launch_draw for a Mode B run with eligibility: the same list and write passes around
+// k_draw_diskio_elig.
+hipError_t launch_draw_diskio_elig(const NodeRecB* nodes_b, uint32_t n_nodes, const PodParams& pp,
+                                   const uint8_t* cls, const DiskElig* elig, const DrawArgs& a,
+                                   hipStream_t s) {
+  if (a.n_work == 0 || n_nodes == 0) return hipSuccess;
+  hipError_t e = hipMemsetAsync(a.n_list, 0, 4, s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_draw_list, pod_grid(a.n_work), dim3(kBlock), 0, s, a);
+  const uint32_t gx = std::min(a.n_work, kDrawMaxStrides);
+  const uint32_t C = (n_nodes + kDrawChunk - 1) / kDrawChunk;
+  hipLaunchKernelGGL(k_draw_diskio_elig, dim3(gx, C), dim3(kBlock), 0, s, nodes_b, n_nodes,
+                     kDrawChunk, pp.alpha, pp.beta, cls, elig, a);
   hipLaunchKernelGGL(k_draw_write, pod_grid(a.n_work), dim3(kBlock), 0, s, a);
   return hipGetLastError();
 }

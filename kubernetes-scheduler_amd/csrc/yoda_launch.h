@@ -60,6 +60,29 @@ hipError_t launch_reduce2b(const uint32_t* plc, const uint32_t* pidx, uint32_t C
                            const uint32_t* cls, uint32_t n_pods, uint32_t node_offset,
                            int64_t* best, uint32_t* idx, uint32_t* ties, int64_t* low,
                            hipStream_t s);
+// Mode B with eligibility (yoda_mode_b_follow; yoda_modeb.h): the table build (elig [n_nodes],
+// cnt [kDiskSelCount], from the candidate words -- nullptr: off -- and the presence bitmap), and
+// the siblings of the five launches above and of launch_draw.  csel: [n_cls] selectors; cls: the
+// pods' class bytes (nullptr: every pod YODA_CAND_ANY).
+struct DiskElig;
+hipError_t launch_modeb_elig_build(const uint64_t* words, const uint64_t* pres, uint32_t n_nodes,
+                                   DiskElig* elig, uint32_t* cnt, hipStream_t s);
+hipError_t launch_k2b_elig(const NodeRecB* nodes, uint32_t n_nodes, const double* cab,
+                           const uint32_t* csel, uint32_t n_cls, const DiskLevels& lv,
+                           const DiskPlan& pl, const DiskElig* elig, uint32_t* plc, uint32_t* pidx,
+                           hipStream_t s);
+hipError_t launch_reduce2b_elig(const uint32_t* plc, const uint32_t* pidx, uint32_t C,
+                                uint32_t n_cls, const uint32_t* cls, uint32_t n_pods,
+                                uint32_t node_offset, int64_t* best, uint32_t* idx, uint32_t* ties,
+                                int64_t* low, hipStream_t s);
+hipError_t launch_fill_diskio_state_elig(uint32_t n_pods, const uint8_t* cls, const uint32_t* cnt,
+                                         uint64_t* maxima, uint32_t* counts, hipStream_t s);
+hipError_t launch_k2b_rows_elig(const NodeRecB* nodes, uint32_t n_nodes, const PodParams& pp,
+                                const uint8_t* cls, const DiskElig* elig, uint32_t n_pods,
+                                const Partials& part, int64_t* rows, hipStream_t s);
+hipError_t launch_draw_diskio_elig(const NodeRecB* nodes_b, uint32_t n_nodes, const PodParams& pp,
+                                   const uint8_t* cls, const DiskElig* elig, const DrawArgs& a,
+                                   hipStream_t s);
 hipError_t launch_rows_transpose(const int64_t* in, uint32_t n_nodes, uint32_t n_pods,
                                  const uint32_t* perm,
                                  int64_t* out, hipStream_t s);

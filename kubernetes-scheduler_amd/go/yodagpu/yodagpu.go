@@ -403,6 +403,20 @@ func (g *Handle) CandidatesInfo() ([3]uint32, error) {
 	return out, check(g.h, rc, "yoda_candidates_info")
 }
 
+// ModeBFollow makes Mode B's batch path (ScoreRow, Batch, Greedy with absent nodes) follow
+// SetNodePresent and the candidate classes (yoda_mode_b_follow): a pod's cycle runs over the
+// present nodes that are candidates of its class.  Off, the default, Mode B refuses while a node
+// is absent or candidates are on.  A setting: it stays across uploads.  ShardedBatch and
+// ShardedGreedy keep refusing either way.
+// Like the rest of this file, not compiled in this repository (no Go toolchain in the image).
+func (g *Handle) ModeBFollow(enable bool) error {
+	on := C.int(0)
+	if enable {
+		on = 1
+	}
+	return check(g.h, C.yoda_mode_b_follow(g.h, on), "yoda_mode_b_follow")
+}
+
 // packPods parses the scv/* labels and the diskIO annotation with the reference's own
 // helpers (filter.go:60-74, sort.go:12-18, algorithm.go:103-104) into the C-side
 // yoda_pod_soa arrays.

@@ -90,6 +90,8 @@ _SIGS = {
     "yoda_set_pod_classes": ([_vp, _u32, _vp], C.c_int),
     "yoda_candidates_info": ([_vp, _vp], C.c_int),
     "yoda_candidates_profile": ([_vp, C.POINTER(C.c_double)], C.c_int),
+    "yoda_mode_b_follow": ([_vp, C.c_int], C.c_int),
+    "yoda_mode_b_info": ([_vp, _vp], C.c_int),
     "yoda_snapshot_check": ([_vp, _vp, _vp], C.c_int),
     "yoda_shard_topk": ([_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp], C.c_int),
     "yoda_shard_topk_depth": ([_vp], C.c_int),
@@ -498,7 +500,8 @@ class Yoda:
         """Take the listed GLOBAL node ids (others ignored) out of the uploaded snapshot
         (present 0) or back in (non-zero), no re-upload (yoda_set_node_present): while absent a
         node is in no Filter, no PreScore maximum and no pick of Mode A; Mode B raises YodaError
-        (YODA_ERR_STATE) until every node is back.  `present`: one flag per id, or a scalar for
+        (YODA_ERR_STATE) until every node is back, unless mode_b_follow is on.  `present`: one flag
+        per id, or a scalar for
         all of them; a repeated id keeps its last flag."""
         n = np.ascontiguousarray(ids, np.uint32).ravel()
         f = np.ascontiguousarray(np.broadcast_to(np.asarray(present, np.uint8), n.shape)
@@ -520,7 +523,8 @@ class Yoda:
         one uint64 per node of this handle, bit c set when the node is a candidate for class c;
         n_classes 1..64.  n_classes 0 (words may be None) turns candidates off, as upload_nodes
         does.  The PreScore maxima do not move; Filter, counts, scores and picks follow the
-        candidates.  While on, Mode B, greedy, shard and comm calls raise YODA_ERR_STATE."""
+        candidates.  While on, greedy, shard and comm calls raise YODA_ERR_STATE, and so does Mode B
+        unless mode_b_follow is on."""
         w = None if words is None else np.ascontiguousarray(words, np.uint64).ravel()
         if w is not None and n_classes and w.size != self.n_nodes:
             raise ValueError("set_candidates: one word per node of this handle")
@@ -551,6 +555,22 @@ class Yoda:
         of every class) -- yoda_candidates_info; host only."""
         out = np.zeros(3, np.uint32)
         self._check(lib().yoda_candidates_info(self._h, _np_ptr(out)), "yoda_candidates_info")
+        return tuple(int(v) for v in out)
+
+    def mode_b_follow(self, enable: bool = True):
+        """Mode B's single-handle batch path (run, eval, download, score_rows, the draw, greedy
+        with absent nodes) follows set_node_present and the candidate classes: pod p's cycle is
+        the reference's on the nodes of E(p) = present and candidates of p's class
+        (yoda_mode_b_follow).  Off, the default: Mode B raises YODA_ERR_STATE while a node is
+        absent or candidates are on.  A setting: it stays across uploads."""
+        self._check(lib().yoda_mode_b_follow(self._h, 1 if enable else 0), "yoda_mode_b_follow")
+
+    def mode_b_info(self):
+        """(enabled, effective pod classes D' of the last Mode B batch run, 1 if that run took the
+        eligibility kernels, eligibility-table builds since the upload) -- yoda_mode_b_info; host
+        only."""
+        out = np.zeros(4, np.uint32)
+        self._check(lib().yoda_mode_b_info(self._h, _np_ptr(out)), "yoda_mode_b_info")
         return tuple(int(v) for v in out)
 
     def candidates_profile(self) -> float:
