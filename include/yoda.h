@@ -418,7 +418,10 @@ int yoda_k2_trace_read(yoda_t* h, uint64_t* out, uint64_t n_slots);
  * "assume" of SURVEY §3.4).  YODA_GREEDY_CARD_CAPACITY additionally decrements the picked
  * node's CardNumber by the pod's number (saturating at 0): a build-defined extension,
  * batched as well (a window restarts at the first pod the capacity certificate cannot
- * clear).  The uploaded snapshot is left unchanged. */
+ * clear).  The uploaded snapshot is left unchanged.
+ *   While candidate classes are on (yoda_set_candidates) it returns YODA_ERR_STATE unless
+ * yoda_greedy_candidates is on: each pod's cycle is then the candidate-class cycle against the
+ * current state, the pod's class taken from the yoda_set_pod_classes array at its input index. */
 #define YODA_GREEDY_CARD_CAPACITY 1u
 int yoda_greedy(yoda_t* h, const yoda_pod_soa* pods, int mode, uint32_t flags, int32_t* pick);
 /* Work counters of the last yoda_greedy: GPU top-k windows, pods evaluated one by one
@@ -546,7 +549,9 @@ int yoda_nodes_absent(const yoda_t* h, uint32_t* n_absent);
  * yoda_shard_exchange_order) and the host queries (yoda_shard_topk_depth,
  * yoda_shard_overflow_count) answer.  A change of the candidate state also drops a sharded
  * step's pending exact merge.  With candidates off they run as they always did.  Mode B's
- * single-handle batch path honours the classes once yoda_mode_b_follow (below) is on.
+ * single-handle batch path honours the classes once yoda_mode_b_follow (below) is on, and
+ * yoda_greedy on one handle once yoda_greedy_candidates (below) is on; the sharded and
+ * communicator greedy calls keep refusing.
  *   The calls are ordered on the handle's stream and invalidate pending run, phase-1 and top-k
  * state, as yoda_set_node_present does; each validates its arguments before it writes anything.
  *   Cost: one pass over K1's masks after the Filter kernel (k_cand_narrow); the K2 pruning seeds
@@ -578,6 +583,33 @@ int yoda_candidates_info(const yoda_t* h, uint32_t* out);
 /* Diagnostic: the narrowing pass's time (HIP events, ms) summed over the runs that the
  * yoda_profile_read calls since the last call of this one have read (yoda_profile on). */
 int yoda_candidates_profile(yoda_t* h, double* narrow_ms);
+/* ---- yoda_greedy honours the candidate classes (opt-in) ----
+ * enable != 0: yoda_greedy on this handle runs while candidates are on, each pod's cycle being
+ * the candidate-class cycle above against the CURRENT node state of the batch (the assumes of
+ * the pods before it in queue order; with YODA_GREEDY_CARD_CAPACITY at the current CardNumber):
+ * the PreScore maxima over every present node that passes Yoda's Filter now, a candidate or not;
+ * F'(p) = the nodes of that set with cand(p, n); |F'| = 0 YODA_PICK_NONE, |F'| = 1 that node
+ * without scoring, |F'| >= 2 with a zero-total node of F' YODA_PICK_ERROR, otherwise the lowest
+ * node among the top-scored of F' (U64 path: the exact normalize over F', SCORE_RANGE ->
+ * YODA_PICK_ERROR).  The assume is unchanged, and a pod without a pick assumes nothing.  The
+ * candidate words do not change inside a batch.
+ *   The pods' classes are the yoda_set_pod_classes array indexed by the pod's position in `pods`
+ * (input order, not queue order): as long as pods->n_pods, or empty (every pod YODA_CAND_ANY);
+ * otherwise YODA_ERR_STATE and nothing is launched.  After the call, success or failure, the
+ * handle holds the node state, presence, candidate words and class array (host and device) it
+ * held before.
+ *   Mode B (YODA_MODE_DISKIO) honours the classes only when yoda_mode_b_follow is on too: the
+ * independent cycles of yoda_run in queue order, each pod with its own class; with it off the
+ * Mode B refusal stands.
+ *   Off (the default): yoda_greedy returns YODA_ERR_STATE while candidates are on, exactly as
+ * before.  A setting: it stays across uploads until changed.  YODA_ERR_INVALID_ARG on a NULL
+ * handle.  Unchanged with the setting on: yoda_shard_*, yoda_comm_* and yoda_comm_greedy* (and
+ * the Python driver dist.sharded_greedy on top of the shard calls) keep returning YODA_ERR_STATE
+ * while candidates are on.
+ *   Cost: with candidates never set nothing on yoda_greedy's path changes.  With them on, every
+ * window runs the narrowing pass after its Filter kernel, and a capacity window's exact fallback
+ * reads one 8-byte word per node more (profiles/greedycand/timing.txt). */
+int yoda_greedy_candidates(yoda_t* h, int enable);
 /* ---- Mode B follows the absent nodes and the candidate classes (opt-in) ----
  * Mode B's Filter is a pass-through (scheduler.go:96-99), so the nodes a Mode B pod may land on
  * are decided by the node set and the other plugins' Filter alone.  With the setting on,
@@ -592,8 +624,9 @@ int yoda_candidates_profile(yoda_t* h, double* narrow_ms);
  * outside E has feasibility bit 0 and raw and normalized scores of -1, a node of E scores what it
  * scores without the setting, and NormalizeScore takes highest and lowest over E.
  *   Followed by yoda_eval, yoda_run, yoda_download, yoda_score_rows and yoda_score_rows_norm
- * (their bitmask_out included), the single-handle draw, and yoda_greedy in Mode B while nodes are
- * absent (it keeps refusing candidate classes, as every greedy call does).  Unchanged with the
+ * (their bitmask_out included), the single-handle draw, and yoda_greedy in Mode B: while nodes
+ * are absent, and with candidate classes once yoda_greedy_candidates is on as well (without it
+ * yoda_greedy refuses candidate classes in either mode).  Unchanged with the
  * setting on: yoda_shard_* and yoda_comm_* in Mode B, the shard draw calls included, keep
  * returning YODA_ERR_STATE while a node is absent or candidates are on, and
  * yoda_run(YODA_MODE_DISKIO, YODA_RUN_BITMASK) + yoda_download_bitmask keeps its "run Mode A"
@@ -704,6 +737,16 @@ int yoda_gs_begin_window(yoda_gs_t* g, uint32_t ws, uint32_t wn, uint32_t k,
  * certifies a pod only while no node it could use has lost cards in the window. */
 int yoda_gs_set_witness(yoda_gs_t* g, const uint64_t* maxima, const uint32_t* wit_count,
                         const uint32_t* wit_node);
+/* Capacity sessions: the candidate words [N] (index = GLOBAL node id, as yoda_set_candidates) and
+ * the pods' classes [P] in input order (NULL: every pod YODA_CAND_ANY).  Copied.  Before the first
+ * window; YODA_ERR_STATE after one began; YODA_ERR_RANGE for a class >= n_classes that is not
+ * YODA_CAND_ANY; n_classes 0 clears them.  flags == 0 sessions accept and ignore them.
+ *   The windows of such a session carry counts and lists over F' = F and cand (what the narrowed
+ * masks give) and maxima with witnesses over F (Yoda's Filter alone); the certificate counts a
+ * lost node against the feasible set only if it is the pod's candidate, and against the
+ * witnesses either way. */
+int yoda_gs_set_candidates(yoda_gs_t* g, uint32_t n_classes, const uint64_t* words,
+                           const uint8_t* cls);
 /* Resolve the window in queue order; *next = the first window pod it cannot certify (wn when
  * the window is done).  flags == 0: the caller scores that pod exactly against the current
  * state (yoda_shard_best_one) and feeds it to yoda_gs_assign.  YODA_GREEDY_CARD_CAPACITY:

@@ -272,6 +272,11 @@ struct yoda_handle {
   std::vector<uint8_t> h_cls;
   int cls_top = -1;
   DevBuf cand_cls;
+  // yoda_greedy_candidates: yoda_greedy honours the classes.  Inside such a batch h_cls is the
+  // slice of the uploaded window (GreedyClasses) and cand_cls the batch's classes in queue order,
+  // of which the uploaded pods start at cls_off (0 outside a batch)
+  bool greedy_cand = false;
+  size_t cls_off = 0;
   // yoda_update_node_cards / yoda_snapshot_check: the changed nodes' packed rows (host), the
   // block summaries k_bsum_build writes for the self-check
   std::vector<uint32_t> cu_rows;
@@ -905,7 +910,8 @@ int mode_b_absent(yoda_t* h, int mode, bool batch = false) {
 }
 
 // Candidate classes narrow the batch path only (yoda_run, yoda_eval, the row calls): the greedy,
-// shard and communicator entry points refuse to run while they are on, as Mode B does.
+// shard and communicator entry points refuse to run while they are on, as Mode B does
+// (yoda_greedy on one handle: until yoda_greedy_candidates is on).
 int cand_refuse(yoda_t* h, const char* what) {
   if (!h->cand_classes) return YODA_OK;
   return fail(h, YODA_ERR_STATE,
@@ -1167,7 +1173,7 @@ bool modeb_keyed(const yoda_t* h) {
 bool modeb_elig_on(const yoda_t* h) { return h->b_follow && (h->n_absent > 0 || modeb_keyed(h)); }
 // The pods' class bytes on the device for the eligibility kernels (nullptr: every pod ANY).
 const uint8_t* modeb_cls_bytes(const yoda_t* h) {
-  return modeb_keyed(h) ? h->cand_cls.as<uint8_t>() : nullptr;
+  return modeb_keyed(h) ? h->cand_cls.as<uint8_t>() + h->cls_off : nullptr;
 }
 
 // The batch's Mode B pod classes, from the staged (alpha, beta) of the last upload: pods with
@@ -1334,6 +1340,36 @@ enum class Maxima {
   OwnFinal,   // ... and the reduce writes the reciprocals too (yoda_run)
 };
 
+// The narrowing pass after a phase 1's reduce (candidates on): the masks this run's K1 wrote
+// (h->bm_sparse: which form) and counts [2][P] from Yoda's Filter to every plugin's.  The maxima
+// stay K1's, over F.  pr: the run reads the block-grouped node tables.
+int cand_narrow(yoda_t* h, uint32_t* counts, uint32_t P, bool pr) {
+  CandArgs a{};
+  a.words = (pr ? h->cand_w_p : h->cand_w).as<uint64_t>();
+  a.band = (pr ? h->cand_and_p : h->cand_and).as<uint64_t>();
+  a.cls = h->h_cls.empty() ? nullptr : h->cand_cls.as<uint8_t>() + h->cls_off;
+  a.perm = h->ordered ? h->perm.as<uint32_t>() : nullptr;
+  a.zt = (pr ? h->cand_zt_p : h->cand_zt).as<uint64_t>();
+  a.n_nodes = h->n_nodes;
+  a.n_work = P;
+  a.bm = h->bitmask.as<uint64_t>();
+  a.bs = h->bm_sparse ? h->bsum.as<BlockMask>() : nullptr;
+  a.blk = h->bm_sparse ? h->blk.as<uint64_t>() : nullptr;
+  a.bm_stride = bm_row(h->n_nodes);
+  a.bs_stride = bs_row(h->n_nodes);
+  a.blk_stride = blk_row(h->n_nodes);
+  a.counts = counts;
+  hipEvent_t c0 = h->profiling ? h->next_event() : nullptr;
+  hipEvent_t c1 = h->profiling ? h->next_event() : nullptr;
+  if (c0) HIP_TRY(h, hipEventRecord(c0, h->stream));
+  HIP_TRY(h, launch_cand_narrow(a, h->stream));
+  if (c1) {
+    HIP_TRY(h, hipEventRecord(c1, h->stream));
+    h->ev_cand.emplace_back(c0, c1);
+  }
+  return YODA_OK;
+}
+
 // Phase 1: Filter + PreScore maxima (Mode A), or the all-feasible state (Mode B).
 int phase1(yoda_t* h, int mode, uint64_t* maxima, uint32_t* counts,
            Maxima whose = Maxima::Exchanged) {
@@ -1426,37 +1462,18 @@ int phase1(yoda_t* h, int mode, uint64_t* maxima, uint32_t* counts,
                             h->has_k1sum ? pod_params(h).cmask1 : nullptr));
   h->lpt_sorted = h->lpt_active;  // (the order of this run's pod blocks, for phase 2)
   h->rcp_ready = rcp;
-  if (h->cand_classes) {  // the masks and counts from Yoda's Filter to every plugin's
-    CandArgs a{};
-    a.words = (pr ? h->cand_w_p : h->cand_w).as<uint64_t>();
-    a.band = (pr ? h->cand_and_p : h->cand_and).as<uint64_t>();
-    a.cls = h->h_cls.empty() ? nullptr : h->cand_cls.as<uint8_t>();
-    a.perm = h->ordered ? h->perm.as<uint32_t>() : nullptr;
-    a.zt = (pr ? h->cand_zt_p : h->cand_zt).as<uint64_t>();
-    a.n_nodes = h->n_nodes;
-    a.n_work = P;
-    a.bm = h->bitmask.as<uint64_t>();
-    a.bs = h->bm_sparse ? h->bsum.as<BlockMask>() : nullptr;
-    a.blk = h->bm_sparse ? h->blk.as<uint64_t>() : nullptr;
-    a.bm_stride = bm_row(h->n_nodes);
-    a.bs_stride = bs_row(h->n_nodes);
-    a.blk_stride = blk_row(h->n_nodes);
-    a.counts = counts;
-    hipEvent_t c0 = h->profiling ? h->next_event() : nullptr;
-    hipEvent_t c1 = h->profiling ? h->next_event() : nullptr;
-    if (c0) HIP_TRY(h, hipEventRecord(c0, h->stream));
-    HIP_TRY(h, launch_cand_narrow(a, h->stream));
-    if (c1) {
-      HIP_TRY(h, hipEventRecord(c1, h->stream));
-      h->ev_cand.emplace_back(c0, c1);
-    }
-  }
+  // the masks and counts from Yoda's Filter to every plugin's
+  if (h->cand_classes) return cand_narrow(h, counts, P, pr);
   return YODA_OK;
 }
 
 // Phase 1 of a capacity-decrement greedy window: Filter + PreScore maxima with their
 // witnesses (k1_witness), dense masks.  Outputs maxima [6][P], counts [2][P] and
 // wit [2][6][P] (witness count, lowest witness node + node_offset), in the run's pod order.
+// With candidates on (yoda_greedy with yoda_greedy_candidates; the shard call refuses) the masks
+// -- sparse from the block-witness kernel, dense from k1_witness -- and counts are then narrowed
+// to F' through the upload-order tables, as phase 1's; maxima and wit stay over F, which is what
+// the session's maxima certificate needs.
 int phase1_witness(yoda_t* h, uint64_t* maxima, uint32_t* counts, uint32_t* wit,
                    uint32_t node_offset) {
   const uint32_t P = h->n_pods, N = h->n_nodes;
@@ -1508,6 +1525,7 @@ int phase1_witness(yoda_t* h, uint64_t* maxima, uint32_t* counts, uint32_t* wit,
   }
   HIP_TRY(h, launch_reduce_wit(part.max_u, h->p_wit.as<uint32_t>(), part.cnt, C, P,
                                node_offset, maxima, counts, wit, wit + 6 * (size_t)P, pod_params(h).mt, h->stream));
+  if (h->cand_classes) return cand_narrow(h, counts, P, false);
   return YODA_OK;
 }
 
@@ -3724,14 +3742,21 @@ int greedy_eval_fast(yoda_t* h, uint32_t s, int32_t* pick_out) {
 }  // extern "C"
 static int greedy_batch(yoda_t* h, const yoda_pod_soa* pods, int mode, uint32_t flags,
                         int32_t* pick);
+static int greedy_mode_b(yoda_t* h, const yoda_pod_soa* pods, int32_t* pick);
 extern "C" {
 
 int yoda_greedy(yoda_t* h, const yoda_pod_soa* pods, int mode, uint32_t flags, int32_t* pick) {
   if (!h) return YODA_ERR_INVALID_ARG;
   if (!pods || !pick) return fail(h, YODA_ERR_INVALID_ARG, "NULL pods or pick");
   if (!h->has_nodes) return fail(h, YODA_ERR_NO_NODES, "no node snapshot uploaded");
-  if (int rc = cand_refuse(h, "yoda_greedy")) return rc;
+  if (!h->greedy_cand)
+    if (int rc = cand_refuse(h, "yoda_greedy")) return rc;
   if (int rc = mode_b_absent(h, mode, true)) return rc;
+  // (candidates on: the class array is the batch's, in input order -- cand_ready's rule)
+  if (h->cand_classes && !h->h_cls.empty() && h->h_cls.size() != pods->n_pods)
+    return fail(h, YODA_ERR_STATE, "yoda_set_pod_classes: the class array's length is not n_pods");
+  if (h->cand_classes && h->cls_top >= (int)h->cand_classes)
+    return fail(h, YODA_ERR_STATE, "yoda_set_pod_classes: a class is not below n_classes");
   try {
     HIP_TRY(h, hipSetDevice(h->device));
     GreedyScope scope(h);
@@ -3744,20 +3769,7 @@ int yoda_greedy(yoda_t* h, const yoda_pod_soa* pods, int mode, uint32_t flags, i
     h->greedy_prep_ms = 0;
     if (P == 0) return YODA_OK;
     if (mode != YODA_MODE_DISKIO) return greedy_batch(h, pods, mode, flags, pick);
-    // Mode B reads no assumed-pod state: independent cycles, in queue order (sort.Less,
-    // sort.go:8-10 -- scv/priority descending, then input index)
-    int rc;
-    std::vector<uint32_t> order;
-    queue_order(pods->priority, P, order);
-    PodGather all;
-    all.build(pods, order.data(), P);
-    if ((rc = yoda_upload_pods(h, &all.soa)) || (rc = run_private(h, mode, 0, false))) return rc;
-    std::vector<int32_t> pk(P);
-    // the handle's stream may be non-blocking: copy and wait on it, not on the null stream
-    HIP_TRY(h, hipMemcpyAsync(pk.data(), h->pick.p, P * 4ull, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    for (uint32_t i = 0; i < P; ++i) pick[order[i]] = pk[i];
-    return YODA_OK;
+    return greedy_mode_b(h, pods, pick);
   } catch (const std::bad_alloc&) {
     return fail(h, YODA_ERR_INVALID_ARG, "host allocation failed");
   } catch (...) {
@@ -4451,6 +4463,12 @@ int yoda_mode_b_follow(yoda_t* h, int enable) {
   return YODA_OK;
 }
 
+int yoda_greedy_candidates(yoda_t* h, int enable) {
+  if (!h) return YODA_ERR_INVALID_ARG;
+  h->greedy_cand = enable != 0;
+  return YODA_OK;
+}
+
 int yoda_mode_b_info(const yoda_t* h, uint32_t* out) {
   if (!h || !out) return YODA_ERR_INVALID_ARG;
   out[0] = h->b_follow ? 1u : 0u;
@@ -4754,7 +4772,9 @@ int yoda_shard_best_one(yoda_t* h, uint32_t pod, double* score, int32_t* node) {
 
 // Pod p of `pods` scheduled exactly against the CURRENT device node state (k_one_*: Filter,
 // CollectMaxValues, Score, then k8s' outcome rules as k_finalize applies them).  Local pick.
-static int greedy_eval_exact(yoda_t* h, const yoda_pod_soa* pods, uint32_t p, int32_t* pick) {
+// cls: the pod's candidate class (YODA_CAND_ANY, or candidates off: the unrestricted kernels).
+static int greedy_eval_exact(yoda_t* h, const yoda_pod_soa* pods, uint32_t p, uint8_t cls,
+                             int32_t* pick) {
   const uint32_t N = h->n_nodes;
   *pick = YODA_PICK_NONE;
   if (N == 0) return YODA_OK;
@@ -4782,7 +4802,9 @@ static int greedy_eval_exact(yoda_t* h, const yoda_pod_soa* pods, uint32_t p, in
   }
   HIP_TRY(h, launch_one(h->K, h->path, h->nodes.as<unsigned char>(), N, op,
                         h->one_feas.as<uint64_t>(), h->one_part.p, h->one_done.as<uint32_t>(),
-                        h->one_out.as<OneOut>(), pod_params(h).mt, h->stream));
+                        h->one_out.as<OneOut>(), pod_params(h).mt, h->stream,
+                        h->cand_classes && cls != YODA_CAND_ANY ? h->cand_w.as<uint64_t>() : nullptr,
+                        cls));
   HIP_TRY(h, h->pick_stage.ensure(sizeof(OneOut)));
   HIP_TRY(h, hipMemcpyAsync(h->pick_stage.p, h->one_out.p, sizeof(OneOut), hipMemcpyDeviceToHost,
                             h->stream));
@@ -4863,6 +4885,50 @@ struct HostNodes {
   }
 };
 
+// The pod classes of a batch with candidates on (yoda_greedy_candidates).  The caller's array is
+// in input order and as long as the batch; the batch uploads its pods window by window in queue
+// order.  begin() takes the caller's array off the handle and puts the batch's own device copy
+// in queue order (cls[order[q]]) in its place; window() points what phase 1, cand_ready and Mode
+// B's class keys read -- h_cls and cls_off -- at the uploaded slice [ws, ws + wn), which
+// k_cand_narrow reads through the window's sort permutation.  The destructor puts the caller's
+// array back, host and device, on every exit path.
+struct GreedyClasses {
+  yoda_t* h;
+  std::vector<uint8_t> caller, queue;
+  DevBuf dev;
+  bool on = false;
+  explicit GreedyClasses(yoda_t* x) : h(x) {}
+  GreedyClasses(const GreedyClasses&) = delete;
+  GreedyClasses& operator=(const GreedyClasses&) = delete;
+  int begin(const uint32_t* order, uint32_t P) {
+    if (!h->cand_classes || h->h_cls.empty() || P == 0) return YODA_OK;
+    queue.resize(P);
+    for (uint32_t q = 0; q < P; ++q) queue[q] = h->h_cls[order[q]];
+    HIP_TRY(h, dev.ensure(P));
+    HIP_TRY(h, hipMemcpyAsync(dev.p, queue.data(), P, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));  // (the copy's source is pageable)
+    caller.swap(h->h_cls);
+    h->cand_cls.swap(dev);
+    on = true;
+    window(0, P);
+    return YODA_OK;
+  }
+  void window(uint32_t ws, uint32_t wn) {
+    if (!on) return;
+    h->h_cls.assign(queue.begin() + ws, queue.begin() + ws + wn);
+    h->cls_off = ws;
+  }
+  // the class of the pod at queue position q
+  uint8_t at(uint32_t q) const { return on ? queue[q] : (uint8_t)YODA_CAND_ANY; }
+  ~GreedyClasses() {
+    if (!on) return;
+    h->h_cls.swap(caller);
+    h->cand_cls.swap(dev);
+    h->cls_off = 0;
+    cand_invalidate(h);  // (the pending outcomes are a window's)
+  }
+};
+
 // One batch: the handle with its node ids local (node_offset 0 until the batch ends), the
 // session, and the one push -- the nodes the session changed since the last push, or
 // (original) every node it touched as the snapshot had it, to the device.
@@ -4870,10 +4936,13 @@ struct GreedyBatch {
   yoda_t* h;
   const uint32_t node_offset;
   yoda_gs_t* g = nullptr;
+  GreedyClasses cls;
   std::vector<uint32_t> ids;
   std::vector<uint64_t> al, cn;
   static constexpr bool kMapped = true;  // (push_node_state)
-  explicit GreedyBatch(yoda_t* x) : h(x), node_offset(x->node_offset) { h->node_offset = 0; }
+  explicit GreedyBatch(yoda_t* x) : h(x), node_offset(x->node_offset), cls(x) {
+    h->node_offset = 0;
+  }
   ~GreedyBatch() {
     h->node_offset = node_offset;
     if (g) yoda_gs_destroy(g);
@@ -4950,6 +5019,7 @@ int greedy_windows(GreedyBatch& b, const yoda_pod_soa* pods, bool capacity) {
     if ((rc = b.push())) return rc;
     const uint32_t wn = std::min(W, P - ws);
     win.build(pods, g->order.data() + ws, wn);
+    b.cls.window(ws, wn);
     if ((rc = yoda_upload_pods(h, &win.soa))) return rc;
     const double t_up = ms_since(tw);
     if ((rc = prepare_run(h, YODA_MODE_SCV))) return rc;
@@ -5067,7 +5137,8 @@ int greedy_windows(GreedyBatch& b, const yoda_pod_soa* pods, bool capacity) {
           fallback = unc <= scan_max;
         }
         if (!fallback) break;
-        if ((rc = b.push()) || (rc = greedy_eval_exact(h, pods, g->order[ws + next], &pk)))
+        if ((rc = b.push()) ||
+            (rc = greedy_eval_exact(h, pods, g->order[ws + next], b.cls.at(ws + next), &pk)))
           return rc;
       } else {
         if (!g->wrapped && ++fb_since >= rf.every && wn - next >= 2 * rf.scan) {
@@ -5172,11 +5243,19 @@ static int greedy_batch(yoda_t* h, const yoda_pod_soa* pods, int mode, uint32_t 
       return fail(h, rc, "greedy: session setup failed");
   }
   yoda_gs_t* g = b.g;
+  // candidates on (yoda_greedy_candidates): the capacity certificate tells F' from F by the
+  // words and classes (host mirrors: local ids, input order); then the classes go to queue order
+  if (capacity && h->cand_classes &&
+      (rc = yoda_gs_set_candidates(g, h->cand_classes, h->h_cand.data(),
+                                   h->h_cls.empty() ? nullptr : h->h_cls.data())))
+    return fail(h, rc, "greedy: session candidates");
+  if ((rc = b.cls.begin(g->order.data(), P))) return rc;
   if (h->generic) {
     // The U64 normalize check can change after every pick: every pod is evaluated exactly
     // against the current state, in queue order.
     for (uint32_t i = 0; i < P; ++i) {
       int32_t pk = YODA_PICK_NONE;
+      b.cls.window(i, 1);  // (the one-pod batch's class)
       if ((rc = b.push()) || (rc = greedy_eval_one(h, pods, g->order[i], mode, &pk))) return rc;
       if ((rc = yoda_gs_assign(g, i, pk))) return fail(h, rc, "greedy: assign");
       ++h->greedy_fallbacks;
@@ -5196,6 +5275,28 @@ static int greedy_batch(yoda_t* h, const yoda_pod_soa* pods, int mode, uint32_t 
   if ((rc = b.push(true))) return rc;
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   h->ran = false;
+  return YODA_OK;
+}
+
+// Mode B reads no assumed-pod state: independent cycles, in queue order (sort.Less,
+// sort.go:8-10 -- scv/priority descending, then input index).  With candidates on (both
+// yoda_mode_b_follow and yoda_greedy_candidates) the class array goes to queue order for the run.
+static int greedy_mode_b(yoda_t* h, const yoda_pod_soa* pods, int32_t* pick) {
+  const uint32_t P = pods->n_pods;
+  int rc;
+  std::vector<uint32_t> order;
+  queue_order(pods->priority, P, order);
+  GreedyClasses cls(h);
+  if ((rc = cls.begin(order.data(), P))) return rc;
+  PodGather all;
+  all.build(pods, order.data(), P);
+  if ((rc = yoda_upload_pods(h, &all.soa)) || (rc = run_private(h, YODA_MODE_DISKIO, 0, false)))
+    return rc;
+  std::vector<int32_t> pk(P);
+  // the handle's stream may be non-blocking: copy and wait on it, not on the null stream
+  HIP_TRY(h, hipMemcpyAsync(pk.data(), h->pick.p, P * 4ull, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  for (uint32_t i = 0; i < P; ++i) pick[order[i]] = pk[i];
   return YODA_OK;
 }
 

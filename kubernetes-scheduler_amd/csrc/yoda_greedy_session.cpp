@@ -132,8 +132,11 @@ bool yoda_greedy_session::scan_lost(uint32_t i, uint32_t p, uint64_t q, uint64_t
     }
     ++n_scan_nodes;
     if (!fit_ws(x, p, q)) return;
-    ++*lf;
-    *lz += total_sum[x] == 0 ? 1 : 0;
+    // x passed Yoda's Filter at the window start: F lost it, and F' too if it is a candidate
+    if (cand(p, x)) {
+      ++*lf;
+      *lz += total_sum[x] == 0 ? 1 : 0;
+    }
     uint64_t v[6];
     if (has_wit && contrib(x, p, v))
       for (int f = 0; f < 6; ++f) lw[f] += v[f] == wmax[(size_t)f * wn + i] ? 1 : 0;
@@ -230,6 +233,10 @@ bool yoda_greedy_session::resolve_capacity(uint32_t i, uint32_t p, int32_t* pk) 
   // certifies with the same outcome (nf0 >= 2 + lq leaves >= 2 feasible nodes; a field with
   // more witnesses than lost nodes, or an unlost single witness, keeps its maximum since
   // lw[f] <= lq).  The lost nodes' cards are examined only when it fails.
+  // Candidate classes leave it as it is: nf0 / nz0 count F', wcnt counts F, and lq = lost(q)
+  // counts the lost nodes of the whole snapshot, so it bounds the loss within F' (nf0 >= 2 + lq
+  // still leaves two nodes of F'; nz0 > 0 && lq > 0 still means a zero-total node of F' may be
+  // gone) as well as the loss within F (the witnesses).
   bool exact = false;
   if (!whole && lq > 0 && nf0 >= 2 + lq && nz0 == 0 && bi != 0xffffffffu &&
       maxima_kept(i, q, lq, false, lw)) {
@@ -461,6 +468,32 @@ int gs_begin_window_at(yoda_gs_t* g, uint32_t ws, uint32_t wn, uint32_t k,
 }
 
 extern "C" {
+
+int yoda_gs_set_candidates(yoda_gs_t* g, uint32_t n_classes, const uint64_t* words,
+                           const uint8_t* cls) {
+  if (!g || n_classes > YODA_MAX_CAND_CLASSES) return YODA_ERR_INVALID_ARG;
+  if (g->in_window) return YODA_ERR_STATE;
+  if (n_classes == 0) {
+    g->cand_words.clear();
+    g->cand_cls.clear();
+    return YODA_OK;
+  }
+  if (g->N && !words) return YODA_ERR_INVALID_ARG;
+  if (cls)
+    for (uint32_t p = 0; p < g->P; ++p)
+      if (cls[p] != YODA_CAND_ANY && cls[p] >= n_classes) return YODA_ERR_RANGE;
+  if (!(g->flags & YODA_GREEDY_CARD_CAPACITY)) return YODA_OK;  // (flags 0 reads neither)
+  try {
+    std::vector<uint64_t> w(words, words + g->N);
+    std::vector<uint8_t> c;
+    if (cls) c.assign(cls, cls + g->P);
+    g->cand_words.swap(w);
+    g->cand_cls.swap(c);
+    return YODA_OK;
+  } catch (...) {
+    return YODA_ERR_INVALID_ARG;
+  }
+}
 
 int yoda_gs_set_witness(yoda_gs_t* g, const uint64_t* maxima, const uint32_t* wit_count,
                         const uint32_t* wit_node) {

@@ -113,6 +113,17 @@ struct yoda_greedy_session {
   std::vector<uint64_t> wmax;
   std::vector<uint32_t> wcnt, wnode;
 
+  // yoda_gs_set_candidates (capacity sessions): the candidate words [N] and the pods' classes [P]
+  // in input order (empty: every pod YODA_CAND_ANY); no words: candidates off.  The window's
+  // counts and lists are then over F' = F and cand, its maxima and witnesses over F (Yoda's
+  // Filter alone): scan_lost is the one place that tells the two apart.
+  std::vector<uint64_t> cand_words;
+  std::vector<uint8_t> cand_cls;
+  bool cand(uint32_t p, uint32_t n) const {
+    if (cand_words.empty() || cand_cls.empty() || cand_cls[p] == YODA_CAND_ANY) return true;
+    return (cand_words[n] >> cand_cls[p]) & 1ull;
+  }
+
   // the assume step: pod p takes node `node` (a pick < 0 changes nothing)
   void apply(uint32_t p, int32_t node);
   // PodFitsNumber operand of pod p (filter.go:11-16): the label, or 1 (CardNumber > 0)
@@ -142,6 +153,8 @@ struct yoda_greedy_session {
   // the cards at hand: how many had passed its Filter at the window start (lf), how many of
   // those had TotalMemorySum == 0 (lz), and how many were witnesses of each of its maxima
   // (lw).  False (nothing computed) without the cards or when too many nodes were lost.
+  // With candidate classes lf / lz count the pod's candidates only (the nodes F' lost: counts
+  // is over F'), lw every node that passed Yoda's Filter (the witnesses F lost: wcnt is over F).
   // witness_only: the caller needs lw only (nf0 >= 2 + lq and no zero-total node at the window
   // start: lf and lz cannot change its outcome) -- and only for the fields whose witnesses lq
   // lost nodes could all be (wcnt <= lq); a node below every such maximum is skipped unvisited

@@ -3877,13 +3877,19 @@ __global__ __launch_bounds__(kBlock) void k_greedy_one(
 // maxima.  k_one_score: Score of the feasible nodes with them, argmax / ties / lowest.  Both
 // reduce in the last block (a counter reset for the next call), so a pod costs two
 // launches and one small copy.
-template <int K, Path PATH>
-__global__ __launch_bounds__(kBlock) void k_one_filter(const unsigned char* __restrict__ nodes,
-                                                       uint32_t n_nodes, OnePod pod,
-                                                       uint64_t* __restrict__ feas,
-                                                       uint64_t* __restrict__ part,
-                                                       uint32_t* __restrict__ done,
-                                                       OneOut* __restrict__ out, MemTab mt) {
+// CAND (greedy batches with candidate classes, yoda_greedy_candidates): the pod names class
+// cls_bit, and the feasible set is F' = F and cand -- the node's candidate word cand_w[n] (upload
+// order, one coalesced 8-byte load per lane beside the header's) gates nf, nz, first and the
+// feasibility bits k_one_score reads, while Yoda's own verdict keeps feeding the maxima, which
+// are over F (collection.go:39-52 never sees another plugin's Filter).
+template <int K, Path PATH, bool CAND>
+__device__ __forceinline__ void one_filter(const unsigned char* __restrict__ nodes,
+                                           uint32_t n_nodes, const OnePod pod,
+                                           uint64_t* __restrict__ feas,
+                                           uint64_t* __restrict__ part,
+                                           uint32_t* __restrict__ done,
+                                           OneOut* __restrict__ out, const MemTab mt,
+                                           const uint64_t* __restrict__ cand_w, uint32_t cls_bit) {
   using R = Rec<PATH>;
   using T = typename R::T;
   __shared__ uint64_t red[kBlock / kWave][9];
@@ -3903,9 +3909,12 @@ __global__ __launch_bounds__(kBlock) void k_one_filter(const unsigned char* __re
   for (uint32_t nb = blockIdx.x * kBlock; nb < n_nodes; nb += stride_n) {
     const uint32_t n = nb + threadIdx.x;
     bool f = false;
+    [[maybe_unused]] bool fc = false;  // (CAND) f and the pod's candidate bit
     if (n < n_nodes) {
       const unsigned char* rec = nodes + (size_t)n * R::stride(K);
       const NodeHdrG hd = *reinterpret_cast<const NodeHdrG*>(rec);
+      [[maybe_unused]] uint64_t cw = 0ull;
+      if constexpr (CAND) cw = cand_w[n];
       const Group<T, K> fr = load_group<T, K>(rec + R::off(kFree, K));
       const Group<T, K> ck = load_group<T, K>(rec + R::off(kClock, K));
       uint32_t cm = 0, cc = 0;
@@ -3917,10 +3926,20 @@ __global__ __launch_bounds__(kBlock) void k_one_filter(const unsigned char* __re
       }
       f = (pod.number <= hd.card_number) & (cm >= pod.need_mem) & (cc >= pod.need_clk) &
           ((hd.flags & kNodeAbsent) == 0u);
-      if (f) {
-        ++nf;
-        nz += hd.zero_total;
-        first = min(first, n);
+      if constexpr (CAND) {
+        fc = f & (bool)((cw >> cls_bit) & 1ull);
+        if (fc) {
+          ++nf;
+          nz += hd.zero_total;
+          first = min(first, n);
+        }
+      }
+      if (f) {  // (Yoda's verdict: the maxima are over F)
+        if constexpr (!CAND) {
+          ++nf;
+          nz += hd.zero_total;
+          first = min(first, n);
+        }
         const Group<T, K> bw = load_group<T, K>(rec + R::off(kBandwidth, K));
         const Group<T, K> co = load_group<T, K>(rec + R::off(kCore, K));
         const Group<T, K> pw = load_group<T, K>(rec + R::off(kPower, K));
@@ -3938,7 +3957,7 @@ __global__ __launch_bounds__(kBlock) void k_one_filter(const unsigned char* __re
         }
       }
     }
-    const uint64_t b = ballot(f);
+    const uint64_t b = ballot(CAND ? fc : f);
     if (lane_id() == 0 && nb + (threadIdx.x & ~63u) < n_nodes) feas[(nb + threadIdx.x) >> 6] = b;
   }
   // block reduce: waves through shuffles, then LDS
@@ -4022,6 +4041,24 @@ __global__ __launch_bounds__(kBlock) void k_one_filter(const unsigned char* __re
     out->rcp[k] = ru_100_over(M);
   }
   *done = 0u;
+}
+
+template <int K, Path PATH>
+__global__ __launch_bounds__(kBlock) void k_one_filter(const unsigned char* __restrict__ nodes,
+                                                       uint32_t n_nodes, OnePod pod,
+                                                       uint64_t* __restrict__ feas,
+                                                       uint64_t* __restrict__ part,
+                                                       uint32_t* __restrict__ done,
+                                                       OneOut* __restrict__ out, MemTab mt) {
+  one_filter<K, PATH, false>(nodes, n_nodes, pod, feas, part, done, out, mt, nullptr, 0u);
+}
+
+template <int K, Path PATH>
+__global__ __launch_bounds__(kBlock) void k_one_filter_cand(
+    const unsigned char* __restrict__ nodes, uint32_t n_nodes, OnePod pod,
+    uint64_t* __restrict__ feas, uint64_t* __restrict__ part, uint32_t* __restrict__ done,
+    OneOut* __restrict__ out, MemTab mt, const uint64_t* __restrict__ cand_w, uint32_t cls_bit) {
+  one_filter<K, PATH, true>(nodes, n_nodes, pod, feas, part, done, out, mt, cand_w, cls_bit);
 }
 
 template <int K, Path PATH>
@@ -6488,11 +6525,34 @@ uint32_t one_blocks() { return kOneBlocks; }
 
 hipError_t launch_one(int K, Path path, const unsigned char* nodes, uint32_t n_nodes,
                       const OnePod& pod, uint64_t* feas, void* part, uint32_t* done,
-                      OneOut* out, const MemTab& mt, hipStream_t s) {
+                      OneOut* out, const MemTab& mt, hipStream_t s, const uint64_t* cand_w,
+                      uint32_t cls_bit) {
   const dim3 grid(std::max<uint32_t>(1, std::min<uint32_t>(kOneBlocks,
                                                            (n_nodes + kBlock - 1) / kBlock)));
   uint64_t* p1 = static_cast<uint64_t*>(part);
   double* p2 = static_cast<double*>(part);
+  if (cand_w) {  // the pod names a candidate class: Filter over F', maxima over F
+    if (cls_bit >= 64u) return hipErrorInvalidValue;
+    switch (path) {
+      case Path::N32:
+        YODA_K_SWITCH(K, hipLaunchKernelGGL((k_one_filter_cand<KK, Path::N32>), grid, dim3(kBlock),
+                                            0, s, nodes, n_nodes, pod, feas, p1, done, out, mt,
+                                            cand_w, cls_bit);
+                      hipLaunchKernelGGL((k_one_score<KK, Path::N32>), grid, dim3(kBlock), 0, s,
+                                         nodes, n_nodes, pod, feas, p2, done + 1, out));
+        break;
+      case Path::F64:
+        YODA_K_SWITCH(K, hipLaunchKernelGGL((k_one_filter_cand<KK, Path::F64>), grid, dim3(kBlock),
+                                            0, s, nodes, n_nodes, pod, feas, p1, done, out,
+                                            MemTab{}, cand_w, cls_bit);
+                      hipLaunchKernelGGL((k_one_score<KK, Path::F64>), grid, dim3(kBlock), 0, s,
+                                         nodes, n_nodes, pod, feas, p2, done + 1, out));
+        break;
+      default:
+        return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+  }
   switch (path) {
     case Path::N32:
       YODA_K_SWITCH(K, hipLaunchKernelGGL((k_one_filter<KK, Path::N32>), grid, dim3(kBlock), 0, s,

@@ -196,9 +196,12 @@ hipError_t launch_reduce_wit(const uint64_t* pmax, const uint32_t* pwit, const u
 hipError_t launch_wit_prepare(const uint64_t* gmax, const uint64_t* lmax, uint32_t n_pods,
                               uint32_t* wit, hipStream_t s);
 uint32_t one_blocks();
+// cand_w != nullptr: the pod names candidate class cls_bit (< 64) -- k_one_filter_cand, whose
+// feasible set is F' = F and bit cls_bit of cand_w[n] (upload order) while its maxima stay over F
 hipError_t launch_one(int K, Path path, const unsigned char* nodes, uint32_t n_nodes,
                       const OnePod& pod, uint64_t* feas, void* part, uint32_t* done,
-                      OneOut* out, const MemTab& mt, hipStream_t s);
+                      OneOut* out, const MemTab& mt, hipStream_t s,
+                      const uint64_t* cand_w = nullptr, uint32_t cls_bit = 0);
 hipError_t launch_norm_rows(const int64_t* rows, uint32_t n_nodes, uint32_t n_pods,
                             const int64_t* best, const int64_t* lowest, int64_t* norm,
                             hipStream_t s);

@@ -417,6 +417,21 @@ func (g *Handle) ModeBFollow(enable bool) error {
 	return check(g.h, C.yoda_mode_b_follow(g.h, on), "yoda_mode_b_follow")
 }
 
+// GreedyCandidates makes Greedy on this handle honour the candidate classes
+// (yoda_greedy_candidates): each pod's cycle is the candidate-class cycle against the batch's
+// current node state, its class the SetPodClasses entry at the pod's input index (an array as
+// long as the batch, or none).  Mode B needs ModeBFollow as well.  Off, the default, Greedy
+// refuses while candidates are on.  A setting: it stays across uploads.  ShardedGreedy keeps
+// refusing either way.
+// Like the rest of this file, not compiled in this repository (no Go toolchain in the image).
+func (g *Handle) GreedyCandidates(enable bool) error {
+	on := C.int(0)
+	if enable {
+		on = 1
+	}
+	return check(g.h, C.yoda_greedy_candidates(g.h, on), "yoda_greedy_candidates")
+}
+
 // packPods parses the scv/* labels and the diskIO annotation with the reference's own
 // helpers (filter.go:60-74, sort.go:12-18, algorithm.go:103-104) into the C-side
 // yoda_pod_soa arrays.

@@ -91,6 +91,7 @@ _SIGS = {
     "yoda_candidates_info": ([_vp, _vp], C.c_int),
     "yoda_candidates_profile": ([_vp, C.POINTER(C.c_double)], C.c_int),
     "yoda_mode_b_follow": ([_vp, C.c_int], C.c_int),
+    "yoda_greedy_candidates": ([_vp, C.c_int], C.c_int),
     "yoda_mode_b_info": ([_vp, _vp], C.c_int),
     "yoda_snapshot_check": ([_vp, _vp, _vp], C.c_int),
     "yoda_shard_topk": ([_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp], C.c_int),
@@ -119,6 +120,7 @@ _SIGS = {
     "yoda_gs_queue_order": ([_vp, _vp], C.c_int),
     "yoda_gs_begin_window": ([_vp, _u32, _u32, _u32, _vp, _vp, _vp], C.c_int),
     "yoda_gs_set_witness": ([_vp, _vp, _vp, _vp], C.c_int),
+    "yoda_gs_set_candidates": ([_vp, _u32, _vp, _vp], C.c_int),
     "yoda_gs_resolve": ([_vp, C.POINTER(C.c_uint32)], C.c_int),
     "yoda_gs_assign": ([_vp, _u32, C.c_int32], C.c_int),
     "yoda_gs_take_dirty": ([_vp, _u32, _vp, _vp, _vp, C.POINTER(C.c_uint32)], C.c_int),
@@ -523,8 +525,9 @@ class Yoda:
         one uint64 per node of this handle, bit c set when the node is a candidate for class c;
         n_classes 1..64.  n_classes 0 (words may be None) turns candidates off, as upload_nodes
         does.  The PreScore maxima do not move; Filter, counts, scores and picks follow the
-        candidates.  While on, greedy, shard and comm calls raise YODA_ERR_STATE, and so does Mode B
-        unless mode_b_follow is on."""
+        candidates.  While on, shard and comm calls (their greedy drivers included) raise
+        YODA_ERR_STATE; so does Mode B unless mode_b_follow is on, and greedy on this handle unless
+        greedy_candidates is on."""
         w = None if words is None else np.ascontiguousarray(words, np.uint64).ravel()
         if w is not None and n_classes and w.size != self.n_nodes:
             raise ValueError("set_candidates: one word per node of this handle")
@@ -559,11 +562,21 @@ class Yoda:
 
     def mode_b_follow(self, enable: bool = True):
         """Mode B's single-handle batch path (run, eval, download, score_rows, the draw, greedy
-        with absent nodes) follows set_node_present and the candidate classes: pod p's cycle is
+        with absent nodes, and with candidate classes once greedy_candidates is on too) follows
+        set_node_present and the candidate classes: pod p's cycle is
         the reference's on the nodes of E(p) = present and candidates of p's class
         (yoda_mode_b_follow).  Off, the default: Mode B raises YODA_ERR_STATE while a node is
         absent or candidates are on.  A setting: it stays across uploads."""
         self._check(lib().yoda_mode_b_follow(self._h, 1 if enable else 0), "yoda_mode_b_follow")
+
+    def greedy_candidates(self, enable: bool = True):
+        """greedy() on this handle honours the candidate classes (yoda_greedy_candidates): each
+        pod's cycle is the candidate-class cycle against the batch's current node state, its class
+        the set_pod_classes entry at the pod's input index (an array as long as the batch, or
+        none).  Mode B needs mode_b_follow as well.  Off, the default: greedy raises
+        YODA_ERR_STATE while candidates are on.  A setting: it stays across uploads."""
+        self._check(lib().yoda_greedy_candidates(self._h, 1 if enable else 0),
+                    "yoda_greedy_candidates")
 
     def mode_b_info(self):
         """(enabled, effective pod classes D' of the last Mode B batch run, 1 if that run took the
@@ -851,6 +864,21 @@ class GreedySession:
         m, c, n = self._keep_w
         self._check(lib().yoda_gs_set_witness(self._g, _np_ptr(m), _np_ptr(c), _np_ptr(n)),
                     "yoda_gs_set_witness")
+
+    def set_candidates(self, words, n_classes, cls=None):
+        """Capacity sessions: the candidate words (one uint64 per node, by GLOBAL id) and the
+        pods' classes in input order, None: every pod CAND_ANY (yoda_gs_set_candidates).  Before
+        the first window; n_classes 0 clears them.  flags == 0 sessions accept and ignore them."""
+        w = None if words is None else np.ascontiguousarray(words, np.uint64).ravel()
+        c = None if cls is None else np.ascontiguousarray(cls, np.uint8).ravel()
+        if n_classes and (w is None or w.size != self.n_nodes):
+            raise ValueError("set_candidates: one word per node of the session")
+        if c is not None and c.size != self.n_pods:
+            raise ValueError("set_candidates: one class per pod of the session")
+        self._check(lib().yoda_gs_set_candidates(self._g, int(n_classes),
+                                                 None if w is None else _np_ptr(w),
+                                                 None if c is None else _np_ptr(c)),
+                    "yoda_gs_set_candidates")
 
     def resolve(self) -> int:
         nxt = C.c_uint32()
