@@ -543,15 +543,18 @@ int yoda_nodes_absent(const yoda_t* h, uint32_t* n_absent);
  * a node is one yoda_update_candidates entry with word 0.
  *   Honoured by yoda_eval, yoda_run (with and without YODA_RUN_BITMASK), yoda_download,
  * yoda_download_bitmask, yoda_score_rows and yoda_score_rows_norm in Mode A.  While candidates
- * are on, Mode B, yoda_greedy*, yoda_shard_* and yoda_comm_* return YODA_ERR_STATE and do nothing
- * else -- every shard call that starts, advances or reads a step, the exact-normalize, merge,
- * witness and draw calls included; only the settings (yoda_shard_tie_draw,
- * yoda_shard_exchange_order) and the host queries (yoda_shard_topk_depth,
- * yoda_shard_overflow_count) answer.  A change of the candidate state also drops a sharded
- * step's pending exact merge.  With candidates off they run as they always did.  Mode B's
+ * are on (and until the opt-in settings below say otherwise), Mode B, yoda_greedy*, yoda_shard_*
+ * and yoda_comm_* return YODA_ERR_STATE and do nothing else -- every shard call that starts,
+ * advances or reads a step, the exact-normalize, merge, witness and draw calls included; only
+ * the settings (yoda_shard_tie_draw, yoda_shard_exchange_order, yoda_shard_candidates) and the
+ * host queries (yoda_shard_topk_depth, yoda_shard_overflow_count) answer.  A change of the
+ * candidate state also drops a sharded step's pending exact merge.  With candidates off they
+ * run as they always did.  Mode B's
  * single-handle batch path honours the classes once yoda_mode_b_follow (below) is on, and
- * yoda_greedy on one handle once yoda_greedy_candidates (below) is on; the sharded and
- * communicator greedy calls keep refusing.
+ * yoda_greedy on one handle once yoda_greedy_candidates (below) is on; the sharded Mode A
+ * evaluation step (yoda_shard_phase1 .. yoda_shard_draw_apply, yoda_comm_run[_local]) once
+ * yoda_shard_candidates (below) is on; the sharded and communicator greedy calls and Mode B on
+ * shards keep refusing.
  *   The calls are ordered on the handle's stream and invalidate pending run, phase-1 and top-k
  * state, as yoda_set_node_present does; each validates its arguments before it writes anything.
  *   Cost: one pass over K1's masks after the Filter kernel (k_cand_narrow); the K2 pruning seeds
@@ -605,11 +608,63 @@ int yoda_candidates_profile(yoda_t* h, double* narrow_ms);
  * before.  A setting: it stays across uploads until changed.  YODA_ERR_INVALID_ARG on a NULL
  * handle.  Unchanged with the setting on: yoda_shard_*, yoda_comm_* and yoda_comm_greedy* (and
  * the Python driver dist.sharded_greedy on top of the shard calls) keep returning YODA_ERR_STATE
- * while candidates are on.
+ * while candidates are on (the sharded evaluation step: until yoda_shard_candidates is on).
  *   Cost: with candidates never set nothing on yoda_greedy's path changes.  With them on, every
  * window runs the narrowing pass after its Filter kernel, and a capacity window's exact fallback
  * reads one 8-byte word per node more (profiles/greedycand/timing.txt). */
 int yoda_greedy_candidates(yoda_t* h, int enable);
+/* ---- Node shards honour the candidate classes in the evaluation step (opt-in) ----
+ * enable != 0: while candidates are on, the sharded Mode A evaluation step runs on this handle --
+ * yoda_shard_phase1, _phase2, _prepare_merge, _finalize, _exact_records, _exact_merge, _draw_keys,
+ * _draw_apply, yoda_comm_run and yoda_comm_run_local.  Each shard holds the words of ITS nodes
+ * (yoda_set_candidates: upload order of the shard; yoda_update_candidates takes GLOBAL ids and
+ * ignores those of other shards, so one list serves every shard) and the WHOLE batch's class
+ * array.  After the step yoda_download gives, on every shard, exactly what one handle holding
+ * the whole snapshot gives from yoda_run under the same words (each node's at its global id) and
+ * classes, by the contract above: the maxima over F (the exchanged MAX, unchanged); n_feasible,
+ * the single-feasible-node rule, UNSCHEDULABLE and DIV_ZERO (a zero-total node of F' with
+ * |F'| >= 2, both counted over all shards) follow the global F'; so do NormalizeScore's bounds,
+ * n_ties, top_score and the lowest-node pick, and with yoda_shard_tie_draw the seeded draw -- on
+ * the three record paths (the U64 path's exact-normalize exchange included), in both exchange
+ * orders, through the packed-key merge and the record merge.  Phase 1 narrows the shard's masks
+ * and counts before they are exchanged; every later kernel of the step reads Filter state
+ * through those masks alone.  The K2 pruning seeds are off, as in yoda_run.
+ *   A step with candidates on whose class array is not as long as the batch returns
+ * YODA_ERR_STATE and launches nothing, as yoda_run.
+ *   Agreement.  The counts are summed over the shards, so shards that disagree on the candidate
+ * state give wrong picks silently.  yoda_comm_run[_local] check it: the first all-reduce carries
+ * a digest of (this setting, n_classes, the class array's length, a 64-bit hash of its bytes) and
+ * its complement, as for the draw settings; on disagreement every shard fails with
+ * YODA_ERR_STATE and the handles stay usable.  Two states are refused on the shard itself, BEFORE
+ * it launches or exchanges anything, because that is their contract (the old refusal, and
+ * "launches nothing"): candidates on with this setting off, and a class array whose length is
+ * not the batch's.  In one process (yoda_comm_run_local) every shard is checked before any of
+ * them runs, so all fail together.  Over RCCL (yoda_comm_run) the refusing rank returns while
+ * the others enter the all-reduce and wait for it: give every rank the same setting, as for
+ * yoda_shard_exchange_order, and check the class array's length against the batch on every rank
+ * (yoda_candidates_info out[1]) before a collective step.  The digest then catches what a rank
+ * cannot see alone: another n_classes, other class bytes, candidates off on one rank.  The
+ * words differ per shard by design and are in no digest.  A caller that drives yoda_shard_*
+ * itself OWNS the agreement: dist.ShardExchange checks the same digest, in the MAX reduce that
+ * checks the draw settings.
+ *   Off (the default): every yoda_shard_* and yoda_comm_* call returns YODA_ERR_STATE while
+ * candidates are on, with the same messages and launches as before.  A setting: it stays across
+ * uploads until changed.  YODA_ERR_INVALID_ARG on a NULL handle.
+ *   Refused whatever the setting, while candidates are on: Mode B on shards, the greedy-window
+ * shard calls (yoda_shard_topk[_deep], _best_one, _phase1_witness, _witness_prepare,
+ * _witness_download), yoda_comm_greedy[_local] and dist.sharded_greedy.  They are the next step.
+ *   Cost: with candidates never set, the first exchange is 16 bytes longer and nothing else
+ * changes.  With them on, each shard runs the narrowing pass over its own nodes after its K1
+ * (the single handle's figures above: 0.82 / 0.96 ms a step, 0.39 / 0.43 ms of it the pass).
+ * Measured at 100k pods x 100k nodes, config 3, every shard in ONE process on one MI355X through
+ * yoda_comm_run_local (profiles/shardcand/timing.txt), 8 classes that each lack 1 % / 30 % of
+ * the nodes: the sharded step 1.31 / 1.63 ms at world 2 and 3.08 / 3.69 ms at world 8 (0.82 and
+ * 2.21 ms with candidates never set), the pass 0.42 / 0.46 ms and 0.83 / 0.88 ms of it (24-32 %).
+ * Candidates never set, against the parent commit in interleaved fresh processes: inside the
+ * parent's process-to-process spread at world 8 (2.213 against 2.208 ms), 0.002 ms above its
+ * slowest process at world 2 (0.822 against 0.811 ms).  World sizes above 1 on separate GPUs are
+ * not measured. */
+int yoda_shard_candidates(yoda_t* h, int enable);
 /* ---- Mode B follows the absent nodes and the candidate classes (opt-in) ----
  * Mode B's Filter is a pass-through (scheduler.go:96-99), so the nodes a Mode B pod may land on
  * are decided by the node set and the other plugins' Filter alone.  With the setting on,

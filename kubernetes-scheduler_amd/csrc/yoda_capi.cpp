@@ -277,6 +277,10 @@ struct yoda_handle {
   // of which the uploaded pods start at cls_off (0 outside a batch)
   bool greedy_cand = false;
   size_t cls_off = 0;
+  // yoda_shard_candidates: the sharded evaluation step honours the classes.  cls_hash: a 64-bit
+  // hash of the caller's class bytes (yoda_set_pod_classes), for the shards' agreement digest
+  bool shard_cand = false;
+  uint64_t cls_hash = 0;
   // yoda_update_node_cards / yoda_snapshot_check: the changed nodes' packed rows (host), the
   // block summaries k_bsum_build writes for the self-check
   std::vector<uint32_t> cu_rows;
@@ -912,8 +916,11 @@ int mode_b_absent(yoda_t* h, int mode, bool batch = false) {
 // Candidate classes narrow the batch path only (yoda_run, yoda_eval, the row calls): the greedy,
 // shard and communicator entry points refuse to run while they are on, as Mode B does
 // (yoda_greedy on one handle: until yoda_greedy_candidates is on).
-int cand_refuse(yoda_t* h, const char* what) {
-  if (!h->cand_classes) return YODA_OK;
+// step: a call of the sharded Mode A evaluation step, which runs once yoda_shard_candidates is
+// on (phase 1 narrows the masks and counts whichever entry point called it; Mode B on shards
+// keeps refusing through mode_b_absent).
+int cand_refuse(yoda_t* h, const char* what, bool step = false) {
+  if (!h->cand_classes || (step && h->shard_cand)) return YODA_OK;
   return fail(h, YODA_ERR_STATE,
               std::string(what) + " does not honour candidate classes (yoda_set_candidates): "
                                   "turn them off (n_classes 0)");
@@ -3229,7 +3236,7 @@ int yoda_shard_draw_keys(yoda_t* h, int mode, uint64_t* d_keys) {
   if (!d_keys) return fail(h, YODA_ERR_INVALID_ARG, "NULL key buffer");
   if (mode != YODA_MODE_SCV && mode != YODA_MODE_DISKIO)
     return fail(h, YODA_ERR_INVALID_ARG, "mode must be YODA_MODE_SCV or YODA_MODE_DISKIO");
-  int rc = cand_refuse(h, "yoda_shard_draw_keys");
+  int rc = cand_refuse(h, "yoda_shard_draw_keys", true);
   if (rc) return rc;
   if ((rc = mode_b_absent(h, mode))) return rc;
   if ((rc = shard_draw_ready(h, "yoda_shard_draw_keys"))) return rc;
@@ -3268,7 +3275,7 @@ int yoda_shard_draw_keys(yoda_t* h, int mode, uint64_t* d_keys) {
 int yoda_shard_draw_apply(yoda_t* h, const uint64_t* d_keys) {
   if (!h) return YODA_ERR_INVALID_ARG;
   if (!d_keys) return fail(h, YODA_ERR_INVALID_ARG, "NULL key buffer");
-  int rc = cand_refuse(h, "yoda_shard_draw_apply");
+  int rc = cand_refuse(h, "yoda_shard_draw_apply", true);
   if (rc) return rc;
   if ((rc = shard_draw_ready(h, "yoda_shard_draw_apply"))) return rc;
   if (h->draw_stage != 2)
@@ -3288,7 +3295,7 @@ int yoda_shard_exchange_order(yoda_t* h, int caller_order) {
 
 int yoda_shard_phase1(yoda_t* h, int mode, uint64_t* d_maxima, uint32_t* d_counts) {
   if (!h) return YODA_ERR_INVALID_ARG;
-  if (int rc = cand_refuse(h, "yoda_shard_phase1")) return rc;
+  if (int rc = cand_refuse(h, "yoda_shard_phase1", true)) return rc;
   // caller-order exchange (yoda_shard_exchange_order): each shard its private order; not on the
   // U64 path (its exact-normalize records are per sorted position)
   h->xo = h->xo_enabled && !h->generic;
@@ -3316,7 +3323,7 @@ int yoda_shard_phase1(yoda_t* h, int mode, uint64_t* d_maxima, uint32_t* d_count
 int yoda_shard_phase2(yoda_t* h, int mode, const uint64_t* d_maxima, const uint32_t* d_counts,
                       int64_t* d_best, uint32_t* d_idx, uint32_t* d_ties, int64_t* d_lowest) {
   if (!h) return YODA_ERR_INVALID_ARG;
-  int rc = cand_refuse(h, "yoda_shard_phase2");
+  int rc = cand_refuse(h, "yoda_shard_phase2", true);
   if (rc) return rc;
   if ((rc = check_ready(h, mode))) return rc;
   if (!h->phase1_done) return fail(h, YODA_ERR_STATE, "yoda_shard_phase2 before phase1");
@@ -3347,7 +3354,7 @@ int yoda_shard_phase2(yoda_t* h, int mode, const uint64_t* d_maxima, const uint3
 int yoda_shard_prepare_merge(yoda_t* h, const int64_t* d_best_global, const int64_t* d_best_local,
                              uint32_t* d_idx, uint32_t* d_ties) {
   if (!h) return YODA_ERR_INVALID_ARG;
-  if (int rc = cand_refuse(h, "yoda_shard_prepare_merge")) return rc;
+  if (int rc = cand_refuse(h, "yoda_shard_prepare_merge", true)) return rc;
   if (!d_best_global || !d_best_local || !d_idx || !d_ties)
     return fail(h, YODA_ERR_INVALID_ARG, "NULL exchange buffer");
   HIP_TRY(h, hipSetDevice(h->device));
@@ -3360,7 +3367,7 @@ int yoda_shard_prepare_merge(yoda_t* h, const int64_t* d_best_global, const int6
 int yoda_shard_finalize(yoda_t* h, int mode, const uint32_t* d_counts, const int64_t* d_best,
                         const uint32_t* d_idx, const uint32_t* d_ties, const int64_t* d_lowest) {
   if (!h) return YODA_ERR_INVALID_ARG;
-  int rc = cand_refuse(h, "yoda_shard_finalize");
+  int rc = cand_refuse(h, "yoda_shard_finalize", true);
   if (rc) return rc;
   if ((rc = check_ready(h, mode))) return rc;
   if (!d_counts || !d_best || !d_idx || !d_ties || !d_lowest)
@@ -3404,7 +3411,7 @@ int yoda_shard_finalize(yoda_t* h, int mode, const uint32_t* d_counts, const int
 
 int yoda_shard_exact_records(yoda_t* h, void* d_rec) {
   if (!h || !d_rec) return YODA_ERR_INVALID_ARG;
-  if (int rc = cand_refuse(h, "yoda_shard_exact_records")) return rc;
+  if (int rc = cand_refuse(h, "yoda_shard_exact_records", true)) return rc;
   if (!h->k3_pending) return fail(h, YODA_ERR_STATE, "no exact-normalize pods pending");
   HIP_TRY(h, hipSetDevice(h->device));
   HIP_TRY(h, hipMemcpyAsync(d_rec, h->k3rec.p, (size_t)h->n_work * sizeof(ShardRec),
@@ -3414,7 +3421,7 @@ int yoda_shard_exact_records(yoda_t* h, void* d_rec) {
 
 int yoda_shard_exact_merge(yoda_t* h, const void* d_all, int world) {
   if (!h || !d_all || world < 1) return YODA_ERR_INVALID_ARG;
-  if (int rc = cand_refuse(h, "yoda_shard_exact_merge")) return rc;
+  if (int rc = cand_refuse(h, "yoda_shard_exact_merge", true)) return rc;
   if (!h->k3_pending) return fail(h, YODA_ERR_STATE, "no exact-normalize pods pending");
   try {
     HIP_TRY(h, hipSetDevice(h->device));
@@ -4426,6 +4433,7 @@ int yoda_set_pod_classes(yoda_t* h, uint32_t n_pods, const uint8_t* cls) {
     if (!h->h_cls.empty()) cand_invalidate(h);
     h->h_cls.clear();
     h->cls_top = -1;
+    h->cls_hash = 0;
     return YODA_OK;
   }
   // (candidates off: any class a later yoda_set_candidates could name; the run checks again)
@@ -4447,6 +4455,9 @@ int yoda_set_pod_classes(yoda_t* h, uint32_t n_pods, const uint8_t* cls) {
     cand_invalidate(h);
     h->h_cls.swap(copy);
     h->cls_top = top;
+    uint64_t x = 0xcbf29ce484222325ull;  // (FNV-1a, once per array: the steps read the result)
+    for (uint8_t c : h->h_cls) x = (x ^ c) * 0x100000001b3ull;
+    h->cls_hash = x;
     return YODA_OK;
   } catch (const std::bad_alloc&) {
     return fail(h, YODA_ERR_INVALID_ARG, "host allocation failed");
@@ -4466,6 +4477,15 @@ int yoda_mode_b_follow(yoda_t* h, int enable) {
 int yoda_greedy_candidates(yoda_t* h, int enable) {
   if (!h) return YODA_ERR_INVALID_ARG;
   h->greedy_cand = enable != 0;
+  return YODA_OK;
+}
+
+int yoda_shard_candidates(yoda_t* h, int enable) {
+  if (!h) return YODA_ERR_INVALID_ARG;
+  const bool on = enable != 0;
+  // (a step begun under the other setting does not continue under this one)
+  if (on != h->shard_cand && h->cand_classes) cand_invalidate(h);
+  h->shard_cand = on;
   return YODA_OK;
 }
 
@@ -5336,7 +5356,11 @@ static uint32_t bit_length(uint64_t v) {
 //   [4] a digest of the shard's draw settings (enable, seed, pod_base; 0: no draw in this step)
 //       and [5] its bitwise complement: after the MAX the two are complements of each other iff
 //       every shard sent the same digest (max d == min d), so every rank sees a disagreement.
-constexpr int kAgreeWords = 6;
+//   [6] a digest of the shard's candidate state (yoda_shard_candidates, n_classes, the class
+//       array's length and a hash of its bytes; 0: candidates off) and [7] its complement, the same
+//       scheme: the counts are SUMMED over the shards, so a shard that narrows by other classes
+//       would give wrong picks silently.  The words differ per shard by design and are not in it.
+constexpr int kAgreeWords = 8;
 constexpr size_t kAgreeBytes = 8 * kAgreeWords;
 
 static uint64_t draw_digest(const yoda_t* h) {
@@ -5344,10 +5368,20 @@ static uint64_t draw_digest(const yoda_t* h) {
   return tie_mix64(tie_mix64(h->tie_seed) ^ (h->tie_pod_base + 0x9E3779B97F4A7C15ull)) | 1ull;
 }
 
-// draw: a step that may end in the draw (yoda_comm_run*; the greedy's steps never do)
+static uint64_t cand_digest(const yoda_t* h) {
+  if (!h->cand_classes) return 0;
+  uint64_t d = tie_mix64(((uint64_t)h->cand_classes << 1) | (h->shard_cand ? 1u : 0u));
+  d = tie_mix64(d ^ ((uint64_t)h->h_cls.size() + 0x9E3779B97F4A7C15ull));
+  return tie_mix64(d ^ h->cls_hash) | 1ull;
+}
+
+// draw: an evaluation step (yoda_comm_run*): it may end in the draw and may run with candidate
+// classes on; the greedy's steps never do either
 static void agreement_words(const yoda_t* h, int mode, uint64_t* w, bool draw = false) {
   w[4] = draw ? draw_digest(h) : 0;
   w[5] = ~w[4];
+  w[6] = draw ? cand_digest(h) : 0;
+  w[7] = ~w[6];
   w[0] = h->generic && mode == YODA_MODE_SCV ? 64u : bit_length(h->score_bound);
   w[1] = bit_length((uint64_t)h->node_offset + h->n_nodes + 1);
   const bool f32q = mode == YODA_MODE_SCV && h->path == Path::N32 && h->q32;
@@ -5369,7 +5403,14 @@ static int comm_step(yoda_t* const* hs, int n, int world, int mode, bool local, 
   const uint32_t P = h0->n_pods;
   const size_t n1 = 6 * (size_t)P + kAgreeWords;  // maxima | agreement words
   for (int i = 0; i < n; ++i) {  // (before any shard's run is prepared)
-    if (hs[i]->cand_classes) return fail(h0, cand_refuse(hs[i], "yoda_comm_run"), hs[i]->last_error);
+    // candidates on: only the evaluation step, with yoda_shard_candidates on, in Mode A and with
+    // a class array that fits the batch; checked on every shard before any of them launches
+    if (hs[i]->cand_classes) {
+      int rc = cand_refuse(hs[i], "yoda_comm_run", draw);
+      if (!rc && mode == YODA_MODE_DISKIO) rc = mode_b_absent(hs[i], mode);
+      if (!rc && hs[i]->has_pods) rc = cand_ready(hs[i]);
+      if (rc) return fail(h0, rc, hs[i]->last_error);
+    }
     if (hs[i]->n_absent && mode == YODA_MODE_DISKIO)
       return fail(h0, mode_b_absent(hs[i], mode), hs[i]->last_error);
   }
@@ -5460,6 +5501,14 @@ static int comm_step(yoda_t* const* hs, int n, int world, int mode, bool local, 
       fail(hs[i], YODA_ERR_STATE,
            "shards disagree on the draw settings: yoda_set_tie_draw (enable, seed, pod_base) and "
            "yoda_shard_tie_draw must be the same on every shard of a batch");
+    return YODA_ERR_STATE;
+  }
+  if (agreed[6] != ~agreed[7]) {
+    for (int i = 0; i < n; ++i)
+      fail(hs[i], YODA_ERR_STATE,
+           "shards disagree on the candidate state: yoda_shard_candidates, n_classes "
+           "(yoda_set_candidates) and the class array (yoda_set_pod_classes) must be the same on "
+           "every shard of a batch");
     return YODA_ERR_STATE;
   }
   const bool drawing = agreed[4] != 0;  // (so every shard of the batch has it enabled)

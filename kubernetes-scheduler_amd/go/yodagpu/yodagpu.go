@@ -432,6 +432,23 @@ func (g *Handle) GreedyCandidates(enable bool) error {
 	return check(g.h, C.yoda_greedy_candidates(g.h, on), "yoda_greedy_candidates")
 }
 
+// ShardCandidates makes the sharded Mode A evaluation step on this handle (ShardedBatch:
+// yoda_comm_run) honour the candidate classes (yoda_shard_candidates): the handle holds the
+// candidate words of ITS shard's nodes and the whole batch's class array, and every shard's
+// outcome equals one handle's Batch on the whole snapshot.  Every rank needs the same setting,
+// class count and class array: yoda_comm_run checks them in its first all-reduce and fails on
+// every rank when they differ.  Off, the default, ShardedBatch refuses while candidates are on.
+// A setting: it stays across uploads.  ShardedGreedy and Mode B on shards keep refusing either
+// way.
+// Like the rest of this file, not compiled in this repository (no Go toolchain in the image).
+func (g *Handle) ShardCandidates(enable bool) error {
+	on := C.int(0)
+	if enable {
+		on = 1
+	}
+	return check(g.h, C.yoda_shard_candidates(g.h, on), "yoda_shard_candidates")
+}
+
 // packPods parses the scv/* labels and the diskIO annotation with the reference's own
 // helpers (filter.go:60-74, sort.go:12-18, algorithm.go:103-104) into the C-side
 // yoda_pod_soa arrays.

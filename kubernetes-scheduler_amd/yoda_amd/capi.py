@@ -92,6 +92,7 @@ _SIGS = {
     "yoda_candidates_profile": ([_vp, C.POINTER(C.c_double)], C.c_int),
     "yoda_mode_b_follow": ([_vp, C.c_int], C.c_int),
     "yoda_greedy_candidates": ([_vp, C.c_int], C.c_int),
+    "yoda_shard_candidates": ([_vp, C.c_int], C.c_int),
     "yoda_mode_b_info": ([_vp, _vp], C.c_int),
     "yoda_snapshot_check": ([_vp, _vp, _vp], C.c_int),
     "yoda_shard_topk": ([_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp], C.c_int),
@@ -163,7 +164,13 @@ def lib():
             raise YodaError(f"libyoda not built: {LIB_PATH} missing (run __graft_entry__.build())")
         L = C.CDLL(LIB_PATH)
         for name, (args, res) in _SIGS.items():
-            fn = getattr(L, name)
+            fn = getattr(L, name, None)
+            if fn is None:
+                # another build for A/B timing (YODA_LIB_PATH) may predate an entry point: calling
+                # it then raises AttributeError; the in-tree library must export every one
+                if os.environ.get("YODA_LIB_PATH"):
+                    continue
+                raise YodaError(f"libyoda: {LIB_PATH} does not export {name}")
             fn.argtypes = args
             fn.restype = res
         _lib = L
@@ -527,7 +534,9 @@ class Yoda:
         does.  The PreScore maxima do not move; Filter, counts, scores and picks follow the
         candidates.  While on, shard and comm calls (their greedy drivers included) raise
         YODA_ERR_STATE; so does Mode B unless mode_b_follow is on, and greedy on this handle unless
-        greedy_candidates is on."""
+        greedy_candidates is on.  The sharded Mode A evaluation step (the shard_* step calls,
+        comm_run, comm_run_local) runs once shard_candidates is on: `words` are then this shard's
+        nodes' words."""
         w = None if words is None else np.ascontiguousarray(words, np.uint64).ravel()
         if w is not None and n_classes and w.size != self.n_nodes:
             raise ValueError("set_candidates: one word per node of this handle")
@@ -577,6 +586,18 @@ class Yoda:
         YODA_ERR_STATE while candidates are on.  A setting: it stays across uploads."""
         self._check(lib().yoda_greedy_candidates(self._h, 1 if enable else 0),
                     "yoda_greedy_candidates")
+
+    def shard_candidates(self, enable: bool = True):
+        """The sharded Mode A evaluation step on this handle honours the candidate classes
+        (yoda_shard_candidates): shard_phase1 .. shard_draw_apply, comm_run and comm_run_local run
+        while candidates are on, and every shard's download equals one handle's run() on the whole
+        snapshot under the same words (by global id) and classes.  Each shard holds its own nodes'
+        words and the whole batch's class array; every shard of a batch needs the same setting,
+        n_classes and class array (comm_run* and dist.ShardExchange check).  Off, the default:
+        those calls raise YODA_ERR_STATE while candidates are on.  The greedy-window shard calls,
+        comm_greedy* and Mode B on shards refuse either way.  A setting: it stays across uploads."""
+        self._check(lib().yoda_shard_candidates(self._h, 1 if enable else 0),
+                    "yoda_shard_candidates")
 
     def mode_b_info(self):
         """(enabled, effective pod classes D' of the last Mode B batch run, 1 if that run took the

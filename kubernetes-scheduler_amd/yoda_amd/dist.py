@@ -220,6 +220,46 @@ def _draw_digest(tie_draw) -> int:
     return (int.from_bytes(d, "little") >> 2) | 1
 
 
+def _cand_digest(candidates) -> int:
+    """A 62-bit digest of (n_classes, the class array's length and bytes), 0 for no candidates:
+    what every shard of a batch must share.  The words differ per shard by design: not in it."""
+    if candidates is None:
+        return 0
+    import hashlib
+    n_classes, _, cls = candidates
+    c = b"" if cls is None else np.ascontiguousarray(cls, np.uint8).tobytes()
+    d = hashlib.blake2b(int(n_classes).to_bytes(8, "little") + len(c).to_bytes(8, "little") + c,
+                        digest_size=8).digest()
+    return (int.from_bytes(d, "little") >> 2) | 1
+
+
+def _agree(reducer, digests, n: int, device):
+    """digests: [(digest, what)].  Each digest and its complement in ONE MAX reduce: after it they
+    are complements of each other iff every rank sent the same digest."""
+    words = [w for d, _ in digests for w in (d, ~d)]
+    chk = [torch.tensor(words, dtype=torch.int64, device=device) for _ in range(n)]
+    reducer(chk, "max")
+    got = [int(v) for v in chk[0].tolist()]
+    for k, (_, what) in enumerate(digests):
+        if got[2 * k] != ~got[2 * k + 1]:
+            raise ValueError(f"ShardExchange: the ranks disagree on {what}")
+
+
+def _set_candidates(handles, candidates):
+    """candidates: None (the handles are left as they are), or (n_classes, words_per_shard, cls):
+    one uint64 array per handle of this process (its nodes, in upload order) and the whole batch's
+    class bytes (None: every pod ANY)."""
+    if candidates is None:
+        return
+    n_classes, words, cls = candidates
+    if len(words) != len(handles):
+        raise ValueError("candidates: one word array per handle of this process")
+    for k, h in enumerate(handles):
+        h.set_candidates(words[k], int(n_classes))
+        h.set_pod_classes(cls)
+        h.shard_candidates(True)
+
+
 def merge_witness(reduce: Reducer, bufs: List[ShardBuffers], prepare: Callable):
     """Capacity greedy phase 1: global maxima (MAX) and counts (SUM) as merge_phase1, then the
     witnesses: a shard below a field's global maximum clears its witness of it (prepare),
@@ -269,20 +309,23 @@ class ShardExchange:
     """Drives libyoda handles (one per shard) through the sharded entry points."""
 
     def __init__(self, handles, reducer: Reducer, device, path_code=None, compact: bool = True,
-                 caller_order: bool = True, tie_draw=None):
+                 caller_order: bool = True, tie_draw=None, candidates=None):
         """tie_draw: None, or (seed, pod_base) -- every step then ends in the seeded selectHost
         draw (yoda_set_tie_draw + yoda_shard_tie_draw on the handles; one more MIN all-reduce of
-        [P] int64).  Every rank must pass the same value: checked here, with one MAX reduce."""
+        [P] int64).  Every rank must pass the same value: checked here, with one MAX reduce.
+        candidates: None, or (n_classes, words_per_shard, cls) -- other plugins' Filter results as
+        candidate classes (yoda_set_candidates / yoda_set_pod_classes / yoda_shard_candidates on
+        the handles): words_per_shard[k] the uint64 words of handle k's nodes in upload order, cls
+        the whole batch's class bytes (None: every pod ANY).  n_classes and cls must be the same
+        on every rank: checked here too, in the same MAX reduce, before a handle is touched.  Live
+        changes between steps go to the handles (update_candidates with global ids: one list for
+        every shard)."""
         self.handles = list(handles)
         self.tie_draw = None if tie_draw is None else (int(tie_draw[0]), int(tie_draw[1]))
-        # a digest and its complement: after the MAX they are complements iff every rank agrees
-        d = [_draw_digest(self.tie_draw)]
-        chk = [torch.tensor([x, ~x], dtype=torch.int64, device=device)
-               for x in (d * len(self.handles))]
-        reducer(chk, "max")
-        lo, hi = (int(v) for v in chk[0].tolist())
-        if lo != ~hi:
-            raise ValueError("ShardExchange: the ranks disagree on tie_draw (seed, pod_base)")
+        _agree(reducer, [(_draw_digest(self.tie_draw), "tie_draw (seed, pod_base)"),
+                         (_cand_digest(candidates), "candidates (n_classes, the class array)")],
+               len(self.handles), device)
+        _set_candidates(self.handles, candidates)
         for h in self.handles:
             if self.tie_draw is None:
                 h.shard_tie_draw(False)
@@ -318,24 +361,27 @@ class ShardExchange:
 
     @classmethod
     def local(cls, handles, device, shards=None, offsets=None, compact: bool = True,
-              caller_order: bool = True, tie_draw=None):
+              caller_order: bool = True, tie_draw=None, candidates=None):
         """Several shards in one process (single-GPU testing).  Pass the node shards to
-        enforce a common record path."""
+        enforce a common record path (a re-upload turns a handle's candidates off: they are set
+        after it)."""
         red = Reducer(local=True)
         path = None
         if shards is not None:
             path = agree_on_path(red, handles, shards, offsets, device)
         return cls(handles, red, device, path, compact=compact, caller_order=caller_order,
-                   tie_draw=tie_draw)
+                   tie_draw=tie_draw, candidates=candidates)
 
     @classmethod
-    def distributed(cls, handle, device, shard=None, offset=0, group=None, tie_draw=None):
-        """One shard per rank over torch.distributed (RCCL)."""
+    def distributed(cls, handle, device, shard=None, offset=0, group=None, tie_draw=None,
+                    candidates=None):
+        """One shard per rank over torch.distributed (RCCL).  candidates: (n_classes, [this
+        rank's words], cls)."""
         red = Reducer(group=group)
         path = None
         if shard is not None:
             path = agree_on_path(red, [handle], [shard], [offset], device)
-        return cls([handle], red, device, path, tie_draw=tie_draw)
+        return cls([handle], red, device, path, tie_draw=tie_draw, candidates=candidates)
 
     def _prepare(self, h, b: ShardBuffers):
         p = ShardBuffers.ptr
@@ -396,9 +442,12 @@ class LibExchange:
     exact-normalize records when K3 flags pods.  torch.distributed here only agrees on the
     record path and broadcasts the communicator id."""
 
-    def __init__(self, handle, device, shard=None, offset: int = 0, group=None, tie_draw=None):
+    def __init__(self, handle, device, shard=None, offset: int = 0, group=None, tie_draw=None,
+                 candidates=None):
         """tie_draw: None, or (seed, pod_base): comm_run then ends in the draw (libyoda checks
-        that the ranks agree, in its first all-reduce)."""
+        that the ranks agree, in its first all-reduce).  candidates: None, or (n_classes, [this
+        rank's words], cls) as ShardExchange's: comm_run then honours the classes (libyoda checks
+        that the ranks agree on them, in the same all-reduce)."""
         import torch.distributed as dist
         from .capi import comm_unique_id
         if tie_draw is not None:
@@ -416,6 +465,7 @@ class LibExchange:
             t.copy_(torch.tensor(list(comm_unique_id()), dtype=torch.uint8))
         dist.broadcast(t, src=0, group=group)
         handle.comm_init(bytes(t.cpu().numpy().tobytes()), rank, world)
+        _set_candidates([handle], candidates)  # (after agree_on_path's re-upload, if any)
         if device.type == "cuda":
             handle.set_stream(torch.cuda.current_stream(device).cuda_stream)
         self.handle = handle
@@ -524,6 +574,10 @@ class HandleShard:
     def generic(self) -> bool:
         return self.h.generic
 
+    @property
+    def candidates_on(self) -> bool:
+        return self.h.candidates_info()[0] != 0
+
     def upload_pods(self, pods):
         self.h.upload_pods(pods)
 
@@ -598,7 +652,12 @@ def sharded_greedy(shards, reduce: Reducer, nodes, pods, flags: int = 0, window:
     how far the last one got), as the single-handle yoda_greedy does.
     `shards`: this process's shards (HandleShard); `nodes`: the FULL snapshot.  The shards'
     node state is restored at the end."""
-    from .capi import GreedySession, greedy_cap_depth, next_window, topk_k, topk_k_capacity
+    from .capi import (GreedySession, YodaError, greedy_cap_depth, next_window, topk_k,
+                       topk_k_capacity)
+    for s in shards:  # (the evaluation step alone honours them on shards: yoda_shard_candidates)
+        if getattr(s, "candidates_on", False):
+            raise YodaError("sharded_greedy: YODA_ERR_STATE: the sharded greedy does not honour "
+                            "candidate classes (yoda_set_candidates): turn them off (n_classes 0)")
     k = topk_k()
     k_cap = topk_k_capacity()  # the capacity windows' phase-1 depth
     k_deep = greedy_cap_depth()  # their lists merged deeper (yoda_comm_greedy's window sequence)
