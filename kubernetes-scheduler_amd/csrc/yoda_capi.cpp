@@ -1142,15 +1142,9 @@ int xo_ensure(yoda_t* h) {
 }
 
 // Mode B score levels (yoda_layout.h DiskLevels): t[k] = the largest |d| >= 0 whose score
-// trunc(10 - 10*|d|) (algorithm.go:110-111, no FMA: this file builds with -ffp-contract=off)
-// is >= k, by bisection over the bit patterns of the non-negative doubles (ordered like their
+// (yoda_modeb.h disk_score, the kernels' own: algorithm.go:110-111, never FMA-contracted) is
+// >= k, by bisection over the bit patterns of the non-negative doubles (ordered like their
 // values); the score is non-increasing in |d|, so the set is [0, t[k]].
-static double diskio_score(double l) {
-  volatile double t = 10.0 * l;
-  volatile double s = 10.0 - t;
-  return s >= 1.0 ? std::trunc((double)s) : 0.0;
-}
-
 static const DiskLevels& diskio_levels() {
   static const DiskLevels lv = [] {
     DiskLevels d{};
@@ -1162,7 +1156,7 @@ static const DiskLevels& diskio_levels() {
         const uint64_t mid = lo + (hi - lo) / 2;
         double x;
         std::memcpy(&x, &mid, 8);
-        if (diskio_score(x) >= (double)k) lo = mid; else hi = mid;
+        if (disk_score(x) >= (double)k) lo = mid; else hi = mid;
       }
       std::memcpy(&d.t[k], &lo, 8);
     }
@@ -1181,6 +1175,17 @@ bool modeb_elig_on(const yoda_t* h) { return h->b_follow && (h->n_absent > 0 || 
 // The pods' class bytes on the device for the eligibility kernels (nullptr: every pod ANY).
 const uint8_t* modeb_cls_bytes(const yoda_t* h) {
   return modeb_keyed(h) ? h->cand_cls.as<uint8_t>() + h->cls_off : nullptr;
+}
+
+// What the Mode B launches take for eligibility: empty (the unrestricted kernels) unless it is
+// on; else the table and counts (ensure_modeb_elig), the pods' class bytes and the pod classes'
+// selectors behind (alpha, beta) in b_cab (ensure_diskio_classes: the batch kernels read them).
+static DiskEligArgs modeb_elig_args(const yoda_t* h) {
+  if (!modeb_elig_on(h)) return DiskEligArgs{};
+  const double* cab = h->b_cab.as<double>();
+  return DiskEligArgs{h->b_elig.as<DiskElig>(),
+                      cab ? reinterpret_cast<const uint32_t*>(cab + 2 * (size_t)h->b_ncls) : nullptr,
+                      modeb_cls_bytes(h), h->b_ecnt.as<uint32_t>()};
 }
 
 // The batch's Mode B pod classes, from the staged (alpha, beta) of the last upload: pods with
@@ -1386,13 +1391,12 @@ int phase1(yoda_t* h, int mode, uint64_t* maxima, uint32_t* counts,
   const uint32_t P = h->n_work;  // sorted positions of this run
   if (P == 0) return YODA_OK;
   if (mode == YODA_MODE_DISKIO) {
-    if (modeb_elig_on(h)) {  // n_feasible = |E|: the count of the pod's class, or of the present
+    if (modeb_elig_on(h))
       if (int rc = ensure_modeb_elig(h)) return rc;
-      HIP_TRY(h, launch_fill_diskio_state_elig(P, modeb_cls_bytes(h), h->b_ecnt.as<uint32_t>(),
-                                               maxima, counts, h->stream));
-      return YODA_OK;
-    }
-    HIP_TRY(h, launch_fill_diskio_state(P, h->n_nodes, maxima, counts, h->stream));
+    // n_feasible = every node, or with eligibility |E|: the count of the pod's class, or of the
+    // present nodes
+    HIP_TRY(h, launch_fill_diskio_state(P, h->n_nodes, maxima, counts, modeb_elig_args(h),
+                                        h->stream));
     return YODA_OK;
   }
   if (h->n_nodes == 0) {
@@ -1573,29 +1577,17 @@ int phase2(yoda_t* h, int mode, const uint64_t* maxima, const uint32_t* counts, 
     HIP_TRY(h, h->b_part.ensure(2 * (size_t)pl.C * D * 4));
     uint32_t* plc = h->b_part.as<uint32_t>();
     uint32_t* pix = plc + (size_t)pl.C * D;
-    const bool elig = modeb_elig_on(h);  // (its table: phase 1 of this run built it)
-    h->b_last_elig = elig;
+    h->b_last_elig = modeb_elig_on(h);  // (its table: phase 1 of this run built it)
     h->b_last_ncls = D;
     if (e0) HIP_TRY(h, hipEventRecord(e0, h->stream));
-    if (elig) {
-      const uint32_t* csel = reinterpret_cast<const uint32_t*>(h->b_cab.as<double>() + 2 * (size_t)D);
-      HIP_TRY(h, launch_k2b_elig(h->nodes_b.as<NodeRecB>(), h->n_nodes, h->b_cab.as<double>(),
-                                 csel, D, diskio_levels(), pl, h->b_elig.as<DiskElig>(), plc, pix,
-                                 h->stream));
-    } else {
-      HIP_TRY(h, launch_k2b(h->nodes_b.as<NodeRecB>(), h->n_nodes, h->b_cab.as<double>(), D,
-                            diskio_levels(), pl, plc, pix, h->stream));
-    }
+    HIP_TRY(h, launch_k2b(h->nodes_b.as<NodeRecB>(), h->n_nodes, h->b_cab.as<double>(), D,
+                          diskio_levels(), pl, plc, pix, modeb_elig_args(h), h->stream));
     if (e1) {
       HIP_TRY(h, hipEventRecord(e1, h->stream));
       h->ev_k2.emplace_back(e0, e1);
     }
-    if (elig)
-      HIP_TRY(h, launch_reduce2b_elig(plc, pix, pl.C, D, h->b_cls.as<uint32_t>(), P,
-                                      h->node_offset, best, idx, ties, low, h->stream));
-    else
-      HIP_TRY(h, launch_reduce2b(plc, pix, pl.C, D, h->b_cls.as<uint32_t>(), P, h->node_offset,
-                                 best, idx, ties, low, h->stream));
+    HIP_TRY(h, launch_reduce2b(plc, pix, pl.C, D, h->b_cls.as<uint32_t>(), P, h->node_offset,
+                               best, idx, ties, low, h->stream));
     return YODA_OK;
   }
   if (mode == YODA_MODE_SCV && !rows && (h->kbub_dirty || (h->kbub_loose && !h->greedy_active)) &&
@@ -1612,13 +1604,8 @@ int phase2(yoda_t* h, int mode, const uint64_t* maxima, const uint32_t* counts, 
     HIP_TRY(h, h->p_idx.ensure(cp * 4));
     HIP_TRY(h, h->p_ties.ensure(cp * 4));
     part = partials(h);
-    if (modeb_elig_on(h))
-      HIP_TRY(h, launch_k2b_rows_elig(h->nodes_b.as<NodeRecB>(), h->n_nodes, pod_params(h),
-                                      modeb_cls_bytes(h), h->b_elig.as<DiskElig>(), P, part, rows,
-                                      h->stream));
-    else
-      HIP_TRY(h, launch_k2b_rows(h->nodes_b.as<NodeRecB>(), h->n_nodes, pod_params(h), P, part,
-                                 rows, h->stream));
+    HIP_TRY(h, launch_k2b_rows(h->nodes_b.as<NodeRecB>(), h->n_nodes, pod_params(h), P, part,
+                               rows, modeb_elig_args(h), h->stream));
   } else {
     // the block argmax K2 (N32 with summaries) marks the chunks it wrote (PodParams::cmask2)
     if (h->path == Path::N32 && h->has_k2sum && !rows) cmask2 = pod_params(h).cmask2;
@@ -2930,12 +2917,6 @@ static int draw_pass(yoda_t* h, int mode) {
   a.pod_base = h->tie_pod_base;
   a.node_offset = h->node_offset;
   const bool diskio = mode == YODA_MODE_DISKIO;
-  if (diskio && modeb_elig_on(h)) {  // the draw among the top-scored nodes of E
-    HIP_TRY(h, launch_draw_diskio_elig(h->nodes_b.as<NodeRecB>(), h->n_nodes, pod_params(h),
-                                       modeb_cls_bytes(h), h->b_elig.as<DiskElig>(), a,
-                                       h->stream));
-    return YODA_OK;
-  }
   // (the U64 path's finalize scattered the maxima to the caller's order: unpermute_outputs)
   if (!diskio && h->generic && h->maxima_sorted)
     return fail(h, YODA_ERR_STATE, "draw pass: generic maxima still in sorted order");
@@ -2943,7 +2924,9 @@ static int draw_pass(yoda_t* h, int mode) {
                          h->nodes_b.as<NodeRecB>(), h->n_nodes, pod_params(h),
                          h->rcp.as<double>(), h->maxima.as<uint64_t>(), h->lowest.as<int64_t>(),
                          h->bitmask.as<uint64_t>(), bm_row(h->n_nodes), h->bs_ptr(),
-                         bs_row(h->n_nodes), h->blk_ptr(), blk_row(h->n_nodes), a, h->stream));
+                         bs_row(h->n_nodes), h->blk_ptr(), blk_row(h->n_nodes), a,
+                         // (Mode B with eligibility: the draw among the top-scored nodes of E)
+                         diskio ? modeb_elig_args(h) : DiskEligArgs{}, h->stream));
   return YODA_OK;
 }
 

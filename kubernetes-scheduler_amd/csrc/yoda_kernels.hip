@@ -11,7 +11,8 @@
 //                          n_feasible, per-pod maxima)
 //   K2  k2_score_*         algorithm.go:264-310 composed as :96, scheduler.go:154,
 //                          argmax/ties/min for NormalizeScore + selectHost
-//   K2B k2_diskio          algorithm.go:99-119 (live Mode B)
+//   K2B k2b_*<ELIG>        algorithm.go:99-119 (Mode B: pod classes in batches, lane = node for
+//                          score rows; ELIG = the run honours absent nodes / candidate classes)
 //   K3  k3_exact_normalize scheduler.go:176-179 with int64 wrap (generic path only)
 //       k_draw_*           k8s selectHost as a seeded draw over each tied pod's tie set (a
 //                          post-pass with LANE = NODE, only with yoda_set_tie_draw enabled)
@@ -4258,304 +4259,15 @@ __global__ __launch_bounds__(kBlock) void k2_score_generic(
 
 // ---------------------------------------------------------------------------------------
 // K2B: BalancedCpuDiskIOPriority (algorithm.go:99-119), every node feasible
-// (Yoda.Filter is a pass-through, scheduler.go:96-99).  No FMA contraction (Go on amd64).
-template <bool ROWS>
-__global__ __launch_bounds__(kBlock) void k2_diskio(const NodeRecB* __restrict__ nodes,
-                                                    uint32_t n_nodes, uint32_t chunk_nodes,
-                                                    const double* __restrict__ alpha_in,
-                                                    const double* __restrict__ beta_in,
-                                                    uint32_t n_pods, double* __restrict__ pbest,
-                                                    uint32_t* __restrict__ pidx,
-                                                    uint32_t* __restrict__ pties,
-                                                    double* __restrict__ plow,
-                                                    int64_t* __restrict__ rows) {
-#pragma clang fp contract(off)
-  const Tile tl = tile();
-  const uint32_t p = tl.pb * kBlock + threadIdx.x;
-  const uint32_t chunk = tl.chunk;
-  const uint32_t n0 = chunk * chunk_nodes;
-  const uint32_t n1 = min(n0 + chunk_nodes, n_nodes);
-  const bool live = p < n_pods;
-  const double alpha = live ? alpha_in[p] : 0.0, beta = live ? beta_in[p] : 0.0;
-  double best = -1.0, low = 1.0e300;
-  uint32_t idx = 0xffffffffu, ties = 0;
-  for (uint32_t n = n0; n < n1; ++n) {
-    const NodeRecB r = nodes[n];
-    const double a = alpha * r.v;
-    const double b = beta * r.u;
-    const double l = fabs(a - b);             // :110
-    const double t = 10.0 * l;
-    const double s = 10.0 - t;                // :111
-    // uint64(Si) on amd64 then Uint64ToInt64: trunc for Si >= 1, else 0 (NaN, negatives)
-    const double score = (s >= 1.0) ? __builtin_trunc(s) : 0.0;
-    if constexpr (ROWS) {
-      if (live) rows[(size_t)n * n_pods + p] = (int64_t)score;
-    }
-    if (score > best) {
-      best = score;
-      idx = n;
-      ties = 1;
-    } else if (score == best) {
-      ++ties;
-    }
-    low = fmin(low, score);
-  }
-  if (!live) return;
-  const size_t o = (size_t)chunk * n_pods + p;
-  pbest[o] = best;
-  pidx[o] = idx;
-  pties[o] = ties;
-  plow[o] = low;
-}
-
-// K2B score rows (yoda_score_rows in Mode B, the plugin's per-cycle row): lane = node, one
-// 256-node chunk per workgroup, the pods of the (small) batch in turn -- every lane busy and
-// the row stores coalesced at P = 1, where the lane = pod kernel above runs one lane of 64.
-// Per pod the chunk's (best, lowest node, ties, lowest score) as k2_diskio's partials.
-__global__ __launch_bounds__(kBlock) void k2b_rows(const NodeRecB* __restrict__ nodes,
-                                                   uint32_t n_nodes,
-                                                   const double* __restrict__ alpha_in,
-                                                   const double* __restrict__ beta_in,
-                                                   uint32_t n_pods, double* __restrict__ pbest,
-                                                   uint32_t* __restrict__ pidx,
-                                                   uint32_t* __restrict__ pties,
-                                                   double* __restrict__ plow,
-                                                   int64_t* __restrict__ rows) {
-#pragma clang fp contract(off)
-  __shared__ double s_best[kBlock / kWave], s_low[kBlock / kWave];
-  __shared__ uint32_t s_idx[kBlock / kWave], s_ties[kBlock / kWave];
-  const uint32_t c = blockIdx.x, n = c * kBlock + threadIdx.x, w = threadIdx.x >> 6;
-  const bool v = n < n_nodes;
-  const NodeRecB r = v ? nodes[n] : NodeRecB{0.0, 0.0};
-  for (uint32_t p = 0; p < n_pods; ++p) {
-    const double alpha = alpha_in[p], beta = beta_in[p];
-    const double a = alpha * r.v;
-    const double b = beta * r.u;
-    const double l = fabs(a - b);  // algorithm.go:110
-    const double t = 10.0 * l;
-    const double sc = 10.0 - t;    // :111
-    // uint64(Si) on amd64 then Uint64ToInt64: trunc for Si >= 1, else 0 (NaN, negatives)
-    const double score = (sc >= 1.0) ? __builtin_trunc(sc) : 0.0;
-    if (v) rows[(size_t)n * n_pods + p] = (int64_t)score;
-    double best = v ? score : -1.0, low = v ? score : 1.0e300;
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) {
-      best = fmax(best, __shfl_xor(best, o, kWave));
-      low = fmin(low, __shfl_xor(low, o, kWave));
-    }
-    const bool at = v && score == best;
-    const uint64_t bb = ballot(at);
-    if ((threadIdx.x & (kWave - 1)) == 0) {
-      s_best[w] = best;
-      s_low[w] = low;
-      s_idx[w] = bb ? (c * kBlock + w * kWave + (uint32_t)__builtin_ctzll(bb)) : 0xffffffffu;
-      s_ties[w] = (uint32_t)__builtin_popcountll(bb);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      double B = -1.0, L = 1.0e300;
-      uint32_t I = 0xffffffffu, T = 0;
-      for (int k = 0; k < kBlock / kWave; ++k) {  // waves in node order: strict '>' keeps lowest
-        if (s_best[k] > B) {
-          B = s_best[k];
-          I = s_idx[k];
-          T = s_ties[k];
-        } else if (s_best[k] == B && s_ties[k]) {
-          T += s_ties[k];
-        }
-        L = fmin(L, s_low[k]);
-      }
-      const size_t o = (size_t)c * n_pods + p;
-      pbest[o] = B;
-      pidx[o] = I;
-      pties[o] = T;
-      plow[o] = L;
-    }
-    __syncthreads();
-  }
-}
-
-// ---------------------------------------------------------------------------------------
-// K2B batch path (DESIGN.md §4, Mode B): the same score over pod CLASSES -- the distinct
-// (alpha, beta) bit pairs of the batch (algorithm.go:105-106).  Pods of one class score every
-// node alike, so their outcome is the class's.  Per pair: a = alpha*V, b = beta*U, d = a - b
-// (:109), and the level of |d| against DiskLevels (score >= k <=> |d| <= t[k]): three f64
-// operations, two compares.  A lane keeps, over nodes in increasing order, the best level
-// seen, its node count and its first (lowest) node; level 0 counts nothing while running
-// (every node is >= 0, NaN included) and is settled at the end.
-// (DiskAcc, disk_init, disk_step: yoda_modeb.h, shared with the host.)
-
-// Lane = class: each lane runs CPL classes over the chunk's nodes, one node record per
-// iteration read by a scalar (wave-uniform) load.
-template <int CPL>
-__global__ __launch_bounds__(kBlock) void k2b_class_lanes(const NodeRecB* __restrict__ nodes,
-                                                          uint32_t n_nodes, uint32_t chunk_nodes,
-                                                          const double* __restrict__ cab,
-                                                          uint32_t n_cls, DiskLevels lvs,
-                                                          uint32_t* __restrict__ plc,
-                                                          uint32_t* __restrict__ pidx) {
-#pragma clang fp contract(off)
-  __shared__ double lv[12];
-  if (threadIdx.x < 12) lv[threadIdx.x] = lvs.t[threadIdx.x];
-  __syncthreads();
-  const uint32_t chunk = blockIdx.y;
-  const uint32_t n0 = chunk * chunk_nodes;
-  const uint32_t n1 = min(n0 + chunk_nodes, n_nodes);
-  const uint32_t c0 = blockIdx.x * (kBlock * CPL) + threadIdx.x;
-  double al[CPL], be[CPL];
-  DiskAcc s[CPL];
-#pragma unroll
-  for (int j = 0; j < CPL; ++j) {
-    const uint32_t c = c0 + j * kBlock;
-    al[j] = c < n_cls ? cab[c] : 0.0;
-    be[j] = c < n_cls ? cab[(size_t)n_cls + c] : 0.0;
-    disk_init(s[j], lv);
-  }
-  // 8 node records per trip: the scalar loads are issued together, one wait per trip
-  constexpr int kTrip = 8;
-  uint32_t n = n0;
-  for (; n + kTrip <= n1; n += kTrip) {
-    NodeRecB r[kTrip];
-#pragma unroll
-    for (int i = 0; i < kTrip; ++i) r[i] = nodes[n + i];
-#pragma unroll
-    for (int i = 0; i < kTrip; ++i) {
-#pragma unroll
-      for (int j = 0; j < CPL; ++j) {
-        const double a = al[j] * r[i].v;
-        const double b = be[j] * r[i].u;
-        disk_step(s[j], fabs(a - b), n + i, lv);
-      }
-    }
-  }
-  for (; n < n1; ++n) {
-    const NodeRecB r = nodes[n];
-#pragma unroll
-    for (int j = 0; j < CPL; ++j) {
-      const double a = al[j] * r.v;
-      const double b = be[j] * r.u;
-      disk_step(s[j], fabs(a - b), n, lv);
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < CPL; ++j) {
-    const uint32_t c = c0 + j * kBlock;
-    if (c >= n_cls) continue;
-    uint32_t cnt = s[j].cnt, idx = s[j].idx;
-    if (s[j].lev == 0u) {
-      cnt = n1 - n0;
-      idx = n0;
-    }
-    plc[(size_t)chunk * n_cls + c] = (s[j].lev << kDiskCountBits) | cnt;
-    pidx[(size_t)chunk * n_cls + c] = idx;
-  }
-}
-
-// Lane = node, one class per workgroup (batches of few classes, e.g. one pod spec): each
-// thread strides over the chunk's nodes, then the workgroup merges (max level; at it, count
-// sum and lowest node).
-__global__ __launch_bounds__(kBlock) void k2b_node_lanes(const NodeRecB* __restrict__ nodes,
-                                                         uint32_t n_nodes, uint32_t chunk_nodes,
-                                                         const double* __restrict__ cab,
-                                                         uint32_t n_cls, DiskLevels lvs,
-                                                         uint32_t* __restrict__ plc,
-                                                         uint32_t* __restrict__ pidx) {
-#pragma clang fp contract(off)
-  __shared__ double lv[12];
-  __shared__ uint32_t red[3][kBlock / kWave];
-  if (threadIdx.x < 12) lv[threadIdx.x] = lvs.t[threadIdx.x];
-  __syncthreads();
-  const uint32_t chunk = blockIdx.x, c = blockIdx.y;
-  const uint32_t n0 = chunk * chunk_nodes;
-  const uint32_t n1 = min(n0 + chunk_nodes, n_nodes);
-  const double al = cab[c], be = cab[(size_t)n_cls + c];
-  DiskAcc s;
-  disk_init(s, lv);
-  uint32_t seen = 0;
-  for (uint32_t n = n0 + threadIdx.x; n < n1; n += kBlock, ++seen) {
-    const NodeRecB r = nodes[n];
-    const double a = al * r.v;
-    const double b = be * r.u;
-    disk_step(s, fabs(a - b), n, lv);
-  }
-  if (s.lev == 0u) {
-    s.cnt = seen;
-    s.idx = seen ? n0 + threadIdx.x : 0xffffffffu;
-  }
-  const uint32_t L = wave_max_u32(s.lev);
-  uint32_t cnt = s.lev == L ? s.cnt : 0u;
-  uint32_t idx = s.lev == L ? s.idx : 0xffffffffu;
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) {
-    cnt += (uint32_t)__shfl_xor((int)cnt, o, kWave);
-    idx = min(idx, (uint32_t)__shfl_xor((int)idx, o, kWave));
-  }
-  const uint32_t w = threadIdx.x / kWave;
-  if (lane_id() == 0) {
-    red[0][w] = L;
-    red[1][w] = cnt;
-    red[2][w] = idx;
-  }
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  uint32_t bl = 0, bc = 0, bi = 0xffffffffu;
-  for (int i = 0; i < kBlock / kWave; ++i) {
-    if (red[1][i] == 0u) continue;  // a wave with no node of this chunk
-    if (red[0][i] > bl) {
-      bl = red[0][i];
-      bc = red[1][i];
-      bi = red[2][i];
-    } else if (red[0][i] == bl) {
-      bc += red[1][i];
-      bi = min(bi, red[2][i]);
-    }
-  }
-  plc[(size_t)chunk * n_cls + c] = (bl << kDiskCountBits) | bc;
-  pidx[(size_t)chunk * n_cls + c] = bi;
-}
-
-// Per pod: its class's chunk partials (chunks in node order: the first chunk reaching the best
-// level holds the lowest node) -> best level, lowest node (+ node_offset), count.  Mode B
-// scores lie in [0, 10], so NormalizeScore cannot overflow and the lowest score is not needed
-// (written as 0).
-__global__ __launch_bounds__(kBlock) void k_reduce2b(const uint32_t* __restrict__ plc,
-                                                     const uint32_t* __restrict__ pidx,
-                                                     uint32_t C, uint32_t n_cls,
-                                                     const uint32_t* __restrict__ cls,
-                                                     uint32_t n_pods, uint32_t node_offset,
-                                                     int64_t* __restrict__ best_out,
-                                                     uint32_t* __restrict__ idx_out,
-                                                     uint32_t* __restrict__ ties_out,
-                                                     int64_t* __restrict__ low_out) {
-  const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
-  if (p >= n_pods) return;
-  const uint32_t c = cls[p];
-  int64_t bl = -1;
-  uint32_t bc = 0, bi = 0xffffffffu;
-  for (uint32_t k = 0; k < C; ++k) {
-    const uint32_t w = plc[(size_t)k * n_cls + c];
-    const int64_t L = (int64_t)(w >> kDiskCountBits);
-    if (L > bl) {
-      bl = L;
-      bc = w & ((1u << kDiskCountBits) - 1u);
-      bi = pidx[(size_t)k * n_cls + c];
-    } else if (L == bl) {
-      bc += w & ((1u << kDiskCountBits) - 1u);
-    }
-  }
-  best_out[p] = bl;
-  idx_out[p] = bi == 0xffffffffu ? bi : bi + node_offset;
-  ties_out[p] = bc;
-  low_out[p] = 0;
-}
-
-// ---------------------------------------------------------------------------------------
-// K2B with eligibility (yoda_mode_b_follow): pod class c walks only the nodes of
-// E = present and candidates of its selector csel[c] (yoda_modeb.h DiskElig).  Siblings of the
-// kernels above, launched only while a node is absent or a pod names a candidate class: the
-// unrestricted kernels stay as they are.  A lane keeps, beside its accumulator, the eligible
-// nodes it stepped over and the first of them (DiskSeen): level 0 settles from those, and a
-// (chunk, class) with no eligible node writes count 0, which every merge skips.
+// (Yoda.Filter is a pass-through, scheduler.go:96-99).  No FMA contraction (Go on amd64): the
+// score is yoda_modeb.h's disk_absdiff / disk_score, shared with the host.
+//
+// One kernel per role, each a template over ELIG (yoda_mode_b_follow).  ELIG =
+// false is the unrestricted run: every node counts.  ELIG = true runs while a node is absent or
+// a pod names a candidate class: pod class c (pod p) walks only the nodes of E = present and
+// candidates of its selector (yoda_modeb.h DiskElig, DiskEligArgs).  The eligibility parts sit
+// under `if constexpr (ELIG)`, so the unrestricted instance holds no table load, no mask and no
+// second walk, and reads nothing of its DiskEligArgs.
 
 // The eligibility table and its 65 counts (nodes of each class, present nodes) from the candidate
 // words (upload order; nullptr: candidates off) and the presence bitmap.  cnt is zeroed by the
@@ -4587,18 +4299,129 @@ __global__ __launch_bounds__(kBlock) void k_modeb_elig_build(const uint64_t* __r
   if (lane == 0 && any) atomicAdd(&cnt[kDiskSelAny], any);
 }
 
-// Lane = class: the lanes of a wave walk the same nodes under different selectors, so the step
-// is branch-free (disk_step_masked) and the level-0 settle walks the words again when it must.
-template <int CPL>
-__global__ __launch_bounds__(kBlock) void k2b_class_lanes_elig(
-    const NodeRecB* __restrict__ nodes, uint32_t n_nodes, uint32_t chunk_nodes,
-    const double* __restrict__ cab, const uint32_t* __restrict__ csel, uint32_t n_cls,
-    DiskLevels lvs, const DiskElig* __restrict__ elig, uint32_t* __restrict__ plc,
-    uint32_t* __restrict__ pidx) {
-#pragma clang fp contract(off)
-  __shared__ double lv[12];
+// The wave's and then the workgroup's (best, lowest score, lowest node at the best, nodes at it)
+// over the lanes with v set, stored as pod p's partial of chunk c; every thread of the workgroup
+// calls it.
+__device__ __forceinline__ void k2b_rows_merge(bool v, double score, uint32_t c, uint32_t p,
+                                               uint32_t n_pods, double* __restrict__ pbest,
+                                               uint32_t* __restrict__ pidx,
+                                               uint32_t* __restrict__ pties,
+                                               double* __restrict__ plow) {
+  __shared__ double s_best[kBlock / kWave], s_low[kBlock / kWave];
+  __shared__ uint32_t s_idx[kBlock / kWave], s_ties[kBlock / kWave];
+  const uint32_t w = threadIdx.x >> 6;
+  double best = v ? score : -1.0, low = v ? score : 1.0e300;
+#pragma unroll
+  for (int o = kWave / 2; o > 0; o >>= 1) {
+    best = fmax(best, __shfl_xor(best, o, kWave));
+    low = fmin(low, __shfl_xor(low, o, kWave));
+  }
+  const bool at = v && score == best;
+  const uint64_t bb = ballot(at);
+  if ((threadIdx.x & (kWave - 1)) == 0) {
+    s_best[w] = best;
+    s_low[w] = low;
+    s_idx[w] = bb ? (c * kBlock + w * kWave + (uint32_t)__builtin_ctzll(bb)) : 0xffffffffu;
+    s_ties[w] = (uint32_t)__builtin_popcountll(bb);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double B = -1.0, L = 1.0e300;
+    uint32_t I = 0xffffffffu, T = 0;
+    for (int k = 0; k < kBlock / kWave; ++k) {  // waves in node order: strict '>' keeps lowest
+      if (s_best[k] > B) {
+        B = s_best[k];
+        I = s_idx[k];
+        T = s_ties[k];
+      } else if (s_best[k] == B && s_ties[k]) {
+        T += s_ties[k];
+      }
+      L = fmin(L, s_low[k]);
+    }
+    const size_t o = (size_t)c * n_pods + p;
+    pbest[o] = B;
+    pidx[o] = I;
+    pties[o] = T;
+    plow[o] = L;
+  }
+  __syncthreads();
+}
+
+// K2B score rows (yoda_score_rows in Mode B, the plugin's per-cycle row): lane = node, one
+// 256-node chunk per workgroup, the pods of the (small) batch in turn -- every lane busy and
+// the row stores coalesced at P = 1.  Per pod the chunk's (best, lowest node, ties, lowest
+// score) partials, as k_reduce2 merges them.  ELIG: a node outside the pod's E keeps the row's
+// -1 (the caller's fill) and stays out of best, low, idx and ties.
+template <bool ELIG>
+__global__ __launch_bounds__(kBlock) void k2b_rows(const NodeRecB* __restrict__ nodes,
+                                                   uint32_t n_nodes,
+                                                   const double* __restrict__ alpha_in,
+                                                   const double* __restrict__ beta_in,
+                                                   uint32_t n_pods, double* __restrict__ pbest,
+                                                   uint32_t* __restrict__ pidx,
+                                                   uint32_t* __restrict__ pties,
+                                                   double* __restrict__ plow,
+                                                   int64_t* __restrict__ rows, DiskEligArgs ea) {
+  const uint32_t c = blockIdx.x, n = c * kBlock + threadIdx.x;
+  const bool in = n < n_nodes;
+  const NodeRecB r = in ? nodes[n] : NodeRecB{0.0, 0.0};
+  DiskElig e{0ull, 0ull};
+  if constexpr (ELIG) {
+    if (in) e = ea.elig[n];
+  }
+  for (uint32_t p = 0; p < n_pods; ++p) {
+    bool v = in;
+    if constexpr (ELIG) v = disk_eligible(e, ea.cls ? disk_sel(ea.cls[p]) : kDiskSelAny);
+    const double score = disk_score(disk_absdiff(alpha_in[p], r.v, beta_in[p], r.u));
+    if (v) rows[(size_t)n * n_pods + p] = (int64_t)score;
+    k2b_rows_merge(v, score, c, p, n_pods, pbest, pidx, pties, plow);
+  }
+}
+
+// ---------------------------------------------------------------------------------------
+// K2B batch path (DESIGN.md §4, Mode B): the same score over pod CLASSES -- the distinct
+// (alpha, beta) bit pairs of the batch (algorithm.go:105-106), with eligibility the (alpha, beta,
+// selector) triples.  Pods of one class score every node alike, so their outcome is the class's.
+// Per pair: |d| = |alpha*V - beta*U| (:109-110), and the level of |d| against DiskLevels (score
+// >= k <=> |d| <= t[k]): three f64 operations, two compares.  A lane keeps, over nodes in
+// increasing order, the best level seen, its node count and its first (lowest) node; level 0
+// counts nothing while running (every node is >= 0, NaN included) and is settled at the end:
+// from the chunk's bounds, or with ELIG from the eligible nodes seen (DiskSeen).  A (chunk,
+// class) with no eligible node writes count 0, which every merge skips.
+// (DiskAcc, disk_init, disk_step, disk_settle, the merges: yoda_modeb.h, shared with the host.)
+
+// The level table into LDS; every thread of the workgroup calls it.
+__device__ __forceinline__ void disk_levels_to_lds(double* lv, const DiskLevels& lvs) {
   if (threadIdx.x < 12) lv[threadIdx.x] = lvs.t[threadIdx.x];
   __syncthreads();
+}
+
+// One (node, class) pair of the lane = class walk.  ELIG: the lanes of a wave walk the same nodes
+// under different selectors, so the step is branch-free (disk_step_masked).
+template <bool ELIG>
+__device__ __forceinline__ void k2b_pair(DiskAcc& s, double al, double be, const NodeRecB& r,
+                                         const DiskElig& e, const DiskSelMask& m, uint32_t n,
+                                         const double* lv) {
+  const double ad = disk_absdiff(al, r.v, be, r.u);
+  if constexpr (ELIG)
+    disk_step_masked(s, disk_eligible(e, m), ad, n, lv);
+  else
+    disk_step(s, ad, n, lv);
+}
+
+// Lane = class: each lane runs CPL classes over the chunk's nodes, one node record (ELIG: and
+// its eligibility record) per iteration read by a scalar (wave-uniform) load.
+template <int CPL, bool ELIG>
+__global__ __launch_bounds__(kBlock) void k2b_class_lanes(const NodeRecB* __restrict__ nodes,
+                                                          uint32_t n_nodes, uint32_t chunk_nodes,
+                                                          const double* __restrict__ cab,
+                                                          uint32_t n_cls, DiskLevels lvs,
+                                                          uint32_t* __restrict__ plc,
+                                                          uint32_t* __restrict__ pidx,
+                                                          DiskEligArgs ea) {
+  __shared__ double lv[12];
+  disk_levels_to_lds(lv, lvs);
+  const DiskElig* __restrict__ elig = ea.elig;
   const uint32_t chunk = blockIdx.y;
   const uint32_t n0 = chunk * chunk_nodes;
   const uint32_t n1 = min(n0 + chunk_nodes, n_nodes);
@@ -4611,10 +4434,11 @@ __global__ __launch_bounds__(kBlock) void k2b_class_lanes_elig(
     const uint32_t c = c0 + j * kBlock;
     al[j] = c < n_cls ? cab[c] : 0.0;
     be[j] = c < n_cls ? cab[(size_t)n_cls + c] : 0.0;
-    sm[j] = disk_sel_mask(c < n_cls ? csel[c] : kDiskSelAny);
+    sm[j] = DiskSelMask{0u, 0u, 0u};
+    if constexpr (ELIG) sm[j] = disk_sel_mask(c < n_cls ? ea.csel[c] : kDiskSelAny);
     disk_init(s[j], lv);
   }
-  // 8 node records and their eligibility words per trip: wave-uniform loads issued together
+  // 8 records per trip: the scalar loads are issued together, one wait per trip
   constexpr int kTrip = 8;
   uint32_t n = n0;
   for (; n + kTrip <= n1; n += kTrip) {
@@ -4623,83 +4447,98 @@ __global__ __launch_bounds__(kBlock) void k2b_class_lanes_elig(
 #pragma unroll
     for (int i = 0; i < kTrip; ++i) {
       r[i] = nodes[n + i];
-      e[i] = elig[n + i];
+      e[i] = DiskElig{0ull, 0ull};
+      if constexpr (ELIG) e[i] = elig[n + i];
     }
 #pragma unroll
     for (int i = 0; i < kTrip; ++i) {
 #pragma unroll
-      for (int j = 0; j < CPL; ++j) {
-        const double a = al[j] * r[i].v;
-        const double b = be[j] * r[i].u;
-        disk_step_masked(s[j], disk_eligible(e[i], sm[j]), fabs(a - b), n + i, lv);
-      }
+      for (int j = 0; j < CPL; ++j) k2b_pair<ELIG>(s[j], al[j], be[j], r[i], e[i], sm[j], n + i, lv);
     }
   }
   for (; n < n1; ++n) {
     const NodeRecB r = nodes[n];
-    const DiskElig e = elig[n];
+    DiskElig e{0ull, 0ull};
+    if constexpr (ELIG) e = elig[n];
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) k2b_pair<ELIG>(s[j], al[j], be[j], r, e, sm[j], n, lv);
+  }
+  // level 0: every node of the chunk, or with ELIG the eligible ones and the first of them,
+  // which takes a second walk over the words (rare: every eligible node of the chunk scores 0)
+  DiskSeen sn[CPL];
+  if constexpr (ELIG) {
+    bool zero = false;
 #pragma unroll
     for (int j = 0; j < CPL; ++j) {
-      const double a = al[j] * r.v;
-      const double b = be[j] * r.u;
-      disk_step_masked(s[j], disk_eligible(e, sm[j]), fabs(a - b), n, lv);
+      disk_seen_init(sn[j]);
+      zero = zero || s[j].lev == 0u;
     }
-  }
-  // level 0 is settled from the eligible nodes of the chunk and the first of them
-  DiskSeen sn[CPL];
-  bool zero = false;
+    if (ballot(zero) != 0ull) {  // (wave-uniform: the words stay wave-uniform loads)
+      for (n = n0; n < n1; ++n) {
+        const DiskElig e = elig[n];
 #pragma unroll
-  for (int j = 0; j < CPL; ++j) {
-    disk_seen_init(sn[j]);
-    zero = zero || s[j].lev == 0u;
-  }
-  if (ballot(zero) != 0ull) {  // (wave-uniform: the words stay wave-uniform loads)
-    for (n = n0; n < n1; ++n) {
-      const DiskElig e = elig[n];
-#pragma unroll
-      for (int j = 0; j < CPL; ++j) disk_seen_add(sn[j], disk_eligible(e, sm[j]), n);
+        for (int j = 0; j < CPL; ++j) disk_seen_add(sn[j], disk_eligible(e, sm[j]), n);
+      }
     }
   }
 #pragma unroll
   for (int j = 0; j < CPL; ++j) {
     const uint32_t c = c0 + j * kBlock;
     if (c >= n_cls) continue;
-    uint32_t cnt, idx;
-    disk_settle(s[j], sn[j], cnt, idx);
+    uint32_t cnt = s[j].cnt, idx = s[j].idx;
+    if constexpr (ELIG) {
+      disk_settle(s[j], sn[j], cnt, idx);
+    } else if (s[j].lev == 0u) {  // every node of the chunk, from its bounds
+      cnt = n1 - n0;
+      idx = n0;
+    }
     plc[(size_t)chunk * n_cls + c] = disk_pack(s[j].lev, cnt);
     pidx[(size_t)chunk * n_cls + c] = idx;
   }
 }
 
-__global__ __launch_bounds__(kBlock) void k2b_node_lanes_elig(
-    const NodeRecB* __restrict__ nodes, uint32_t n_nodes, uint32_t chunk_nodes,
-    const double* __restrict__ cab, const uint32_t* __restrict__ csel, uint32_t n_cls,
-    DiskLevels lvs, const DiskElig* __restrict__ elig, uint32_t* __restrict__ plc,
-    uint32_t* __restrict__ pidx) {
-#pragma clang fp contract(off)
+// Lane = node, one class per workgroup (batches of few classes, e.g. one pod spec): each
+// thread strides over the chunk's nodes (ELIG: the eligible ones), then the wave and the
+// workgroup merge (max level; at it, count sum and lowest node).
+template <bool ELIG>
+__global__ __launch_bounds__(kBlock) void k2b_node_lanes(const NodeRecB* __restrict__ nodes,
+                                                         uint32_t n_nodes, uint32_t chunk_nodes,
+                                                         const double* __restrict__ cab,
+                                                         uint32_t n_cls, DiskLevels lvs,
+                                                         uint32_t* __restrict__ plc,
+                                                         uint32_t* __restrict__ pidx,
+                                                         DiskEligArgs ea) {
   __shared__ double lv[12];
   __shared__ uint32_t red[3][kBlock / kWave];
-  if (threadIdx.x < 12) lv[threadIdx.x] = lvs.t[threadIdx.x];
-  __syncthreads();
+  disk_levels_to_lds(lv, lvs);
   const uint32_t chunk = blockIdx.x, c = blockIdx.y;
   const uint32_t n0 = chunk * chunk_nodes;
   const uint32_t n1 = min(n0 + chunk_nodes, n_nodes);
   const double al = cab[c], be = cab[(size_t)n_cls + c];
-  const uint32_t sel = csel[c];
+  uint32_t sel = kDiskSelAny;
+  if constexpr (ELIG) sel = ea.csel[c];
   DiskAcc s;
   DiskSeen sn;
   disk_init(s, lv);
   disk_seen_init(sn);
   for (uint32_t n = n0 + threadIdx.x; n < n1; n += kBlock) {
-    if (!disk_eligible(elig[n], sel)) continue;
+    if constexpr (ELIG) {
+      if (!disk_eligible(ea.elig[n], sel)) continue;
+    }
     const NodeRecB r = nodes[n];
-    const double a = al * r.v;
-    const double b = be * r.u;
-    disk_step_elig(s, sn, fabs(a - b), n, lv);
+    const double ad = disk_absdiff(al, r.v, be, r.u);
+    if constexpr (ELIG) {
+      disk_step_elig(s, sn, ad, n, lv);
+    } else {
+      disk_step(s, ad, n, lv);
+      ++sn.n;
+    }
   }
+  // (unrestricted: the lane's first node follows from the chunk's bounds)
+  if constexpr (!ELIG) sn.first = sn.n ? n0 + threadIdx.x : 0xffffffffu;
   uint32_t mc, mi;
   disk_settle(s, sn, mc, mi);
-  // the wave's best level among the lanes that hold an eligible node
+  // the wave's best level among the lanes that hold a node
   const uint32_t L = wave_max_u32(mc ? s.lev : 0u);
   uint32_t cnt = s.lev == L ? mc : 0u;
   uint32_t idx = (s.lev == L && mc) ? mi : 0xffffffffu;
@@ -4719,109 +4558,36 @@ __global__ __launch_bounds__(kBlock) void k2b_node_lanes_elig(
   DiskBest b;
   disk_best_init(b);
   for (int i = 0; i < kBlock / kWave; ++i) disk_merge_any(b, red[0][i], red[1][i], red[2][i]);
-  // (no eligible node of this class in the chunk: count 0, skipped by the chunk merge)
+  // (no node of this class in the chunk: count 0, skipped by the chunk merge)
   plc[(size_t)chunk * n_cls + c] = b.cnt ? disk_pack((uint32_t)b.lev, b.cnt) : 0u;
   pidx[(size_t)chunk * n_cls + c] = b.idx;
 }
 
-// k_reduce2b over partials that may be empty (count 0): disk_merge_chunk skips them, so a class
-// with no eligible node at all ends at best -1, no node, count 0.
-__global__ __launch_bounds__(kBlock) void k_reduce2b_elig(const uint32_t* __restrict__ plc,
-                                                          const uint32_t* __restrict__ pidx,
-                                                          uint32_t C, uint32_t n_cls,
-                                                          const uint32_t* __restrict__ cls,
-                                                          uint32_t n_pods, uint32_t node_offset,
-                                                          int64_t* __restrict__ best_out,
-                                                          uint32_t* __restrict__ idx_out,
-                                                          uint32_t* __restrict__ ties_out,
-                                                          int64_t* __restrict__ low_out) {
+// Per pod: its class's chunk partials (chunks in node order: the first chunk reaching the best
+// level holds the lowest node; disk_merge_chunk skips the empty ones) -> best level, lowest
+// node (+ node_offset), count.  A class with no eligible node at all ends at best -1, no node,
+// count 0.  Mode B scores lie in [0, 10], so NormalizeScore cannot overflow and the lowest
+// score is not needed (written as 0).
+__global__ __launch_bounds__(kBlock) void k_reduce2b(const uint32_t* __restrict__ plc,
+                                                     const uint32_t* __restrict__ pidx,
+                                                     uint32_t C, uint32_t n_cls,
+                                                     const uint32_t* __restrict__ cls,
+                                                     uint32_t n_pods, uint32_t node_offset,
+                                                     int64_t* __restrict__ best_out,
+                                                     uint32_t* __restrict__ idx_out,
+                                                     uint32_t* __restrict__ ties_out,
+                                                     int64_t* __restrict__ low_out) {
   const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
   if (p >= n_pods) return;
   const uint32_t c = cls[p];
   DiskBest b;
   disk_best_init(b);
   for (uint32_t k = 0; k < C; ++k)
-    disk_merge_chunk(b, plc[(size_t)k * n_cls + c], pidx[(size_t)k * n_cls + c]);
+    disk_merge_chunk(b, plc[(size_t)k * n_cls + c], &pidx[(size_t)k * n_cls + c]);
   best_out[p] = b.lev;
   idx_out[p] = b.idx == 0xffffffffu ? b.idx : b.idx + node_offset;
   ties_out[p] = b.cnt;
   low_out[p] = 0;
-}
-
-// k_fill_diskio_state with eligibility: n_feasible[p] = the count of the pod's selector.
-// cls: the pods' candidate class bytes (caller order: Mode B runs are never reordered), or
-// nullptr: every pod YODA_CAND_ANY.
-__global__ __launch_bounds__(kBlock) void k_fill_diskio_state_elig(
-    uint32_t n_pods, const uint8_t* __restrict__ cls, const uint32_t* __restrict__ cnt,
-    uint64_t* __restrict__ maxima, uint32_t* __restrict__ counts) {
-  const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
-  if (p >= n_pods) return;
-  for (int f = 0; f < 6; ++f) maxima[(size_t)f * n_pods + p] = 1;
-  counts[p] = cnt[cls ? disk_sel(cls[p]) : kDiskSelAny];
-  counts[(size_t)n_pods + p] = 0;
-}
-
-// k2b_rows with eligibility: a node outside the pod's E keeps the row's -1 (the caller's fill)
-// and stays out of best, low, idx and ties.
-__global__ __launch_bounds__(kBlock) void k2b_rows_elig(
-    const NodeRecB* __restrict__ nodes, uint32_t n_nodes, const double* __restrict__ alpha_in,
-    const double* __restrict__ beta_in, const uint8_t* __restrict__ cls,
-    const DiskElig* __restrict__ elig, uint32_t n_pods, double* __restrict__ pbest,
-    uint32_t* __restrict__ pidx, uint32_t* __restrict__ pties, double* __restrict__ plow,
-    int64_t* __restrict__ rows) {
-#pragma clang fp contract(off)
-  __shared__ double s_best[kBlock / kWave], s_low[kBlock / kWave];
-  __shared__ uint32_t s_idx[kBlock / kWave], s_ties[kBlock / kWave];
-  const uint32_t c = blockIdx.x, n = c * kBlock + threadIdx.x, w = threadIdx.x >> 6;
-  const bool in = n < n_nodes;
-  const NodeRecB r = in ? nodes[n] : NodeRecB{0.0, 0.0};
-  const DiskElig e = in ? elig[n] : DiskElig{0ull, 0ull};
-  for (uint32_t p = 0; p < n_pods; ++p) {
-    const bool v = disk_eligible(e, cls ? disk_sel(cls[p]) : kDiskSelAny);
-    const double alpha = alpha_in[p], beta = beta_in[p];
-    const double a = alpha * r.v;
-    const double b = beta * r.u;
-    const double l = fabs(a - b);  // algorithm.go:110
-    const double t = 10.0 * l;
-    const double sc = 10.0 - t;    // :111
-    const double score = (sc >= 1.0) ? __builtin_trunc(sc) : 0.0;
-    if (v) rows[(size_t)n * n_pods + p] = (int64_t)score;
-    double best = v ? score : -1.0, low = v ? score : 1.0e300;
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) {
-      best = fmax(best, __shfl_xor(best, o, kWave));
-      low = fmin(low, __shfl_xor(low, o, kWave));
-    }
-    const bool at = v && score == best;
-    const uint64_t bb = ballot(at);
-    if ((threadIdx.x & (kWave - 1)) == 0) {
-      s_best[w] = best;
-      s_low[w] = low;
-      s_idx[w] = bb ? (c * kBlock + w * kWave + (uint32_t)__builtin_ctzll(bb)) : 0xffffffffu;
-      s_ties[w] = (uint32_t)__builtin_popcountll(bb);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      double B = -1.0, L = 1.0e300;
-      uint32_t I = 0xffffffffu, T = 0;
-      for (int k = 0; k < kBlock / kWave; ++k) {  // waves in node order: strict '>' keeps lowest
-        if (s_best[k] > B) {
-          B = s_best[k];
-          I = s_idx[k];
-          T = s_ties[k];
-        } else if (s_best[k] == B && s_ties[k]) {
-          T += s_ties[k];
-        }
-        L = fmin(L, s_low[k]);
-      }
-      const size_t o = (size_t)c * n_pods + p;
-      pbest[o] = B;
-      pidx[o] = I;
-      pties[o] = T;
-      plow[o] = L;
-    }
-    __syncthreads();
-  }
 }
 
 // Per-pod merge of K2 chunk partials.  Chunks are in node order, so on equal scores the
@@ -4954,14 +4720,18 @@ __global__ __launch_bounds__(kBlock) void k_merge_prepare(const int64_t* __restr
   }
 }
 
-// Mode B: every node passes Filter.
+// Mode B: every node passes Filter (cnt == nullptr), or with eligibility n_feasible[p] = |E(p)|,
+// the count of the pod's selector.  cnt: the [kDiskSelCount] count table; cls: the pods' candidate
+// class bytes (caller order: Mode B runs are never reordered), or nullptr: every pod YODA_CAND_ANY.
 __global__ __launch_bounds__(kBlock) void k_fill_diskio_state(uint32_t n_pods, uint32_t n_nodes,
+                                                              const uint32_t* __restrict__ cnt,
+                                                              const uint8_t* __restrict__ cls,
                                                               uint64_t* __restrict__ maxima,
                                                               uint32_t* __restrict__ counts) {
   const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
   if (p >= n_pods) return;
   for (int f = 0; f < 6; ++f) maxima[(size_t)f * n_pods + p] = 1;
-  counts[p] = n_nodes;
+  counts[p] = cnt ? cnt[cls ? disk_sel(cls[p]) : kDiskSelAny] : n_nodes;
   counts[(size_t)n_pods + p] = 0;
 }
 
@@ -5494,7 +5264,9 @@ int kernel_capacity(int K, Path path, int which, int mode_diskio) {
   const void* fn = nullptr;
 #define YODA_FN(expr) fn = reinterpret_cast<const void*>(expr)
   if (mode_diskio) {
-    YODA_FN(&k2_diskio<false>);
+    // (Mode B plans its own chunks -- diskio_plan, the rows kernel's 256-node chunks -- so this
+    // only sizes the handle's shared partial buffers: the unrestricted rows kernel stands for it)
+    YODA_FN(&k2b_rows<false>);
   } else if (which == 1) {
     switch (path) {
       // (the one-model tiles' kernel: the chunk plan of config 3 as measured)
@@ -6115,30 +5887,6 @@ hipError_t launch_k2(int K, Path path, const unsigned char* nodes, const unsigne
                                  nullptr, stats, counts, s);
 }
 
-hipError_t launch_k2b_rows(const NodeRecB* nodes, uint32_t n_nodes, const PodParams& pp,
-                           uint32_t n_pods, const Partials& part, int64_t* rows, hipStream_t s) {
-  if (n_nodes == 0 || n_pods == 0) return hipSuccess;
-  hipLaunchKernelGGL(k2b_rows, dim3((n_nodes + kBlock - 1) / kBlock), dim3(kBlock), 0, s, nodes,
-                     n_nodes, pp.alpha, pp.beta, n_pods, part.best_f, part.idx, part.ties,
-                     part.low_f, rows);
-  return hipGetLastError();
-}
-
-hipError_t launch_k2_diskio(const NodeRecB* nodes, uint32_t n_nodes, uint32_t chunk_nodes,
-                            uint32_t C, const PodParams& pp, uint32_t n_pods, const Partials& part,
-                            int64_t* rows, hipStream_t s) {
-  dim3 grid((n_pods + kBlock - 1) / kBlock, C);
-  if (rows)
-    hipLaunchKernelGGL(k2_diskio<true>, grid, dim3(kBlock), 0, s, nodes, n_nodes, chunk_nodes,
-                       pp.alpha, pp.beta, n_pods, part.best_f, part.idx, part.ties, part.low_f,
-                       rows);
-  else
-    hipLaunchKernelGGL(k2_diskio<false>, grid, dim3(kBlock), 0, s, nodes, n_nodes, chunk_nodes,
-                       pp.alpha, pp.beta, n_pods, part.best_f, part.idx, part.ties, part.low_f,
-                       rows);
-  return hipGetLastError();
-}
-
 // Mode B batch plan: few classes (<= 64) run lane = node in chunks of 2048 nodes, one
 // workgroup per (chunk, class); more run lane = class (4 per lane) in enough node chunks for
 // ~8 resident waves per SIMD.
@@ -6162,17 +5910,20 @@ DiskPlan diskio_plan(uint32_t n_nodes, uint32_t n_cls) {
   return pl;
 }
 
+// The Mode B launches: ea.elig set takes the ELIG instance over the same plan and grid.
 hipError_t launch_k2b(const NodeRecB* nodes, uint32_t n_nodes, const double* cab,
                       uint32_t n_cls, const DiskLevels& lv, const DiskPlan& pl, uint32_t* plc,
-                      uint32_t* pidx, hipStream_t s) {
+                      uint32_t* pidx, const DiskEligArgs& ea, hipStream_t s) {
   if (pl.C == 0) return hipSuccess;
   if (pl.node_lanes) {
-    hipLaunchKernelGGL(k2b_node_lanes, dim3(pl.C, n_cls), dim3(kBlock), 0, s, nodes, n_nodes,
-                       pl.chunk, cab, n_cls, lv, plc, pidx);
+    const auto k = ea.elig ? k2b_node_lanes<true> : k2b_node_lanes<false>;
+    hipLaunchKernelGGL(k, dim3(pl.C, n_cls), dim3(kBlock), 0, s, nodes, n_nodes, pl.chunk, cab,
+                       n_cls, lv, plc, pidx, ea);
   } else {
     const uint32_t cb = (n_cls + kBlock * kDiskCPL - 1) / (kBlock * kDiskCPL);
-    hipLaunchKernelGGL(k2b_class_lanes<kDiskCPL>, dim3(cb, pl.C), dim3(kBlock), 0, s, nodes,
-                       n_nodes, pl.chunk, cab, n_cls, lv, plc, pidx);
+    const auto k = ea.elig ? k2b_class_lanes<kDiskCPL, true> : k2b_class_lanes<kDiskCPL, false>;
+    hipLaunchKernelGGL(k, dim3(cb, pl.C), dim3(kBlock), 0, s, nodes, n_nodes, pl.chunk, cab,
+                       n_cls, lv, plc, pidx, ea);
   }
   return hipGetLastError();
 }
@@ -6186,7 +5937,18 @@ hipError_t launch_reduce2b(const uint32_t* plc, const uint32_t* pidx, uint32_t C
   return hipGetLastError();
 }
 
-// The eligibility forms (yoda_mode_b_follow): the same plan and grids over the sibling kernels.
+hipError_t launch_k2b_rows(const NodeRecB* nodes, uint32_t n_nodes, const PodParams& pp,
+                           uint32_t n_pods, const Partials& part, int64_t* rows,
+                           const DiskEligArgs& ea, hipStream_t s) {
+  if (n_nodes == 0 || n_pods == 0) return hipSuccess;
+  const auto k = ea.elig ? k2b_rows<true> : k2b_rows<false>;
+  hipLaunchKernelGGL(k, dim3((n_nodes + kBlock - 1) / kBlock), dim3(kBlock), 0, s, nodes, n_nodes,
+                     pp.alpha, pp.beta, n_pods, part.best_f, part.idx, part.ties, part.low_f, rows,
+                     ea);
+  return hipGetLastError();
+}
+
+// The eligibility table and its counts (cnt is cleared here).
 hipError_t launch_modeb_elig_build(const uint64_t* words, const uint64_t* pres, uint32_t n_nodes,
                                    DiskElig* elig, uint32_t* cnt, hipStream_t s) {
   hipError_t e = hipMemsetAsync(cnt, 0, kDiskSelCount * 4, s);
@@ -6194,48 +5956,6 @@ hipError_t launch_modeb_elig_build(const uint64_t* words, const uint64_t* pres, 
   const uint32_t blocks = std::min<uint32_t>((n_nodes + kBlock - 1) / kBlock, 128u);
   hipLaunchKernelGGL(k_modeb_elig_build, dim3(blocks), dim3(kBlock), 0, s, words, pres, n_nodes,
                      elig, cnt);
-  return hipGetLastError();
-}
-
-hipError_t launch_k2b_elig(const NodeRecB* nodes, uint32_t n_nodes, const double* cab,
-                           const uint32_t* csel, uint32_t n_cls, const DiskLevels& lv,
-                           const DiskPlan& pl, const DiskElig* elig, uint32_t* plc, uint32_t* pidx,
-                           hipStream_t s) {
-  if (pl.C == 0) return hipSuccess;
-  if (pl.node_lanes) {
-    hipLaunchKernelGGL(k2b_node_lanes_elig, dim3(pl.C, n_cls), dim3(kBlock), 0, s, nodes, n_nodes,
-                       pl.chunk, cab, csel, n_cls, lv, elig, plc, pidx);
-  } else {
-    const uint32_t cb = (n_cls + kBlock * kDiskCPL - 1) / (kBlock * kDiskCPL);
-    hipLaunchKernelGGL(k2b_class_lanes_elig<kDiskCPL>, dim3(cb, pl.C), dim3(kBlock), 0, s, nodes,
-                       n_nodes, pl.chunk, cab, csel, n_cls, lv, elig, plc, pidx);
-  }
-  return hipGetLastError();
-}
-
-hipError_t launch_reduce2b_elig(const uint32_t* plc, const uint32_t* pidx, uint32_t C,
-                                uint32_t n_cls, const uint32_t* cls, uint32_t n_pods,
-                                uint32_t node_offset, int64_t* best, uint32_t* idx, uint32_t* ties,
-                                int64_t* low, hipStream_t s) {
-  hipLaunchKernelGGL(k_reduce2b_elig, pod_grid(n_pods), dim3(kBlock), 0, s, plc, pidx, C, n_cls,
-                     cls, n_pods, node_offset, best, idx, ties, low);
-  return hipGetLastError();
-}
-
-hipError_t launch_fill_diskio_state_elig(uint32_t n_pods, const uint8_t* cls, const uint32_t* cnt,
-                                         uint64_t* maxima, uint32_t* counts, hipStream_t s) {
-  hipLaunchKernelGGL(k_fill_diskio_state_elig, pod_grid(n_pods), dim3(kBlock), 0, s, n_pods, cls,
-                     cnt, maxima, counts);
-  return hipGetLastError();
-}
-
-hipError_t launch_k2b_rows_elig(const NodeRecB* nodes, uint32_t n_nodes, const PodParams& pp,
-                                const uint8_t* cls, const DiskElig* elig, uint32_t n_pods,
-                                const Partials& part, int64_t* rows, hipStream_t s) {
-  if (n_nodes == 0 || n_pods == 0) return hipSuccess;
-  hipLaunchKernelGGL(k2b_rows_elig, dim3((n_nodes + kBlock - 1) / kBlock), dim3(kBlock), 0, s,
-                     nodes, n_nodes, pp.alpha, pp.beta, cls, elig, n_pods, part.best_f, part.idx,
-                     part.ties, part.low_f, rows);
   return hipGetLastError();
 }
 
@@ -6285,9 +6005,9 @@ hipError_t launch_merge_prepare(const int64_t* best_global, const int64_t* best_
 }
 
 hipError_t launch_fill_diskio_state(uint32_t n_pods, uint32_t n_nodes, uint64_t* maxima,
-                                    uint32_t* counts, hipStream_t s) {
+                                    uint32_t* counts, const DiskEligArgs& ea, hipStream_t s) {
   hipLaunchKernelGGL(k_fill_diskio_state, pod_grid(n_pods), dim3(kBlock), 0, s, n_pods, n_nodes,
-                     maxima, counts);
+                     ea.elig ? ea.cnt : nullptr, ea.cls, maxima, counts);
   return hipGetLastError();
 }
 
@@ -6884,14 +6604,16 @@ __global__ __launch_bounds__(kBlock) void k_draw_generic(
   }
 }
 
-// Mode B: every node is feasible; the score of k2_diskio (algorithm.go:109-111, no FMA).
-template <bool SHARD>
+// Mode B: every node is feasible, or with ELIG (a single handle's run with eligibility,
+// yoda_mode_b_follow) only the nodes of the pod's E enter the MIN key; the score of k2b_rows
+// (algorithm.go:109-111, no FMA).  ea.cls: the pods' class bytes in the caller's order.
+template <bool SHARD, bool ELIG>
 __global__ __launch_bounds__(kBlock) void k_draw_diskio(const NodeRecB* __restrict__ nodes,
                                                         uint32_t n_nodes, uint32_t chunk_nodes,
                                                         const double* __restrict__ alpha_in,
                                                         const double* __restrict__ beta_in,
-                                                        DrawArgs a) {
-#pragma clang fp contract(off)
+                                                        DrawArgs a, DiskEligArgs ea) {
+  static_assert(!(SHARD && ELIG), "shard entry points refuse Mode B with eligibility");
   const uint32_t nl = min(*a.n_list, a.n_work);
   const uint32_t n0 = blockIdx.y * chunk_nodes;
   const uint32_t n1 = min(n0 + chunk_nodes, n_nodes);
@@ -6900,61 +6622,21 @@ __global__ __launch_bounds__(kBlock) void k_draw_diskio(const NodeRecB* __restri
     const uint32_t o = a.perm ? a.perm[p] : p;
     const double best = (double)a.best[o];
     const double alpha = alpha_in[p], beta = beta_in[p];
+    uint32_t sel = kDiskSelAny;
+    if constexpr (ELIG) sel = ea.cls ? disk_sel(ea.cls[o]) : kDiskSelAny;
     const uint64_t st = tie_pod_state(a.seed, a.pod_base + o);
     uint64_t key = ~0ull;
     for (uint32_t n = n0 + threadIdx.x; n < n1; n += kBlock) {
+      if constexpr (ELIG) {
+        if (!disk_eligible(ea.elig[n], sel)) continue;
+      }
       const NodeRecB r = nodes[n];
-      const double x = alpha * r.v;
-      const double y = beta * r.u;
-      const double l = fabs(x - y);  // :110
-      const double t = 10.0 * l;
-      const double s = 10.0 - t;     // :111
-      const double score = (s >= 1.0) ? __builtin_trunc(s) : 0.0;
-      if (score == best) {
+      if (disk_score(disk_absdiff(alpha, r.v, beta, r.u)) == best) {
         const uint64_t k = tie_key(st, a.node_offset + n);
         key = k < key ? k : key;
       }
     }
     draw_fold(a.keys, SHARD ? o : i, key);
-  }
-}
-
-// k_draw_diskio of a single handle with eligibility (yoda_mode_b_follow): only the nodes of the
-// pod's E enter the MIN key.  cls: the pods' class bytes (caller order), nullptr: every pod ANY.
-__global__ __launch_bounds__(kBlock) void k_draw_diskio_elig(const NodeRecB* __restrict__ nodes,
-                                                             uint32_t n_nodes, uint32_t chunk_nodes,
-                                                             const double* __restrict__ alpha_in,
-                                                             const double* __restrict__ beta_in,
-                                                             const uint8_t* __restrict__ cls,
-                                                             const DiskElig* __restrict__ elig,
-                                                             DrawArgs a) {
-#pragma clang fp contract(off)
-  const uint32_t nl = min(*a.n_list, a.n_work);
-  const uint32_t n0 = blockIdx.y * chunk_nodes;
-  const uint32_t n1 = min(n0 + chunk_nodes, n_nodes);
-  for (uint32_t i = blockIdx.x; i < nl; i += gridDim.x) {
-    const uint32_t p = a.list[i];
-    const uint32_t o = a.perm ? a.perm[p] : p;
-    const double best = (double)a.best[o];
-    const double alpha = alpha_in[p], beta = beta_in[p];
-    const uint32_t sel = cls ? disk_sel(cls[o]) : kDiskSelAny;
-    const uint64_t st = tie_pod_state(a.seed, a.pod_base + o);
-    uint64_t key = ~0ull;
-    for (uint32_t n = n0 + threadIdx.x; n < n1; n += kBlock) {
-      if (!disk_eligible(elig[n], sel)) continue;
-      const NodeRecB r = nodes[n];
-      const double x = alpha * r.v;
-      const double y = beta * r.u;
-      const double l = fabs(x - y);  // :110
-      const double t = 10.0 * l;
-      const double s = 10.0 - t;     // :111
-      const double score = (s >= 1.0) ? __builtin_trunc(s) : 0.0;
-      if (score == best) {
-        const uint64_t k = tie_key(st, a.node_offset + n);
-        key = k < key ? k : key;
-      }
-    }
-    draw_fold(a.keys, i, key);
   }
 }
 
@@ -6979,12 +6661,17 @@ template <bool SHARD>
 static hipError_t launch_draw_keys(int K, Path path, int mode_diskio, const unsigned char* nodes,
                              const NodeRecB* nodes_b, uint32_t n_nodes, const PodParams& pp,
                              const double* rcp, const uint64_t* maxima, const int64_t* low,
-                             const MaskSrc& ms, const DrawArgs& a, hipStream_t s) {
+                             const MaskSrc& ms, const DrawArgs& a, const DiskEligArgs& ea,
+                             hipStream_t s) {
   const uint32_t gx = std::min(a.n_work, kDrawMaxStrides);
   const uint32_t C = (n_nodes + kDrawChunk - 1) / kDrawChunk;
   if (mode_diskio) {
-    hipLaunchKernelGGL(k_draw_diskio<SHARD>, dim3(gx, C), dim3(kBlock), 0, s, nodes_b, n_nodes,
-                       kDrawChunk, pp.alpha, pp.beta, a);
+    auto k = k_draw_diskio<SHARD, false>;
+    if constexpr (!SHARD) {  // (a sharded step refuses Mode B with eligibility: its ea is empty)
+      if (ea.elig) k = k_draw_diskio<false, true>;
+    }
+    hipLaunchKernelGGL(k, dim3(gx, C), dim3(kBlock), 0, s, nodes_b, n_nodes, kDrawChunk, pp.alpha,
+                       pp.beta, a, ea);
   } else if (path == Path::U64) {
     YODA_K_SWITCH(K, hipLaunchKernelGGL((k_draw_generic<KK, SHARD>), dim3(gx), dim3(kBlock), 0, s,
                                         nodes, n_nodes, pp.m_u, pp.c_u, maxima, low, ms, a));
@@ -7009,7 +6696,7 @@ hipError_t launch_draw(int K, Path path, int mode_diskio, const unsigned char* n
                        const double* rcp, const uint64_t* maxima, const int64_t* low,
                        const uint64_t* bm, uint32_t bm_stride, const BlockMask* bs,
                        uint32_t bs_stride, const uint64_t* blk, uint32_t blk_stride,
-                       const DrawArgs& a, hipStream_t s) {
+                       const DrawArgs& a, const DiskEligArgs& ea, hipStream_t s) {
   if (a.n_work == 0 || n_nodes == 0) return hipSuccess;
   if (bs && !blk) return hipErrorInvalidValue;  // sparse masks are read through their block list
   hipError_t e = hipMemsetAsync(a.n_list, 0, 4, s);
@@ -7017,25 +6704,8 @@ hipError_t launch_draw(int K, Path path, int mode_diskio, const unsigned char* n
   hipLaunchKernelGGL(k_draw_list, pod_grid(a.n_work), dim3(kBlock), 0, s, a);
   const MaskSrc ms{bm, bs, bm_stride, bs_stride, blk, blk_stride};
   e = launch_draw_keys<false>(K, path, mode_diskio, nodes, nodes_b, n_nodes, pp, rcp, maxima, low,
-                              ms, a, s);
+                              ms, a, ea, s);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_draw_write, pod_grid(a.n_work), dim3(kBlock), 0, s, a);
-  return hipGetLastError();
-}
-
-// launch_draw for a Mode B run with eligibility: the same list and write passes around
-// k_draw_diskio_elig.
-hipError_t launch_draw_diskio_elig(const NodeRecB* nodes_b, uint32_t n_nodes, const PodParams& pp,
-                                   const uint8_t* cls, const DiskElig* elig, const DrawArgs& a,
-                                   hipStream_t s) {
-  if (a.n_work == 0 || n_nodes == 0) return hipSuccess;
-  hipError_t e = hipMemsetAsync(a.n_list, 0, 4, s);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_draw_list, pod_grid(a.n_work), dim3(kBlock), 0, s, a);
-  const uint32_t gx = std::min(a.n_work, kDrawMaxStrides);
-  const uint32_t C = (n_nodes + kDrawChunk - 1) / kDrawChunk;
-  hipLaunchKernelGGL(k_draw_diskio_elig, dim3(gx, C), dim3(kBlock), 0, s, nodes_b, n_nodes,
-                     kDrawChunk, pp.alpha, pp.beta, cls, elig, a);
   hipLaunchKernelGGL(k_draw_write, pod_grid(a.n_work), dim3(kBlock), 0, s, a);
   return hipGetLastError();
 }
@@ -7082,7 +6752,7 @@ hipError_t launch_shard_draw_keys(int K, Path path, int mode_diskio, const unsig
   if (n_nodes == 0) return hipGetLastError();  // a shard without nodes: every key stays ~0
   const MaskSrc ms{bm, bs, bm_stride, bs_stride, blk, blk_stride};
   e = launch_draw_keys<true>(K, path, mode_diskio, nodes, nodes_b, n_nodes, pp, rcp, maxima, low,
-                             ms, a, s);
+                             ms, a, DiskEligArgs{}, s);
   if (e != hipSuccess) return e;
   return hipGetLastError();
 }

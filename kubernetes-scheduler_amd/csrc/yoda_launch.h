@@ -47,42 +47,27 @@ hipError_t launch_k2(int K, Path path, const unsigned char* nodes, const unsigne
                      const uint64_t* bm, uint32_t bm_stride, const BlockMask* bs,
                      uint32_t bs_stride, const Partials& part, int64_t* rows,
                      unsigned long long* stats, const uint32_t* counts, hipStream_t s);
+// Mode B (yoda_modeb.h).  ea: the run's eligibility (yoda_mode_b_follow) -- the table, the pod
+// classes' selectors, the pods' class bytes and the counts; an empty one (elig == nullptr) is an
+// unrestricted run and takes the kernels' ELIG = false instances.  launch_draw takes it too.
+struct DiskElig;
+struct DiskEligArgs;
+// The table build: elig [n_nodes], cnt [kDiskSelCount], from the candidate words (nullptr: off)
+// and the presence bitmap.
+hipError_t launch_modeb_elig_build(const uint64_t* words, const uint64_t* pres, uint32_t n_nodes,
+                                   DiskElig* elig, uint32_t* cnt, hipStream_t s);
 hipError_t launch_k2b_rows(const NodeRecB* nodes, uint32_t n_nodes, const PodParams& pp,
-                           uint32_t n_pods, const Partials& part, int64_t* rows, hipStream_t s);
-hipError_t launch_k2_diskio(const NodeRecB* nodes, uint32_t n_nodes, uint32_t chunk_nodes,
-                            uint32_t C, const PodParams& pp, uint32_t n_pods, const Partials& part,
-                            int64_t* rows, hipStream_t s);
+                           uint32_t n_pods, const Partials& part, int64_t* rows,
+                           const DiskEligArgs& ea, hipStream_t s);
 DiskPlan diskio_plan(uint32_t n_nodes, uint32_t n_cls);
 hipError_t launch_k2b(const NodeRecB* nodes, uint32_t n_nodes, const double* cab,
                       uint32_t n_cls, const DiskLevels& lv, const DiskPlan& pl, uint32_t* plc,
-                      uint32_t* pidx, hipStream_t s);
+                      uint32_t* pidx, const DiskEligArgs& ea, hipStream_t s);
+// (one kernel for both: it skips the empty partials that only a run with eligibility writes)
 hipError_t launch_reduce2b(const uint32_t* plc, const uint32_t* pidx, uint32_t C, uint32_t n_cls,
                            const uint32_t* cls, uint32_t n_pods, uint32_t node_offset,
                            int64_t* best, uint32_t* idx, uint32_t* ties, int64_t* low,
                            hipStream_t s);
-// Mode B with eligibility (yoda_mode_b_follow; yoda_modeb.h): the table build (elig [n_nodes],
-// cnt [kDiskSelCount], from the candidate words -- nullptr: off -- and the presence bitmap), and
-// the siblings of the five launches above and of launch_draw.  csel: [n_cls] selectors; cls: the
-// pods' class bytes (nullptr: every pod YODA_CAND_ANY).
-struct DiskElig;
-hipError_t launch_modeb_elig_build(const uint64_t* words, const uint64_t* pres, uint32_t n_nodes,
-                                   DiskElig* elig, uint32_t* cnt, hipStream_t s);
-hipError_t launch_k2b_elig(const NodeRecB* nodes, uint32_t n_nodes, const double* cab,
-                           const uint32_t* csel, uint32_t n_cls, const DiskLevels& lv,
-                           const DiskPlan& pl, const DiskElig* elig, uint32_t* plc, uint32_t* pidx,
-                           hipStream_t s);
-hipError_t launch_reduce2b_elig(const uint32_t* plc, const uint32_t* pidx, uint32_t C,
-                                uint32_t n_cls, const uint32_t* cls, uint32_t n_pods,
-                                uint32_t node_offset, int64_t* best, uint32_t* idx, uint32_t* ties,
-                                int64_t* low, hipStream_t s);
-hipError_t launch_fill_diskio_state_elig(uint32_t n_pods, const uint8_t* cls, const uint32_t* cnt,
-                                         uint64_t* maxima, uint32_t* counts, hipStream_t s);
-hipError_t launch_k2b_rows_elig(const NodeRecB* nodes, uint32_t n_nodes, const PodParams& pp,
-                                const uint8_t* cls, const DiskElig* elig, uint32_t n_pods,
-                                const Partials& part, int64_t* rows, hipStream_t s);
-hipError_t launch_draw_diskio_elig(const NodeRecB* nodes_b, uint32_t n_nodes, const PodParams& pp,
-                                   const uint8_t* cls, const DiskElig* elig, const DrawArgs& a,
-                                   hipStream_t s);
 hipError_t launch_rows_transpose(const int64_t* in, uint32_t n_nodes, uint32_t n_pods,
                                  const uint32_t* perm,
                                  int64_t* out, hipStream_t s);
@@ -92,7 +77,7 @@ hipError_t launch_reduce2(const Partials& part, uint32_t C, uint32_t n_pods, boo
 hipError_t launch_merge_prepare(const int64_t* best_global, const int64_t* best_local,
                                 uint32_t n_pods, uint32_t* idx, uint32_t* ties, hipStream_t s);
 hipError_t launch_fill_diskio_state(uint32_t n_pods, uint32_t n_nodes, uint64_t* maxima,
-                                    uint32_t* counts, hipStream_t s);
+                                    uint32_t* counts, const DiskEligArgs& ea, hipStream_t s);
 hipError_t launch_finalize(const uint32_t* counts, const int64_t* best, const uint32_t* idx,
                            const uint32_t* ties_in, const int64_t* lowest, uint32_t n_pods,
                            bool generic, int32_t* pick, int32_t* status, uint32_t* ties_out,
@@ -222,7 +207,7 @@ hipError_t launch_draw(int K, Path path, int mode_diskio, const unsigned char* n
                        const double* rcp, const uint64_t* maxima, const int64_t* low,
                        const uint64_t* bm, uint32_t bm_stride, const BlockMask* bs,
                        uint32_t bs_stride, const uint64_t* blk, uint32_t blk_stride,
-                       const DrawArgs& a, hipStream_t s);
+                       const DrawArgs& a, const DiskEligArgs& ea, hipStream_t s);
 // The sharded draw (yoda_shard_draw_keys / _apply): a.keys is the dense caller-order [n_pods]
 // key buffer; a.best / a.status / a.ties the GLOBAL outcome; a.norm_top the exact merge's.
 hipError_t launch_shard_draw_keys(int K, Path path, int mode_diskio, const unsigned char* nodes,

@@ -11,6 +11,26 @@
 
 namespace yoda {
 
+// The Mode B score (algorithm.go:109-111): |d| = |alpha*V - beta*U|, then uint64(10 - 10*|d|) on
+// amd64 and Uint64ToInt64: trunc for a value >= 1, else 0 (NaN, negatives).  Go on amd64 fuses
+// nothing, so neither function is FMA-contracted, whatever the flags of the file that includes
+// them.  The one definition for the kernels, the host's level table (diskio_levels) and the
+// stand-alone checks.
+__host__ __device__ __forceinline__ double disk_absdiff(double alpha, double v, double beta,
+                                                        double u) {
+#pragma clang fp contract(off)
+  const double a = alpha * v;
+  const double b = beta * u;
+  return __builtin_fabs(a - b);  // :110
+}
+
+__host__ __device__ __forceinline__ double disk_score(double l) {
+#pragma clang fp contract(off)
+  const double t = 10.0 * l;
+  const double s = 10.0 - t;  // :111
+  return (s >= 1.0) ? __builtin_trunc(s) : 0.0;
+}
+
 // A lane keeps, over nodes in increasing order, the best level seen, its node count and its
 // first (lowest) node; level 0 counts nothing while running (every node is >= 0, NaN included)
 // and is settled at the end.
@@ -89,8 +109,18 @@ __host__ __device__ __forceinline__ DiskElig disk_elig_of(bool present, uint64_t
   return DiskElig{present ? word : 0ull, present ? 1ull : 0ull};
 }
 
+// What a run with eligibility hands the Mode B kernels and their launchers, by value; elig ==
+// nullptr (the empty value) is an unrestricted run, whose kernel instances (ELIG = false) read
+// none of it.
+struct DiskEligArgs {
+  const DiskElig* elig;  // [n_nodes] records
+  const uint32_t* csel;  // batch kernels: the [n_cls] selectors of the pod classes
+  const uint8_t* cls;    // rows, draw, n_feasible: the pods' class bytes (nullptr: every pod ANY)
+  const uint32_t* cnt;   // [kDiskSelCount] nodes of each class, present nodes
+};
+
 // The eligible nodes a lane has stepped over and the first of them: what level 0 settles from
-// (the unrestricted kernels settle it from the chunk's bounds, which count every node).
+// (the unrestricted instances settle it from the chunk's bounds, which count every node).
 struct DiskSeen {
   uint32_t n, first;
 };
@@ -162,15 +192,17 @@ __host__ __device__ __forceinline__ void disk_merge_any(DiskBest& b, uint32_t le
 }
 
 // Chunk partials in node order: the first chunk reaching the best level holds the lowest node.
+// idx points at the partial's node, which is read only when the partial takes the lead (a
+// kernel's merge loop then loads one word per chunk, not two).
 __host__ __device__ __forceinline__ void disk_merge_chunk(DiskBest& b, uint32_t word,
-                                                          uint32_t idx) {
+                                                          const uint32_t* idx) {
   const uint32_t cnt = word & ((1u << kDiskCountBits) - 1u);
   if (cnt == 0u) return;
   const int64_t L = (int64_t)(word >> kDiskCountBits);
   if (L > b.lev) {
     b.lev = L;
     b.cnt = cnt;
-    b.idx = idx;
+    b.idx = *idx;
   } else if (L == b.lev) {
     b.cnt += cnt;
   }

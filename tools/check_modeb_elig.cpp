@@ -1,6 +1,7 @@
 // check_modeb_elig: the Mode B batch path's accumulator, settle and merges with eligibility
-// (yoda_modeb.h, as the k2b_*_elig kernels and k_reduce2b_elig use them) against a brute-force
-// loop over E, for both launch forms' merge orders, and the pod-class builder.
+// (yoda_modeb.h, as the k2b_*<ELIG = true> kernels and k_reduce2b use them) against a brute-force
+// loop over E, for both launch forms' merge orders, the pod-class builder, and the shared score
+// (disk_score, disk_absdiff) against the level table of the earlier host-only form.
 //
 //   c++ -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -I<hip include dir>
 //       -D__HIP_PLATFORM_AMD__ -o check_modeb_elig tools/check_modeb_elig.cpp && ./check_modeb_elig
@@ -34,7 +35,8 @@ uint64_t rnd() {  // splitmix64
 }
 double unit() { return (double)(rnd() >> 11) / 9007199254740992.0; }
 
-// trunc(10 - 10 |d|) when >= 1, else 0 (algorithm.go:110-111, then Uint64ToInt64); no FMA
+// trunc(10 - 10 |d|) when >= 1, else 0 (algorithm.go:110-111, then Uint64ToInt64); no FMA: the
+// volatile form libyoda's level table was built with before disk_score, kept as the yardstick
 double score_of(double l) {
   volatile double t = 10.0 * l;
   volatile double s = 10.0 - t;
@@ -42,7 +44,7 @@ double score_of(double l) {
 }
 
 // t[k]: the largest |d| whose score is >= k, by bisection over the double bit patterns
-DiskLevels levels() {
+DiskLevels levels(double (*score)(double) = score_of) {
   DiskLevels d{};
   d.t[0] = HUGE_VAL;
   d.t[11] = -1.0;
@@ -52,7 +54,7 @@ DiskLevels levels() {
       const uint64_t mid = lo + (hi - lo) / 2;
       double x;
       std::memcpy(&x, &mid, 8);
-      if (score_of(x) >= (double)k) lo = mid; else hi = mid;
+      if (score(x) >= (double)k) lo = mid; else hi = mid;
     }
     std::memcpy(&d.t[k], &lo, 8);
   }
@@ -112,7 +114,7 @@ int trial(const DiskLevels& lv, uint32_t n_nodes, uint32_t chunk, uint32_t n_cls
       for (uint32_t c = 0; c < n_cls; ++c) {
         uint32_t word, idx;
         if (form == 0) {  // one lane walks the chunk in node order, branch-free; level 0 walks
-          DiskAcc s;      // the words again (k2b_class_lanes_elig)
+          DiskAcc s;      // the words again (k2b_class_lanes<.., true>)
           DiskSeen sn;
           const DiskSelMask sm = disk_sel_mask(sel[c]);
           disk_init(s, lv.t);
@@ -163,7 +165,7 @@ int trial(const DiskLevels& lv, uint32_t n_nodes, uint32_t chunk, uint32_t n_cls
       }
       DiskBest g;
       disk_best_init(g);
-      for (uint32_t k = 0; k < C; ++k) disk_merge_chunk(g, plc[(size_t)k * n_cls + c], pix[(size_t)k * n_cls + c]);
+      for (uint32_t k = 0; k < C; ++k) disk_merge_chunk(g, plc[(size_t)k * n_cls + c], &pix[(size_t)k * n_cls + c]);
       if (g.lev != w.lev || g.cnt != w.cnt || g.idx != w.idx)
         return fail(form ? "lane = node" : "lane = class", n_nodes, chunk, c, w, g);
       ++checked;
@@ -209,6 +211,22 @@ int classes_trial(uint32_t n_pods, bool bytes) {
 
 int main() {
   const DiskLevels lv = levels();
+  // the shared score (yoda_modeb.h disk_score, disk_absdiff; contraction off by their own pragma,
+  // so this holds under -ffp-contract=fast too) gives the level table bit for bit, and the
+  // volatile forms' values on random pairs
+  {
+    const DiskLevels shared = levels([](double l) { return disk_score(l); });
+    if (std::memcmp(shared.t, lv.t, sizeof lv.t) != 0)
+      return std::printf("check_modeb_elig: disk_score moves the level table\n"), 1;
+    for (int i = 0; i < 200000; ++i) {
+      const NodeRecB r{unit() * 3.0, unit() * 3.0};
+      const double al = unit() * 2.0, be = unit() * 2.0;
+      const double want = abs_d(al, be, r), got = disk_absdiff(al, r.v, be, r.u);
+      if (std::memcmp(&want, &got, 8) != 0 || score_of(want) != disk_score(got))
+        return std::printf("check_modeb_elig: disk_absdiff / disk_score differ at %d\n", i), 1;
+    }
+    for (int k = 0; k < 12; ++k) std::printf("t[%2d] = %a\n", k, lv.t[k]);
+  }
   // the selector's bit: class 63 is bit 63 of lo, ANY is presence alone
   {
     const DiskElig e = disk_elig_of(true, 1ull << 63), a = disk_elig_of(false, ~0ull);
