@@ -705,6 +705,88 @@ int yoda_mode_b_follow(yoda_t* h, int enable);
  * 1 if that run took the eligibility kernels (0: the unchanged ones), eligibility-table builds
  * since the upload}. */
 int yoda_mode_b_info(const yoda_t* h, uint32_t* out);
+/* ---- Filter diagnosis: why a node was rejected ----
+ * kube-scheduler builds a Pending pod's FitError event ("0/N nodes are available: a ..., b ...")
+ * and its PostFilter walk from the per-node Filter statuses.  The reference's Filter is three
+ * predicates with three meanings (pkg/yoda/filter/filter.go:11-58), called in the order of
+ * pkg/yoda/collection/collection.go:41-44; the batch path evaluates all three and, without
+ * these calls, hands back n_feasible alone.  One reason per (pod, node):
+ *   YODA_REASON_NONE           the node is in F'(p) (the candidate-class block above): it passes
+ *   YODA_REASON_NUMBER         PodFitsNumber fails (filter.go:11-16): not enough cards
+ *   YODA_REASON_MEMORY         number passes, PodFitsMemory fails (filter.go:18-33): too few
+ *                              healthy cards with that much free memory
+ *   YODA_REASON_CLOCK          number and memory pass, PodFitsClock fails (filter.go:35-50): too
+ *                              few healthy cards at that clock
+ *   YODA_REASON_NOT_CANDIDATE  another plugin's Filter rejected it: the pod's class bit is clear
+ *                              in the node's word (yoda_set_candidates)
+ *   YODA_REASON_ABSENT         the node is not in the node set (yoda_set_node_present)
+ * Precedence: absent > not a candidate > number > memory > clock.  Not-a-candidate goes before
+ * Yoda's own reasons because the in-tree Filter plugins run before an out-of-tree one in a
+ * profile: such a node never reaches Yoda's Filter, and the caller gets Yoda's reasons over
+ * exactly the candidate nodes (it knows its own per-class rejection counts).  A YODA_CAND_ANY
+ * pod, or candidates off, never gives YODA_REASON_NOT_CANDIDATE.  YODA_REASON_NONE holds exactly
+ * where the feasibility bit of yoda_download_bitmask / yoda_score_rows is set.
+ *   Mode A only.  Mode B has no Filter of its own (scheduler.go:96-99): its rejected nodes are
+ * n_nodes - absent - n_feasible, and the calls below refuse it.
+ *
+ * The batch path: counts per pod.  yoda_diagnose runs after a completed Mode A run whose results
+ * are still pending -- exactly when yoda_download would answer: after yoda_run, yoda_eval,
+ * yoda_score_rows[_norm], and on a shard handle after a step through yoda_shard_finalize or
+ * yoda_comm_run[_local] with no exact-normalize pods pending.  Asynchronous on the handle's
+ * stream; it does not disturb the run (yoda_download before and after it gives the same bytes),
+ * and calling it twice gives the same counts.  It evaluates the state the run evaluated: the live
+ * records (yoda_set_node_state, yoda_update_node_cards), the presence bits, the candidate words
+ * and the class array.  yoda_set_node_state and yoda_update_alloc never invalidated a pending
+ * run: a diagnosis after them reads the pushed CardNumber, while the selection and n_feasible
+ * stay the run's.  It selects the pods whose final n_feasible is 0 -- on a shard the global
+ * count after the exchange -- or with YODA_DIAG_ALL every pod; the selection is made on the
+ * device, with no host round trip between run and diagnosis.
+ *   yoda_download_diagnosis: counts[4 * p ..] = {not a candidate, number, memory, clock} nodes of
+ * pod p, in the caller's pod order whatever yoda_set_pod_order says; a pod that was not selected
+ * has all four words 0xFFFFFFFF.  Absent nodes are counted nowhere, so for a selected pod the
+ * four counts + n_feasible = n_nodes - absent -- unless yoda_set_node_state or yoda_update_alloc
+ * came between the run and the diagnosis (above): the counts then follow the pushed CardNumber
+ * and n_feasible does not.  The counts are over the handle's own nodes: on a shard handle this
+ * shard's, and the caller sums the shards' downloads.
+ *   YODA_ERR_INVALID_ARG: a NULL handle or buffer, unknown flag bits, n_counts != 4 * n_pods.
+ * YODA_ERR_STATE, with nothing launched: no pending run; the last run was Mode B or yoda_greedy*;
+ * any call since the run that invalidates pending run state (whatever invalidates yoda_download:
+ * an upload of nodes or pods, yoda_update_node_cards, yoda_set_node_present, the candidate calls,
+ * yoda_reason_rows, the start of a sharded step); yoda_download_diagnosis without this run's
+ * yoda_diagnose before it.
+ *
+ * The row path: a reason per node.  yoda_reason_rows serves the uploaded pods (a handful, as
+ * yoda_score_rows: P * N <= 2^31), synchronously, into host memory: reasons[p * N + n] is the
+ * code of (pod p, local node n), 0 exactly where bit (p, n) of yoda_score_rows' bitmask is set.
+ * Mode A semantics; it honours the candidates, the class array (the length rule and
+ * YODA_ERR_STATE of yoda_run) and the absent nodes, needs no previous run, and invalidates what
+ * yoda_score_rows invalidates (a pending run, phase-1, top-k and draw state): call it before
+ * yoda_score_rows when the picks of the latter are wanted.  YODA_ERR_NO_NODES / YODA_ERR_NO_PODS
+ * before the uploads, YODA_ERR_INVALID_ARG for a NULL buffer or n_reasons != P * N.
+ *
+ * Cost: nothing on any other entry point (one sibling kernel family, k1_diagnose; the K1 / K2
+ * kernels are unchanged).  The sweep reads every node record once per selected pod wave through
+ * the scalar path, as the per-node K1 sweep does, without the maxima fold; its (pod wave, node
+ * chunk) tasks are sized on the device from the selection, so a few unschedulable pods still
+ * fill the GPU.  Measured at 100k pods x 100k nodes, config 3 (profiles/diagnosis/timing.txt,
+ * medians over fresh processes, HIP events): yoda_diagnose 0.048 ms with one unschedulable pod,
+ * 3.63 ms with the workload's own 21,440 (the step: 0.385 ms), 16.34 ms with YODA_DIAG_ALL --
+ * against 19.44 ms for the per-node K1 sweep (YODA_UPLOAD_PER_NODE_K1) over the same 10^10 pairs,
+ * which folds the maxima
+ * as well; yoda_reason_rows 0.060 ms for 1 pod and 0.228 ms for 24 (host wall clock) beside 0.244
+ * and 1.063 ms for yoda_score_rows.  Never called: the step 0.3903 against the parent's 0.3896 ms
+ * in interleaved fresh processes, inside the parent's spread (0.3876-0.3912 ms).  Not measured:
+ * shard handles, the F64 / U64 record paths, K other than 8. */
+#define YODA_REASON_NONE 0
+#define YODA_REASON_NUMBER 1
+#define YODA_REASON_MEMORY 2
+#define YODA_REASON_CLOCK 3
+#define YODA_REASON_NOT_CANDIDATE 4
+#define YODA_REASON_ABSENT 5
+#define YODA_DIAG_ALL 1u /* every pod, not only those with n_feasible == 0 */
+int yoda_diagnose(yoda_t* h, uint32_t flags);
+int yoda_download_diagnosis(yoda_t* h, uint32_t* counts /* [P][4] */, uint64_t n_counts);
+int yoda_reason_rows(yoda_t* h, uint8_t* reasons /* [P][N] */, uint64_t n_reasons);
 /* Diagnostic (synchronizes).  digest[8]: a 64-bit hash per table over its words as the device
  * holds them -- records, K1 summaries, K2 summaries, per-card model rows, K1 mixed tiles, block
  * summaries, G table, G maxima + reciprocals (0 where the record path has none).  mismatch[4]:

@@ -281,6 +281,13 @@ struct yoda_handle {
   // hash of the caller's class bytes (yoda_set_pod_classes), for the shards' agreement digest
   bool shard_cand = false;
   uint64_t cls_hash = 0;
+  // yoda_diagnose: the selected pods (caller ids) and their number, the counts [P][4];
+  // diag_done: they are the pending run's (cleared wherever a run completes; a run that is no
+  // longer pending -- ran == false -- has no diagnosis either).  diag_rows: yoda_reason_rows'
+  // padded rows on the device and their pinned copy
+  bool diag_done = false;
+  DevBuf diag_list, diag_n, diag_counts, diag_rows;
+  PinnedBuf diag_stage;
   // yoda_update_node_cards / yoda_snapshot_check: the changed nodes' packed rows (host), the
   // block summaries k_bsum_build writes for the self-check
   std::vector<uint32_t> cu_rows;
@@ -2973,6 +2980,7 @@ static int run_private(yoda_t* h, int mode, uint32_t flags, bool draw) {
     if (defer && (rc = pods_complete(h))) return rc;
     if (draw && h->tie_draw && (rc = draw_pass(h, mode))) return rc;
     h->ran = true;
+    h->diag_done = false;
     h->ran_bitmask = mode == YODA_MODE_SCV && (flags & YODA_RUN_BITMASK);
     h->last_mode = mode;
     return YODA_OK;
@@ -3106,6 +3114,7 @@ int yoda_score_rows_norm(yoda_t* h, int mode, uint32_t* bitmask_out, uint64_t n_
                        false)))
       return rc;
     h->ran = true;
+    h->diag_done = false;
     h->ran_bitmask = mode == YODA_MODE_SCV;
     h->last_mode = mode;
     if (rows && scores_out) {
@@ -3144,6 +3153,129 @@ int yoda_score_rows_norm(yoda_t* h, int mode, uint32_t* bitmask_out, uint64_t n_
         return rc;
       }
     }
+    return YODA_OK;
+  } catch (...) {
+    return fail(h, YODA_ERR_INVALID_ARG, "unexpected exception");
+  }
+}
+
+// ---- Filter diagnosis ----------------------------------------------------------------------
+static_assert(YODA_REASON_NONE == kReasonNone && YODA_REASON_NUMBER == kReasonNumber &&
+                  YODA_REASON_MEMORY == kReasonMemory && YODA_REASON_CLOCK == kReasonClock &&
+                  YODA_REASON_NOT_CANDIDATE == kReasonNotCandidate &&
+                  YODA_REASON_ABSENT == kReasonAbsent,
+              "the kernels' reason codes are the header's");
+
+// The sweep's inputs: the pod arrays of the upload (caller order; the record path's thresholds,
+// those K1 reads through the run's order), the base records, the candidate state.
+static DiagArgs diag_args(yoda_t* h) {
+  DiagArgs a{};
+  const unsigned char* b = h->pod_blob.as<unsigned char>();
+  const size_t* off = h->pod_off;
+  a.nodes = h->nodes.as<unsigned char>();
+  a.n_nodes = h->n_nodes;
+  a.n_pods = h->n_pods;
+  switch (h->path) {
+    case Path::N32: a.m = b + off[kPodM32]; a.c = b + off[kPodC32]; break;
+    case Path::F64: a.m = b + off[kPodMF]; a.c = b + off[kPodCF]; break;
+    case Path::U64: a.m = b + off[kPodMU]; a.c = b + off[kPodCU]; break;
+  }
+  a.number = reinterpret_cast<const uint64_t*>(b + off[kPodNumber]);
+  a.need_mem = reinterpret_cast<const uint32_t*>(b + off[kPodNeedMem]);
+  a.need_clk = reinterpret_cast<const uint32_t*>(b + off[kPodNeedClk]);
+  if (h->cand_classes) {
+    a.cand_w = h->cand_w.as<uint64_t>();
+    a.cls = h->h_cls.empty() ? nullptr : h->cand_cls.as<uint8_t>() + h->cls_off;
+  }
+  return a;
+}
+
+int yoda_diagnose(yoda_t* h, uint32_t flags) {
+  if (!h) return YODA_ERR_INVALID_ARG;
+  if (flags & ~YODA_DIAG_ALL) return fail(h, YODA_ERR_INVALID_ARG, "yoda_diagnose: unknown flag bits");
+  if (!h->ran || !h->has_nodes || !h->has_pods)
+    return fail(h, YODA_ERR_STATE, "yoda_diagnose: no completed run is pending");
+  if (h->k3_pending)
+    return fail(h, YODA_ERR_STATE,
+                "exact normalize pending: run yoda_shard_exact_records / yoda_shard_exact_merge");
+  if (h->last_mode != YODA_MODE_SCV)
+    return fail(h, YODA_ERR_STATE, "yoda_diagnose: Mode B has no Filter (the rejected nodes are "
+                                   "n_nodes - absent - n_feasible)");
+  try {
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = pods_complete(h);  // (the f64 / u64 thresholds of a deferred upload)
+    if (rc) return rc;
+    const uint32_t P = h->n_pods;
+    h->diag_done = false;
+    if (P == 0) {
+      h->diag_done = true;
+      return YODA_OK;
+    }
+    HIP_TRY(h, h->diag_list.ensure((size_t)P * 4));
+    HIP_TRY(h, h->diag_n.ensure(16));
+    HIP_TRY(h, h->diag_counts.ensure((size_t)P * 16));
+    HIP_TRY(h, hipMemsetAsync(h->diag_n.p, 0, 16, h->stream));
+    HIP_TRY(h, launch_diag_select(h->counts.as<uint32_t>(), P, (flags & YODA_DIAG_ALL) != 0,
+                                  h->diag_list.as<uint32_t>(), h->diag_n.as<uint32_t>(),
+                                  h->diag_counts.as<uint32_t>(), h->stream));
+    DiagArgs a = diag_args(h);
+    a.list = h->diag_list.as<uint32_t>();
+    a.n_list = h->diag_n.as<uint32_t>();
+    a.counts = h->diag_counts.as<uint32_t>();
+    HIP_TRY(h, launch_diagnose(h->K, h->path, false, a, h->stream));
+    h->diag_done = true;
+    return YODA_OK;
+  } catch (...) {
+    return fail(h, YODA_ERR_INVALID_ARG, "unexpected exception");
+  }
+}
+
+int yoda_download_diagnosis(yoda_t* h, uint32_t* counts, uint64_t n_counts) {
+  if (!h) return YODA_ERR_INVALID_ARG;
+  if (!counts) return fail(h, YODA_ERR_INVALID_ARG, "NULL counts buffer");
+  if (!h->ran || !h->diag_done || h->k3_pending || h->last_mode != YODA_MODE_SCV)
+    return fail(h, YODA_ERR_STATE, "yoda_download_diagnosis before this run's yoda_diagnose");
+  if (n_counts != 4ull * h->n_pods)
+    return fail(h, YODA_ERR_INVALID_ARG, "yoda_download_diagnosis: n_counts is not 4 * n_pods");
+  if (h->n_pods == 0) return YODA_OK;
+  HIP_TRY(h, hipSetDevice(h->device));
+  HIP_TRY(h, hipMemcpyAsync(counts, h->diag_counts.p, (size_t)h->n_pods * 16,
+                            hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return YODA_OK;
+}
+
+int yoda_reason_rows(yoda_t* h, uint8_t* reasons, uint64_t n_reasons) {
+  int rc = check_ready(h, YODA_MODE_SCV, true);
+  if (rc) return rc;
+  if (!reasons) return fail(h, YODA_ERR_INVALID_ARG, "NULL reasons buffer");
+  const uint32_t P = h->n_pods, N = h->n_nodes;
+  if (n_reasons != (uint64_t)P * N)
+    return fail(h, YODA_ERR_INVALID_ARG, "yoda_reason_rows: n_reasons is not n_pods * n_nodes");
+  if ((uint64_t)N * P > (1ull << 31))
+    return fail(h, YODA_ERR_RANGE, "yoda_reason_rows is for small pod batches (P*N <= 2^31)");
+  // what yoda_score_rows invalidates: the pending run, phase-1, top-k and draw state
+  h->ran = false;
+  h->ran_bitmask = false;
+  h->diag_done = false;
+  h->phase1_done = false;
+  h->k3_pending = false;
+  h->topk_ready = false;
+  h->draw_stage = 0;
+  if ((uint64_t)N * P == 0) return YODA_OK;
+  try {
+    const size_t stride = ((size_t)N + 63) / 64 * 64;
+    HIP_TRY(h, h->diag_rows.ensure(stride * P));
+    HIP_TRY(h, h->diag_stage.ensure(stride * P));
+    DiagArgs a = diag_args(h);
+    a.rows = h->diag_rows.as<unsigned char>();
+    a.row_stride = (uint32_t)stride;
+    HIP_TRY(h, launch_diagnose(h->K, h->path, true, a, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->diag_stage.p, h->diag_rows.p, stride * P, hipMemcpyDeviceToHost,
+                              h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    const unsigned char* st = static_cast<const unsigned char*>(h->diag_stage.p);
+    for (uint32_t p = 0; p < P; ++p) std::memcpy(reasons + (size_t)p * N, st + p * stride, N);
     return YODA_OK;
   } catch (...) {
     return fail(h, YODA_ERR_INVALID_ARG, "unexpected exception");
@@ -3383,6 +3515,7 @@ int yoda_shard_finalize(yoda_t* h, int mode, const uint32_t* d_counts, const int
         return rc;
     }
     h->ran = true;
+    h->diag_done = false;
     h->ran_bitmask = false;
     h->last_mode = mode;
     h->draw_stage = 1;
@@ -5432,7 +5565,7 @@ static int comm_step(yoda_t* const* hs, int n, int world, int mode, bool local, 
                               h->stream));
   }
   if (P == 0) {
-    for (int i = 0; i < n; ++i) hs[i]->ran = true;
+    for (int i = 0; i < n; ++i) hs[i]->ran = true, hs[i]->diag_done = false;
     return YODA_OK;
   }
   // the caller-order views of the exchanged buffers (the handle's own ones on the U64 path)
@@ -5583,6 +5716,7 @@ static int comm_step(yoda_t* const* hs, int n, int world, int mode, bool local, 
                   h->idx.as<uint32_t>(), h->ties.as<uint32_t>(), h->lowest.as<int64_t>(), true);
     if (rc) return rc;
     h->ran = true;
+    h->diag_done = false;
     h->ran_bitmask = false;
     h->last_mode = mode;
     h->draw_stage = 1;

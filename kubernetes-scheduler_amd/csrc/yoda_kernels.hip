@@ -192,6 +192,43 @@ __device__ __forceinline__ bool k1_node(const unsigned char* rec, typename Rec<P
   return feas;
 }
 
+// k1_node's sibling for the diagnosis (yoda_diagnose, yoda_reason_rows): the same record, the
+// same loads and the same card counts, but instead of folding the node it names the FIRST
+// predicate that rejects it, in the call order of collection.go:41-44 -- PodFitsNumber
+// (filter.go:11-16), PodFitsMemory (:18-33), PodFitsClock (:35-50) -- or kReasonAbsent for a node
+// outside the node set.  kReasonNone exactly where k1_node returns true.  The candidate test is
+// the caller's (it needs the node's word, not its record).
+template <int K, Path PATH>
+__device__ __forceinline__ uint32_t k1_reasons(const unsigned char* rec, typename Rec<PATH>::T m,
+                                               typename Rec<PATH>::T c, uint64_t number,
+                                               uint32_t need_mem, uint32_t need_clk) {
+  using R = Rec<PATH>;
+  using T = typename R::T;
+  const NodeHdrG hd = *reinterpret_cast<const NodeHdrG*>(rec);
+  const Group<T, K> fr = load_group<T, K>(rec + R::off(kFree, K));
+  const Group<T, K> ck = load_group<T, K>(rec + R::off(kClock, K));
+  bool uniform = false;
+  if constexpr (PATH == Path::N32) uniform = (hd.flags & kNodeUniform4) != 0u;
+  uint32_t cm = 0, cc = 0;
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    const uint32_t hj = (hd.healthy_mask >> j) & 1u;
+    cm += (uint32_t)(fr.v[j] >= m) & hj;   // CardFitsMemory (filter.go:52-54)
+  }
+  if (uniform) {
+    // (only ck[0] is meaningful: every real card has that clock)
+    cc = (ck.v[0] == c) ? (uint32_t)__builtin_popcount(hd.healthy_mask) : 0u;
+  } else {
+#pragma unroll
+    for (int j = 0; j < K; ++j)
+      cc += (uint32_t)(ck.v[j] == c) & ((hd.healthy_mask >> j) & 1u);  // filter.go:56-58
+  }
+  uint32_t code = cc >= need_clk ? kReasonNone : kReasonClock;
+  code = cm >= need_mem ? code : kReasonMemory;
+  code = number <= hd.card_number ? code : kReasonNumber;
+  return (hd.flags & kNodeAbsent) != 0u ? kReasonAbsent : code;
+}
+
 __device__ __forceinline__ uint64_t ballot(bool b) { return __builtin_amdgcn_ballot_w64(b); }
 // per-16-bit-half maximum of two packed pairs (v_pk_max_u16)
 __device__ __forceinline__ uint32_t max16x2(uint32_t a, uint32_t b) {
@@ -378,6 +415,130 @@ __global__ __launch_bounds__(kBlock) void k1_filter_maxima(
   for (int f = 0; f < 6; ++f) pmax[((size_t)f * C + chunk) * n_pods + p] = (uint64_t)mx[f];
   pcnt[((size_t)0 * C + chunk) * n_pods + p] = nf;
   pcnt[((size_t)1 * C + chunk) * n_pods + p] = nz;
+}
+
+// ---------------------------------------------------------------------------------------
+// The diagnosis (include/yoda.h "Filter diagnosis"): why Filter rejected a node, per (pod, node).
+// k_diag_select compacts the selected pods of a completed run on the device -- the pods whose
+// final n_feasible is 0, or every pod -- into list / *n_list (caller ids, any order: each pod's
+// counts are its own) and initialises the counts: zeros for a selected pod, all ones otherwise.
+// *n_list is zero on entry.
+__global__ __launch_bounds__(kBlock) void k_diag_select(const uint32_t* __restrict__ n_feasible,
+                                                        uint32_t n_pods, uint32_t all,
+                                                        uint32_t* __restrict__ list,
+                                                        uint32_t* __restrict__ n_list,
+                                                        uint32_t* __restrict__ counts) {
+  const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+  const bool sel = p < n_pods && (all != 0u || n_feasible[p] == 0u);
+  const uint64_t b = ballot(sel);
+  if (p < n_pods) {
+    const uint32_t v = sel ? 0u : 0xffffffffu;
+    reinterpret_cast<uint4*>(counts)[p] = make_uint4(v, v, v, v);
+  }
+  if (b == 0ull) return;
+  const uint32_t lane = lane_id();
+  const uint32_t first = (uint32_t)__builtin_ctzll(b);
+  uint32_t base = 0;
+  if (lane == first) base = atomicAdd(n_list, (uint32_t)__builtin_popcountll(b));
+  base = (uint32_t)__builtin_amdgcn_readlane((int)base, (int)first);
+  if (sel) list[base + (uint32_t)__builtin_popcountll(b & ((1ull << lane) - 1ull))] = p;
+}
+
+// The sweep.  One wave a workgroup; a LANE is a selected POD (list[i], caller order: the pod
+// arrays are the upload's own, so a padded or sorted run order never reaches this kernel and no
+// pod is visited twice), a task is (pod wave of the selected pods) x (node chunk), and the
+// workgroups stride over the tasks.  Both factors are known only on the device (*n_list), so
+// the kernel sizes the chunks itself: about a.target_tasks tasks, in whole 64-node blocks -- one
+// selected wave gets one block a task (every CU busy), a whole batch long chunks (few atomics).
+// A workgroup past the tasks, or any workgroup of an empty selection, exits before it reads or
+// writes anything but *n_list.  Every node record goes through k1_reasons (wave-uniform address:
+// scalar loads), the candidate word through one more uniform load.
+//   ROWS == false: four per-lane counters over the chunk, then at most one atomicAdd per
+// non-zero counter into counts [P][4] = {not a candidate, number, memory, clock}; integer adds,
+// so the result does not depend on the schedule.  Absent nodes are counted nowhere.
+//   ROWS == true: the chunk is one block; the lane's 64 codes go to its row of a 64 x 64-byte
+// LDS tile and from there as ONE 64-byte run to rows[p * row_stride + 64 * block] (row_stride a
+// multiple of 64, so the four 16-byte stores are aligned and whole); codes past the last node
+// are kReasonPad.
+template <int K, Path PATH, bool ROWS>
+__global__ __launch_bounds__(kWave) void k1_diagnose(const unsigned char* __restrict__ nodes,
+                                                     const uint64_t* __restrict__ cand_w,
+                                                     const DiagArgs a) {
+  using R = Rec<PATH>;
+  using T = typename R::T;
+  __shared__ uint4 tile[ROWS ? kWave * 4 : 1];
+  const uint32_t nsel = a.n_list ? uniform_u32(*a.n_list) : a.n_pods;
+  if (nsel == 0u || a.n_nodes == 0u) return;
+  const uint32_t nw = (nsel + 63u) >> 6, NB = (a.n_nodes + 63u) >> 6;
+  uint32_t cb = 1u;  // 64-node blocks a chunk
+  if constexpr (!ROWS) {
+    const uint32_t want = max(1u, min(NB, a.target_tasks / nw));
+    cb = (NB + want - 1u) / want;
+  }
+  const uint32_t C = (NB + cb - 1u) / cb;
+  const uint32_t tasks = nw * C;
+  const uint32_t lane = threadIdx.x;
+  const T* m_in = static_cast<const T*>(a.m);
+  const T* c_in = static_cast<const T*>(a.c);
+  for (uint32_t task = blockIdx.x; task < tasks; task += gridDim.x) {
+    const uint32_t w = task / C, chunk = task - w * C;
+    const uint32_t i = 64u * w + lane;
+    const bool live = i < nsel;
+    const uint32_t p = live ? (a.list ? a.list[i] : i) : 0u;
+    T m = 0, c = 0;
+    uint64_t number = ~0ull;
+    uint32_t need_mem = 0, need_clk = 0, cls = 0xffu;
+    if (live) {
+      m = m_in[p];
+      c = c_in[p];
+      number = a.number[p];
+      need_mem = a.need_mem[p];
+      need_clk = a.need_clk[p];
+      if (a.cls) cls = a.cls[p];
+    }
+    // (a YODA_CAND_ANY lane, or candidates off: no candidate test)
+    const bool restricted = cand_w != nullptr && cls != 0xffu;
+    const uint32_t n0 = chunk * cb * 64u;
+    const uint32_t n1 = min(n0 + cb * 64u, a.n_nodes);
+    uint32_t cnt[4] = {0u, 0u, 0u, 0u};
+    for (uint32_t nb = n0; nb < n1; nb += 64u) {
+      const uint32_t ne = ROWS ? nb + 64u : min(nb + 64u, n1);
+      for (uint32_t n = nb; n < ne; ++n) {
+        uint32_t code = kReasonPad;
+        if (!ROWS || n < n1) {
+          code = k1_reasons<K, PATH>(nodes + (size_t)n * R::stride(K), m, c, number, need_mem,
+                                     need_clk);
+          if (cand_w) {
+            const uint64_t word = cand_w[n];  // (uniform: one scalar load)
+            const bool out = restricted & (((word >> (cls & 63u)) & 1ull) == 0ull);
+            code = (out & (code != kReasonAbsent)) ? kReasonNotCandidate : code;
+          }
+        }
+        if constexpr (ROWS) {
+          reinterpret_cast<unsigned char*>(tile)[lane * 64u + (n - nb)] = (unsigned char)code;
+        } else {
+          cnt[0] += (uint32_t)(code == kReasonNotCandidate);
+          cnt[1] += (uint32_t)(code == kReasonNumber);
+          cnt[2] += (uint32_t)(code == kReasonMemory);
+          cnt[3] += (uint32_t)(code == kReasonClock);
+        }
+      }
+      if constexpr (ROWS) {
+        if (live) {
+          uint4* out = reinterpret_cast<uint4*>(a.rows + (size_t)p * a.row_stride + nb);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) out[q] = tile[lane * 4u + q];
+        }
+      }
+    }
+    if constexpr (!ROWS) {
+      if (live) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (cnt[k]) atomicAdd(a.counts + 4u * (size_t)p + k, cnt[k]);
+      }
+    }
+  }
 }
 
 // K1 for the capacity-decrement greedy windows (YODA_GREEDY_CARD_CAPACITY, fast record
@@ -5253,6 +5414,39 @@ hipError_t launch_k1(int K, Path path, const unsigned char* nodes, const unsigne
                                           part.cnt, bm, bm_stride));
       break;
   }
+  return hipGetLastError();
+}
+
+hipError_t launch_diag_select(const uint32_t* n_feasible, uint32_t n_pods, bool all,
+                              uint32_t* list, uint32_t* n_list, uint32_t* counts, hipStream_t s) {
+  if (n_pods == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_diag_select, pod_grid(n_pods), dim3(kBlock), 0, s, n_feasible, n_pods,
+                     all ? 1u : 0u, list, n_list, counts);
+  return hipGetLastError();
+}
+
+// The sweep's launch shape: one-wave workgroups, 32 a CU at most (8 waves a SIMD,
+// 4 KB of LDS each in the rows form), striding over the tasks; the counts form aims at four
+// tasks a workgroup so that an uneven task does not end the launch alone.
+constexpr uint32_t kDiagGrid = 256u * 32u;
+constexpr uint32_t kDiagTargetTasks = 4u * kDiagGrid;
+
+hipError_t launch_diagnose(int K, Path path, bool rows, DiagArgs a, hipStream_t s) {
+  if (a.n_pods == 0 || a.n_nodes == 0) return hipSuccess;
+  const uint64_t most = (uint64_t)((a.n_pods + 63u) / 64u) * ((a.n_nodes + 63u) / 64u);
+  const dim3 grid((uint32_t)std::min<uint64_t>(most, kDiagGrid));
+  a.target_tasks = kDiagTargetTasks;
+#define YODA_DIAG(PATH)                                                                        \
+  if (rows) YODA_K_SWITCH(K, hipLaunchKernelGGL((k1_diagnose<KK, PATH, true>), grid, dim3(kWave), \
+                                                0, s, a.nodes, a.cand_w, a))                  \
+  else YODA_K_SWITCH(K, hipLaunchKernelGGL((k1_diagnose<KK, PATH, false>), grid, dim3(kWave), 0, \
+                                           s, a.nodes, a.cand_w, a))
+  switch (path) {
+    case Path::N32: YODA_DIAG(Path::N32); break;
+    case Path::F64: YODA_DIAG(Path::F64); break;
+    case Path::U64: YODA_DIAG(Path::U64); break;
+  }
+#undef YODA_DIAG
   return hipGetLastError();
 }
 

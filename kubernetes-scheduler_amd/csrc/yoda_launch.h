@@ -233,6 +233,13 @@ hipError_t launch_cand_update(const uint32_t* node, const uint64_t* value, uint3
                               uint64_t* words, const uint32_t* inv, uint64_t* words_p,
                               hipStream_t s);
 hipError_t launch_cand_narrow(const CandArgs& a, hipStream_t s);
+// Filter diagnosis (yoda_diagnose / yoda_reason_rows).  launch_diag_select: the pods of a
+// completed run whose n_feasible is 0 (all: every pod) into list / *n_list (zero on entry), and
+// counts [n_pods][4] zeroed for them, all ones for the others.  launch_diagnose: the sweep
+// (k1_diagnose; rows: the per-node codes instead of the counts); it chooses target_tasks.
+hipError_t launch_diag_select(const uint32_t* n_feasible, uint32_t n_pods, bool all,
+                              uint32_t* list, uint32_t* n_list, uint32_t* counts, hipStream_t s);
+hipError_t launch_diagnose(int K, Path path, bool rows, DiagArgs a, hipStream_t s);
 
 // ---- yoda_order.hip ----
 // Scratch for the sort: keys[2][P] u64, idx[2][P] u32, then hipcub's temp storage.

@@ -566,6 +566,29 @@ struct CandArgs {
   uint32_t* counts;       // [2][n_work]
 };
 
+// Filter diagnosis (include/yoda.h YODA_REASON_*): the reason codes, and the arguments of the
+// sweep (k1_diagnose).  Everything is in the CALLER's pod order and the UPLOAD order of the nodes.
+constexpr uint32_t kReasonNone = 0u, kReasonNumber = 1u, kReasonMemory = 2u, kReasonClock = 3u,
+                   kReasonNotCandidate = 4u, kReasonAbsent = 5u;
+constexpr uint32_t kReasonPad = 0xffu;  // a row byte past the last node (never handed out)
+struct DiagArgs {
+  const unsigned char* nodes;  // the base records
+  uint32_t n_nodes, n_pods;
+  const void* m;               // the record path's thresholds: u32 (ranks with MemTab), f64, u64
+  const void* c;
+  const uint64_t* number;
+  const uint32_t* need_mem;
+  const uint32_t* need_clk;
+  const uint64_t* cand_w;      // [n_nodes] candidate words; nullptr: candidates off
+  const uint8_t* cls;          // [n_pods] class bytes; nullptr: every pod YODA_CAND_ANY
+  const uint32_t* list;        // the selected pods; nullptr: pod i = i
+  const uint32_t* n_list;      // their number (device); nullptr: n_pods
+  uint32_t target_tasks;       // counts form: about this many (pod wave, chunk) tasks
+  uint32_t row_stride;         // rows form: bytes a pod row, a multiple of 64
+  uint32_t* counts;            // [n_pods][4]
+  unsigned char* rows;         // [n_pods][row_stride]
+};
+
 // selectHost draw (include/yoda.h yoda_set_tie_draw): the draw word of (seed, pod, node) and the
 // 64-bit key (word << 32 | node) whose MIN over a pod's tie set is its pick.  mix64: the
 // splitmix64 finalizer; fmix32: the murmur3 32-bit finalizer (a bijection of the u32, so for

@@ -89,7 +89,11 @@ type Yoda struct {
 	cardNumber []uint64
 }
 
-type rowState struct{ row *yodagpu.Row }
+// (reasons: nil in Mode B -- PreFilter)
+type rowState struct {
+	row     *yodagpu.Row
+	reasons []yodagpu.Reason
+}
 
 func (r *rowState) Clone() framework.StateData { return r }
 
@@ -339,7 +343,17 @@ func (y *Yoda) PreFilter(ctx context.Context, state *framework.CycleState, p *v1
 	if err != nil {
 		return framework.NewStatus(framework.Error, err.Error())
 	}
-	state.Write(rowKey, &rowState{row})
+	// The reason row beside the score row, for every Mode A pod: kube-scheduler reads the per-node
+	// Filter statuses (the FitError event, PostFilter) whenever no node passes EVERY Filter plugin,
+	// and this row knows nothing of the other plugins' verdicts.  (ReasonRow serves the pod that
+	// ScoreRow uploaded; the row state keeps nothing of the run it drops.)
+	var reasons []yodagpu.Reason
+	if y.mode == yodagpu.ModeSCV {
+		if reasons, err = y.gpu.ReasonRow(); err != nil {
+			return framework.NewStatus(framework.Error, err.Error())
+		}
+	}
+	state.Write(rowKey, &rowState{row, reasons})
 	return framework.NewStatus(framework.Success, "")
 }
 
@@ -362,10 +376,37 @@ func (y *Yoda) Filter(ctx context.Context, state *framework.CycleState, pod *v1.
 		return framework.NewStatus(framework.Error, err.Error())
 	}
 	i, ok := y.gpu.NodeIndex(nodeInfo.Node().GetName())
-	if !ok || row.Feasible[i/32]>>(uint(i)%32)&1 == 0 {
-		return framework.NewStatus(framework.Unschedulable, "node(s) didn't match the scv card requirements")
+	if !ok {
+		return framework.NewStatus(framework.Unschedulable, filterMessage)
+	}
+	if row.Feasible[i/32]>>(uint(i)%32)&1 == 0 {
+		msg := filterMessage
+		if d, err := state.Read(rowKey); err == nil {
+			if rs := d.(*rowState).reasons; rs != nil {
+				msg = reasonMessage(rs[i])
+			}
+		}
+		return framework.NewStatus(framework.Unschedulable, msg)
 	}
 	return framework.NewStatus(framework.Success, "")
+}
+
+// Filter's messages: kube-scheduler groups the nodes of a FitError event by message.  Without a
+// reason row (Mode B) the single sentence.
+const filterMessage = "node(s) didn't match the scv card requirements"
+
+func reasonMessage(r yodagpu.Reason) string {
+	switch r {
+	case yodagpu.ReasonNumber:
+		return "node(s) didn't have enough scv cards (scv/number)"
+	case yodagpu.ReasonMemory:
+		return "node(s) had too few healthy scv cards with the requested free memory (scv/memory)"
+	case yodagpu.ReasonClock:
+		return "node(s) had too few healthy scv cards at the requested clock (scv/clock)"
+	case yodagpu.ReasonNotCandidate, yodagpu.ReasonAbsent:
+		return "node(s) were rejected by another plugin or are not in the node set"
+	}
+	return filterMessage
 }
 
 func (y *Yoda) PreScore(ctx context.Context, state *framework.CycleState, pod *v1.Pod,

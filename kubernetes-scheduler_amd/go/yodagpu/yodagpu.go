@@ -511,6 +511,55 @@ func (g *Handle) ScoreRow(pod *v1.Pod, mode Mode) (*Row, error) {
 	return row, nil
 }
 
+// Reason is why Filter rejected a (pod, node) pair (YODA_REASON_*): the first that applies in the
+// precedence absent > not a candidate > number > memory > clock.
+type Reason uint8
+
+const (
+	ReasonNone         Reason = C.YODA_REASON_NONE          // the node passes
+	ReasonNumber       Reason = C.YODA_REASON_NUMBER        // PodFitsNumber fails (filter.go:11-16)
+	ReasonMemory       Reason = C.YODA_REASON_MEMORY        // PodFitsMemory fails (filter.go:18-33)
+	ReasonClock        Reason = C.YODA_REASON_CLOCK         // PodFitsClock fails (filter.go:35-50)
+	ReasonNotCandidate Reason = C.YODA_REASON_NOT_CANDIDATE // another plugin's Filter (SetCandidates)
+	ReasonAbsent       Reason = C.YODA_REASON_ABSENT        // not in the node set (SetNodePresent)
+)
+
+// ReasonRow gives the reason code of every node for the pods uploaded last (ScoreRow's pod):
+// reasons[n] == ReasonNone exactly where the row's feasibility bit is set (yoda_reason_rows;
+// Mode A).  It invalidates a pending run, as ScoreRow does.
+// Like the rest of this file, not compiled in this repository (no Go toolchain in the image).
+func (g *Handle) ReasonRow() ([]Reason, error) {
+	n := len(g.nodes)
+	out := make([]Reason, n+1)
+	rc := C.yoda_reason_rows(g.h, (*C.uint8_t)(unsafe.Pointer(&out[0])), C.uint64_t(n))
+	if err := check(g.h, rc, "yoda_reason_rows"); err != nil {
+		return nil, err
+	}
+	return out[:n], nil
+}
+
+// Diagnose counts, after Batch (or ShardedBatch: over this shard's nodes, the caller sums the
+// ranks), the nodes each pod lost to each reason: counts[p] = {not a candidate, number, memory,
+// clock}, for the pods without a feasible node -- all: for every pod; a pod that was not selected
+// has 0xFFFFFFFF in all four.  Absent nodes are counted nowhere (yoda_diagnose +
+// yoda_download_diagnosis; Mode A).  nPods: the size of that batch.
+// Like the rest of this file, not compiled in this repository (no Go toolchain in the image).
+func (g *Handle) Diagnose(nPods int, all bool) ([][4]uint32, error) {
+	flags := C.uint32_t(0)
+	if all {
+		flags = C.YODA_DIAG_ALL
+	}
+	if err := check(g.h, C.yoda_diagnose(g.h, flags), "yoda_diagnose"); err != nil {
+		return nil, err
+	}
+	out := make([][4]uint32, nPods+1)
+	rc := C.yoda_download_diagnosis(g.h, (*C.uint32_t)(unsafe.Pointer(&out[0])), C.uint64_t(4*nPods))
+	if err := check(g.h, rc, "yoda_download_diagnosis"); err != nil {
+		return nil, err
+	}
+	return out[:nPods], nil
+}
+
 // Batch schedules many pods independently against the snapshot (configs 2-4).  Picks are
 // node indices, -1 unschedulable, -2 error (see statuses).
 func (g *Handle) Batch(pods []*v1.Pod, mode Mode) (picks []int32, statuses []int32, err error) {

@@ -12,7 +12,7 @@ from typing import Optional
 
 import numpy as np
 
-from .soa import CEvalOut, CNodeSoA, CPodSoA, EvalResult, NodeSoA, PodSoA
+from .soa import DIAG_ALL, CEvalOut, CNodeSoA, CPodSoA, EvalResult, NodeSoA, PodSoA
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # YODA_LIB_PATH: another build of libyoda for interleaved A/B timing (tools/ab_lib.sh)
@@ -94,6 +94,9 @@ _SIGS = {
     "yoda_greedy_candidates": ([_vp, C.c_int], C.c_int),
     "yoda_shard_candidates": ([_vp, C.c_int], C.c_int),
     "yoda_mode_b_info": ([_vp, _vp], C.c_int),
+    "yoda_diagnose": ([_vp, _u32], C.c_int),
+    "yoda_download_diagnosis": ([_vp, _vp, C.c_uint64], C.c_int),
+    "yoda_reason_rows": ([_vp, _vp, C.c_uint64], C.c_int),
     "yoda_snapshot_check": ([_vp, _vp, _vp], C.c_int),
     "yoda_shard_topk": ([_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp], C.c_int),
     "yoda_shard_topk_depth": ([_vp], C.c_int),
@@ -606,6 +609,27 @@ class Yoda:
         out = np.zeros(4, np.uint32)
         self._check(lib().yoda_mode_b_info(self._h, _np_ptr(out)), "yoda_mode_b_info")
         return tuple(int(v) for v in out)
+
+    def diagnose(self, all: bool = False) -> np.ndarray:
+        """Why Filter rejected nodes, after a completed Mode A run (yoda_diagnose +
+        yoda_download_diagnosis): uint32 [P, 4] = (not a candidate, number, memory, clock) nodes
+        per pod, caller order, for the pods whose n_feasible is 0 -- all=True: for every pod; a
+        pod that was not selected has 0xFFFFFFFF in all four.  Absent nodes are counted nowhere.
+        On a shard handle the counts cover the shard's nodes: sum the shards' arrays."""
+        self._check(lib().yoda_diagnose(self._h, DIAG_ALL if all else 0), "yoda_diagnose")
+        counts = np.zeros((self.n_pods, 4), np.uint32)
+        self._check(lib().yoda_download_diagnosis(self._h, _np_ptr(counts), counts.size),
+                    "yoda_download_diagnosis")
+        return counts
+
+    def reason_rows(self) -> np.ndarray:
+        """uint8 [P, N]: the soa.REASON_* code of every (uploaded pod, node) -- 0 exactly where
+        score_rows() says feasible (yoda_reason_rows; Mode A, a handful of pods).  Invalidates a
+        pending run, as score_rows does: call it before score_rows to keep the latter's picks."""
+        reasons = np.zeros((self.n_pods, self.n_nodes), np.uint8)
+        self._check(lib().yoda_reason_rows(self._h, _np_ptr(reasons), reasons.size),
+                    "yoda_reason_rows")
+        return reasons
 
     def candidates_profile(self) -> float:
         """The narrowing pass's HIP-event time (ms) over the runs read by profile_read since the

@@ -27,7 +27,8 @@ from typing import Dict, List, Mapping, Optional, Sequence, Tuple
 import numpy as np
 
 from .pack import pack_pods
-from .soa import MODE_SCV, NodeSoA
+from .soa import (MODE_SCV, REASON_ABSENT, REASON_CLOCK, REASON_MEMORY, REASON_NOT_CANDIDATE,
+                  REASON_NUMBER, NodeSoA)
 
 NAME = "yoda"
 MAX_NODE_SCORE = 100
@@ -64,10 +65,24 @@ class NodeScore:
     score: int
 
 
+# Filter's message when the backend cannot say why (no reason_rows), and per reason code
+# (soa.REASON_*, include/yoda.h): kube-scheduler groups the nodes of a FitError event by message
+FILTER_MESSAGE = "node(s) didn't match the scv card requirements"
+REASON_MESSAGES = {
+    REASON_NUMBER: "node(s) didn't have enough scv cards (scv/number)",
+    REASON_MEMORY: "node(s) had too few healthy scv cards with the requested free memory "
+                   "(scv/memory)",
+    REASON_CLOCK: "node(s) had too few healthy scv cards at the requested clock (scv/clock)",
+    REASON_NOT_CANDIDATE: "node(s) were rejected by another plugin or are not in the node set",
+    REASON_ABSENT: "node(s) were rejected by another plugin or are not in the node set",
+}
+
+
 @dataclass
 class _Row:
     feasible: np.ndarray  # bool [N]
     scores: np.ndarray    # int64 [N], -1 where infeasible
+    reasons: Optional[np.ndarray] = None  # uint8 [N] soa.REASON_*, when the backend gives them
 
 
 def _wrap_i64(x: int) -> int:
@@ -100,15 +115,25 @@ class YodaPlugin:
     # ---- extension points ---------------------------------------------------------------
     def pre_filter(self, state: CycleState, pod: Mapping) -> Status:
         self.backend.upload_pods(pack_pods([pod]))
+        # The reason row beside the score row (Mode A; Mode B has no Filter of its own).  It goes
+        # first: yoda_reason_rows drops a pending run, yoda_score_rows leaves its own.  Every pod
+        # gets it: kube-scheduler reads the per-node statuses whenever no node passes EVERY Filter
+        # plugin, and this row knows nothing of the other plugins' verdicts.
+        reasons = None
+        if self.mode == MODE_SCV and hasattr(self.backend, "reason_rows"):
+            reasons = self.backend.reason_rows()[0]
         feas, scores = self.backend.score_rows(self.mode)
-        state.write(NAME + "/row", _Row(feas[0], scores[0]))
+        state.write(NAME + "/row", _Row(feas[0], scores[0], reasons))
         return Status()
 
     def filter(self, state: CycleState, pod: Mapping, node_name: str) -> Status:
         row: _Row = state.read(NAME + "/row")
-        if row.feasible[self.index[node_name]]:
+        i = self.index[node_name]
+        if row.feasible[i]:
             return Status()
-        return Status(UNSCHEDULABLE, "node(s) didn't match the scv card requirements")
+        if row.reasons is None:
+            return Status(UNSCHEDULABLE, FILTER_MESSAGE)
+        return Status(UNSCHEDULABLE, REASON_MESSAGES.get(int(row.reasons[i]), FILTER_MESSAGE))
 
     def pre_score(self, state: CycleState, pod: Mapping, nodes: Sequence[str]) -> Status:
         return Status()

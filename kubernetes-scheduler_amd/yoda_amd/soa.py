@@ -25,6 +25,15 @@ STATUS_SCORE_RANGE = 3
 UPLOAD_FORCE_GENERIC = 1
 RUN_BITMASK = 1
 GREEDY_CARD_CAPACITY = 1
+# Filter diagnosis (include/yoda.h YODA_REASON_*): why Filter rejected a (pod, node) pair, in the
+# precedence absent > not a candidate > number > memory > clock
+REASON_NONE = 0
+REASON_NUMBER = 1
+REASON_MEMORY = 2
+REASON_CLOCK = 3
+REASON_NOT_CANDIDATE = 4
+REASON_ABSENT = 5
+DIAG_ALL = 1
 
 _u8p = C.POINTER(C.c_uint8)
 _u32p = C.POINTER(C.c_uint32)
