@@ -482,7 +482,7 @@ int yoda_set_node_state(yoda_t* h, uint32_t count, const uint32_t* nodes, const 
  * [t * max_cards + j], slots >= the node's uploaded card_count ignored; an id listed more than
  * once keeps its LAST entry; count == 0 is a no-op.  Card count, CardNumber, TotalMemory[Sum],
  * clock, bandwidth, core, power are NOT changed by this call (CardNumber: yoda_set_node_state;
- * the rest: yoda_upload_nodes).  max_cards: 1..16 and at least the uploaded card count of every
+ * the rest: yoda_replace_nodes).  max_cards: 1..16 and at least the uploaded card count of every
  * listed node.  After it the handle answers every entry point as a handle freshly uploaded with
  * the modified snapshot would.  YODA_ERR_RANGE: a value the uploaded snapshot's format cannot
  * hold -- on the 32-bit record path a FreeMemory above 0xFFFFFFFE or, with memory ranks
@@ -526,6 +526,59 @@ int yoda_set_node_present(yoda_t* h, uint32_t count, const uint32_t* nodes,
                           const uint8_t* present);
 /* Diagnostic (host only): how many nodes of this handle's snapshot are absent. */
 int yoda_nodes_absent(const yoda_t* h, uint32_t* n_absent);
+/* Replace the WHOLE record of the listed nodes -- card count, CardNumber, every card field, the
+ * memory sums, the allocation, and Mode B's cpu / disk_io -- without re-uploading the snapshot: a
+ * machine whose GPUs were swapped, a changed card count, TotalMemory[Sum], clock, bandwidth, core
+ * or power.  recs: a yoda_node_soa with n_nodes == count whose entry t is the complete new record
+ * of node nodes[t] (GLOBAL id); recs->max_cards (1..16) is its own stride; every array means what
+ * it means for yoda_upload_nodes (alloc_memory == NULL: 0; cpu / disk_io: required when the
+ * snapshot was uploaded with them, ignored when it was not).  Ids outside this handle's shard are
+ * ignored, so one list serves every shard; an id listed more than once keeps its LAST entry (the
+ * earlier ones are neither checked nor written); count == 0 is a no-op.  YODA_ERR_NO_NODES before
+ * an upload; YODA_ERR_INVALID_ARG for a NULL array, recs->n_nodes != count, a card_count above
+ * recs->max_cards or missing cpu / disk_io.  The work is ordered on the handle's stream; pending
+ * run, phase-1, top-k, draw and diagnosis state is invalidated.
+ *   After the call the handle answers every entry point -- both modes, all three record paths,
+ * yoda_greedy*, the yoda_shard_* and yoda_comm_* calls, yoda_snapshot_check with every mismatch
+ * word 0 -- as a handle freshly uploaded with the modified snapshot and the same upload flags
+ * would once it is brought to the same presence bits, candidate words, pod classes and settings.
+ * The node keeps its presence bit: an absent node takes the record and stays absent, and the
+ * record counts for the PreScore maxima when it returns.  The node keeps its candidate word
+ * (yoda_update_candidates changes it).  One documented exception: yoda_score_bound and
+ * yoda_small_field_max only grow -- they stay valid upper bounds, not the fresh upload's tight
+ * ones.  The block grouping, the K2 bound levels and the hot-block hint stay as uploaded (speed
+ * only, no result depends on them).
+ *   New nodes (scale-up) are served by spare slots: upload placeholder nodes (card_count 0), take
+ * them out with yoda_set_node_present, and when a node joins replace one placeholder with its
+ * record and put it back.  n_nodes itself never changes.
+ *   YODA_ERR_RANGE: the record does not fit the format the upload chose (NOT the one a fresh
+ * upload of the new snapshot would choose, which may be narrower: the handle keeps the wider one).
+ * A card count above the snapshot's card stride (the uploaded largest count rounded up to 1, 2,
+ * 4, 8 or 16).  On the 32-bit record path: a clock, bandwidth, core or power above 0xFFFFFFFE, or
+ * above 65535 / 55738 when the upload packed them in 16 bits / took f32 quotients (every uploaded
+ * value was that small); a node with several GPU models or TotalMemory values when it did not take
+ * f32 quotients; 800 + 100 * clock / max(bandwidth, 1), times the card stride, of 2^32 or more; a
+ * FreeMemory or TotalMemory above 0xFFFFFFFE or, with memory ranks (yoda_memory_ranks), one that
+ * is no card FreeMemory resp. TotalMemory value of the uploaded snapshot.  On the f64 path a card
+ * field above 2^44.  On both a static score of 2^51 or more, or card stride * (800 + 100 * clock)
+ * + static score of 2^52 or more.  The exact-u64 path takes everything.  Everything is validated
+ * before anything is written: a failed call leaves the handle exactly as it was; re-upload.
+ *   Cost: that of yoda_update_node_cards for the same list (the same writer and rebuilds). */
+int yoda_replace_nodes(yoda_t* h, uint32_t count, const uint32_t* nodes,
+                       const yoda_node_soa* recs);
+/* Mode B's node inputs, NodeInfo.Cpu and NodeInfo.DiskIO (live metrics, re-read in every PreScore:
+ * scheduler.go:101-114), without a re-upload.  Sparse form: nodes holds GLOBAL ids, entry t the
+ * new cpu[t] / disk_io[t] of node nodes[t]; ids outside this handle's shard are ignored, the LAST
+ * entry of a repeated id wins, count == 0 is a no-op.  Dense form: nodes == NULL and
+ * count == n_nodes, entry i is local node i (the whole fleet after a scrape).  YODA_ERR_NO_NODES
+ * before an upload; YODA_ERR_STATE when the snapshot was uploaded without cpu / disk_io;
+ * YODA_ERR_INVALID_ARG for a NULL cpu / disk_io or a dense count other than n_nodes.  The stored
+ * records are bit-identical to a fresh upload's (the same host division).  Ordered on the handle's
+ * stream; pending run state is invalidated.  Presence bits, candidate words, pod classes and
+ * settings stay, and the eligibility table of yoda_mode_b_follow, which does not read the metrics,
+ * is NOT rebuilt (yoda_mode_b_info's build counter).  Mode A never reads these records. */
+int yoda_update_node_metrics(yoda_t* h, uint32_t count, const uint32_t* nodes, const double* cpu,
+                             const double* disk_io);
 /* ---- Candidate classes: other plugins' Filter results in the batch path ----
  * In kube-scheduler a node is scored for a pod only if EVERY Filter plugin passed it (cordon,
  * taints, nodeSelector / affinity, resource fit), while CollectMaxValues

@@ -189,6 +189,11 @@ struct yoda_handle {
   DevBuf memtab;
   MemTab mt = {};
   std::vector<uint64_t> h_frees;  // the distinct card frees, ascending (pod thresholds)
+  std::vector<uint64_t> h_totals;  // ... and the distinct card totals (yoda_replace_nodes)
+  // yoda_replace_nodes: the flags of the upload, and how many nodes are one-model with one
+  // TotalMemory / one-model (all_one_model, all_uni4 below are these against n_nodes)
+  uint32_t upload_flags = 0;
+  uint32_t n_one_model = 0, n_uni4 = 0;
   DevBuf gtab, gtab_aux;  // the G table (yoda_layout.h GTab) + [G maxima | its reciprocals]
   GTab g = {};
   bool has_k1sum = false, has_k2sum = false;
@@ -2486,6 +2491,9 @@ int yoda_upload_nodes(yoda_t* h, const yoda_node_soa* nd, uint32_t node_offset, 
     h->b_elig_dirty = true;  // (Mode B's eligibility table is the old snapshot's)
     h->b_elig_builds = 0;
     h->nodes_diskio = diskio;
+    h->upload_flags = flags;
+    h->n_one_model = rows.n_one_model;
+    h->n_uni4 = rows.n_uni4;
     h->all_one_model = rows.n_one_model == N;
     h->all_uni4 = rows.n_uni4 == N;
     h->kbub_dirty = true;
@@ -2497,6 +2505,7 @@ int yoda_upload_nodes(yoda_t* h, const yoda_node_soa* nd, uint32_t node_offset, 
       if (int rc = build_hot_masks(h)) return rc;
     }
     h->h_frees.swap(mc.frees);
+    h->h_totals.swap(mc.totals);
     h->has_nodes = true;
     // the uploaded pods' N32 memory thresholds follow the snapshot (ranks or the clamp)
     if (h->has_pods && path == Path::N32) {
@@ -4534,6 +4543,330 @@ int yoda_update_candidates(yoda_t* h, uint32_t count, const uint32_t* nodes,
                                   h->perm_on ? h->cand_w_p.as<uint64_t>() : nullptr, h->stream));
     // the block ANDs of both orders: whole, one wave a block (12 KB each at 100k nodes)
     return cand_rebuild_sums(h, false);
+  } catch (const std::bad_alloc&) {
+    h->upd_slot.clear();
+    return fail(h, YODA_ERR_INVALID_ARG, "host allocation failed");
+  } catch (...) {
+    h->upd_slot.clear();
+    return fail(h, YODA_ERR_INVALID_ARG, "unexpected exception");
+  }
+}
+
+namespace {
+
+// Mode B's records of cnt nodes onto the device (k_set_node_metrics): local node loc[k] -- node
+// k when loc == nullptr, the dense form -- takes entry ent[k] (entry k when ent == nullptr) of
+// cpu / disk_io.  The division is the upload's own expression, on the host: the stored records
+// are bit-identical to a fresh upload's.  Staged as the other sparse writers stage (upd_stage /
+// upd_node / upd_event), ordered on the handle's stream.
+int push_node_metrics(yoda_t* h, uint32_t cnt, const uint32_t* loc, const uint32_t* ent,
+                      const double* cpu, const double* disk_io) {
+  if (cnt == 0) return YODA_OK;
+  const size_t o_rec = loc ? ((size_t)cnt * 4 + 15) / 16 * 16 : 0;
+  const size_t bytes = o_rec + (size_t)cnt * sizeof(NodeRecB);
+  if (h->upd_pending) HIP_TRY(h, hipEventSynchronize(h->upd_event));
+  HIP_TRY(h, h->upd_stage.ensure(bytes));
+  HIP_TRY(h, h->upd_node.ensure(bytes));
+  unsigned char* st = static_cast<unsigned char*>(h->upd_stage.p);
+  if (loc) std::memcpy(st, loc, (size_t)cnt * 4);
+  NodeRecB* rb = reinterpret_cast<NodeRecB*>(st + o_rec);
+  for (uint32_t k = 0; k < cnt; ++k) {
+    const uint32_t e = ent ? ent[k] : k;
+    rb[k].v = cpu[e] / 100.0;     // algorithm.go:73
+    rb[k].u = disk_io[e] / 50.0;  // algorithm.go:71
+  }
+  HIP_TRY(h, hipMemcpyAsync(h->upd_node.p, st, bytes, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipEventRecord(h->upd_event, h->stream));
+  h->upd_pending = true;
+  const unsigned char* d = h->upd_node.as<unsigned char>();
+  HIP_TRY(h, launch_set_node_metrics(h->nodes_b.as<NodeRecB>(),
+                                     loc ? reinterpret_cast<const uint32_t*>(d) : nullptr,
+                                     reinterpret_cast<const NodeRecB*>(d + o_rec), cnt, h->n_nodes,
+                                     h->stream));
+  return YODA_OK;
+}
+
+// One card's largest value per MaxValue field (floor 1) of a host record.
+void record_maxima(const yoda_t* h, const unsigned char* r, uint64_t m[6]) {
+  NodeHdrG hd;
+  std::memcpy(&hd, r, sizeof(hd));
+  const uint32_t nc = (uint32_t)__builtin_popcount(hd.real_mask);
+  for (int f = 0; f < 6; ++f) {
+    m[f] = 1;
+    for (uint32_t j = 0; j < nc; ++j) m[f] = std::max(m[f], rec_field(h, r, kMaxToCard[f], j));
+  }
+}
+
+}  // namespace
+
+int yoda_update_node_metrics(yoda_t* h, uint32_t count, const uint32_t* nodes, const double* cpu,
+                             const double* disk_io) {
+  if (!h) return YODA_ERR_INVALID_ARG;
+  if (!h->has_nodes) return fail(h, YODA_ERR_NO_NODES, "no node snapshot uploaded");
+  if (!h->nodes_diskio)
+    return fail(h, YODA_ERR_STATE, "the snapshot was uploaded without cpu / disk_io");
+  if (!nodes && count != h->n_nodes)
+    return fail(h, YODA_ERR_INVALID_ARG, "the dense form takes n_nodes entries");
+  if (count == 0) return YODA_OK;
+  if (!cpu || !disk_io) return fail(h, YODA_ERR_INVALID_ARG, "NULL node metrics array");
+  try {
+    HIP_TRY(h, hipSetDevice(h->device));
+    std::vector<uint32_t> loc, ent;
+    if (nodes) {
+      // one entry per node, the last of a repeated id (the upd_slot pattern of yoda_set_node_state)
+      if (h->upd_slot.size() != h->n_nodes) h->upd_slot.assign(h->n_nodes, ~0u);
+      for (uint32_t t = 0; t < count; ++t) {
+        if (nodes[t] < h->node_offset || nodes[t] - h->node_offset >= h->n_nodes) continue;
+        const uint32_t i = nodes[t] - h->node_offset;
+        uint32_t& slot = h->upd_slot[i];
+        if (slot == ~0u) {
+          slot = (uint32_t)loc.size();
+          loc.push_back(i);
+          ent.push_back(t);
+        } else {
+          ent[slot] = t;
+        }
+      }
+      for (uint32_t i : loc) h->upd_slot[i] = ~0u;
+      if (loc.empty()) return YODA_OK;
+    }
+    // the pending outcomes are the old metrics'; the eligibility table of yoda_mode_b_follow
+    // reads the presence bits and the candidate words only and stays, as do the pods' classes
+    h->ran = false;
+    h->phase1_done = false;
+    h->topk_ready = false;
+    h->draw_stage = 0;
+    h->diag_done = false;
+    h->k3_pending = false;
+    if (nodes) return push_node_metrics(h, (uint32_t)loc.size(), loc.data(), ent.data(), cpu, disk_io);
+    return push_node_metrics(h, count, nullptr, nullptr, cpu, disk_io);
+  } catch (const std::bad_alloc&) {
+    h->upd_slot.clear();
+    return fail(h, YODA_ERR_INVALID_ARG, "host allocation failed");
+  } catch (...) {
+    h->upd_slot.clear();
+    return fail(h, YODA_ERR_INVALID_ARG, "unexpected exception");
+  }
+}
+
+int yoda_replace_nodes(yoda_t* h, uint32_t count, const uint32_t* nodes,
+                       const yoda_node_soa* recs) {
+  if (!h) return YODA_ERR_INVALID_ARG;
+  if (!h->has_nodes) return fail(h, YODA_ERR_NO_NODES, "no node snapshot uploaded");
+  if (count == 0) return YODA_OK;
+  if (!nodes || !recs) return fail(h, YODA_ERR_INVALID_ARG, "NULL node replacement array");
+  if (recs->n_nodes != count)
+    return fail(h, YODA_ERR_INVALID_ARG, "recs->n_nodes differs from count");
+  const uint32_t KS = recs->max_cards;
+  if (KS < 1 || KS > YODA_MAX_CARDS)
+    return fail(h, YODA_ERR_INVALID_ARG, "max_cards must be in 1..16");
+  if (!recs->card_number || !recs->card_count || !recs->free_memory_sum ||
+      !recs->total_memory_sum || !recs->card_free_memory || !recs->card_total_memory ||
+      !recs->card_clock || !recs->card_bandwidth || !recs->card_core || !recs->card_power ||
+      !recs->card_healthy)
+    return fail(h, YODA_ERR_INVALID_ARG, "a required node array is NULL");
+  if (h->nodes_diskio && !(recs->cpu && recs->disk_io))
+    return fail(h, YODA_ERR_INVALID_ARG, "the snapshot holds cpu / disk_io: the records need them");
+  for (uint32_t t = 0; t < count; ++t)
+    if (recs->card_count[t] > KS) return fail(h, YODA_ERR_INVALID_ARG, "card_count > max_cards");
+  try {
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int K = h->K;
+    const bool n32 = h->path == Path::N32;
+    const size_t stride = n32 ? n32_stride(K) : node_stride(K);
+    const uint32_t row_words = packed_row_words(h);
+    // one entry per node, the last of a repeated id (the upd_slot pattern of yoda_set_node_state)
+    if (h->upd_slot.size() != h->n_nodes) h->upd_slot.assign(h->n_nodes, ~0u);
+    if (h->h_absent.size() != h->n_nodes) h->h_absent.assign(h->n_nodes, 0);
+    std::vector<uint32_t> loc, ent;
+    for (uint32_t t = 0; t < count; ++t) {
+      if (nodes[t] < h->node_offset || nodes[t] - h->node_offset >= h->n_nodes) continue;
+      const uint32_t i = nodes[t] - h->node_offset;
+      uint32_t& slot = h->upd_slot[i];
+      if (slot == ~0u) {
+        slot = (uint32_t)loc.size();
+        loc.push_back(i);
+        ent.push_back(t);
+      } else {
+        ent[slot] = t;
+      }
+    }
+    for (uint32_t i : loc) h->upd_slot[i] = ~0u;
+    const uint32_t cnt = (uint32_t)loc.size();
+    if (cnt == 0) return YODA_OK;
+    // Validate every record against the format the upload chose (choose_format's rules, one node
+    // at a time) and pack it into host scratch; nothing of the handle is written before the whole
+    // list has passed.
+    const bool no_uniform = (h->upload_flags & YODA_UPLOAD_NO_UNIFORM) != 0u;
+    h->cu_rows.assign((size_t)cnt * row_words, 0u);
+    std::vector<uint64_t> stat(cnt);
+    std::vector<uint32_t> new_flags(cnt);
+    uint64_t g[6];
+    std::memcpy(g, h->h_gmax, sizeof(g));
+    uint32_t lost = 0;  // bit f: a replaced record held the G maximum of MaxValue field f
+    uint64_t new_actual = h->sb_actual, new_small = h->small_max;
+    long double new_cards = h->sb_cards;
+    for (uint32_t ti = 0; ti < cnt; ++ti) {
+      const uint32_t i = loc[ti], t = ent[ti];
+      const size_t a = (size_t)t * KS;
+      const uint32_t nc = recs->card_count[t];
+      if (nc > (uint32_t)K)
+        return fail(h, YODA_ERR_RANGE, "card count above the snapshot's; re-upload the nodes");
+      const uint64_t* fr = recs->card_free_memory + a;
+      const uint64_t* tot = recs->card_total_memory + a;
+      const uint64_t* ck = recs->card_clock + a;
+      const uint64_t* bw = recs->card_bandwidth + a;
+      const uint64_t* co = recs->card_core + a;
+      const uint64_t* pw = recs->card_power + a;
+      uint8_t hl[YODA_MAX_CARDS];
+      uint32_t fc[YODA_MAX_CARDS] = {}, tc[YODA_MAX_CARDS] = {};
+      uint64_t max_clock = 0, max_small = 0, max_field = 0, max_ckq = 0;
+      bool one = nc > 0 && !no_uniform;  // one GPU model with one TotalMemory
+      for (uint32_t j = 0; j < nc; ++j) {
+        hl[j] = recs->card_healthy[a + j] ? 1 : 0;
+        max_clock = std::max(max_clock, ck[j]);
+        max_small = std::max({max_small, ck[j], bw[j], co[j], pw[j]});
+        max_field = std::max({max_field, fr[j], tot[j], ck[j], bw[j], co[j], pw[j]});
+        if (ck[j] <= kN32FieldMax)
+          max_ckq = std::max(max_ckq, ck[j] * 100u / std::max<uint64_t>(1, bw[j]));
+        one = one && ck[j] == ck[0] && bw[j] == bw[0] && co[j] == co[0] && pw[j] == pw[0] &&
+              tot[j] == tot[0];
+      }
+      if (n32) {
+        if (max_small > kN32FieldMax)
+          return fail(h, YODA_ERR_RANGE, "a card field leaves the 32-bit path; re-upload the nodes");
+        if (h->pack16 && max_small > kPack16Max)
+          return fail(h, YODA_ERR_RANGE,
+                      "a card field leaves the snapshot's 16-bit packing; re-upload the nodes");
+        if (h->q32 && max_small > kF32SmallMax)
+          return fail(h, YODA_ERR_RANGE,
+                      "a card field leaves the snapshot's f32 quotients; re-upload the nodes");
+        if (!h->q32 && !one)
+          return fail(h, YODA_ERR_RANGE,
+                      "a mixed-model node in a snapshot of wide one-model nodes; re-upload the nodes");
+        if ((uint64_t)K * (800u + max_ckq) >= (1ull << 32))
+          return fail(h, YODA_ERR_RANGE, "a clock quotient leaves the 32-bit path; re-upload the nodes");
+        for (uint32_t j = 0; j < nc; ++j) {
+          if (h->mem_ranks) {
+            const auto itf = std::lower_bound(h->h_frees.begin(), h->h_frees.end(), fr[j]);
+            const auto itt = std::lower_bound(h->h_totals.begin(), h->h_totals.end(), tot[j]);
+            if (itf == h->h_frees.end() || *itf != fr[j] || itt == h->h_totals.end() ||
+                *itt != tot[j])
+              return fail(h, YODA_ERR_RANGE,
+                          "memory value outside the snapshot's rank tables; re-upload the nodes");
+            fc[j] = 2u + (uint32_t)(itf - h->h_frees.begin());
+            tc[j] = 2u + (uint32_t)(itt - h->h_totals.begin());
+          } else {
+            if (fr[j] > kN32FieldMax || tot[j] > kN32FieldMax)
+              return fail(h, YODA_ERR_RANGE,
+                          "a memory field leaves the 32-bit path; re-upload the nodes");
+            fc[j] = (uint32_t)fr[j];
+            tc[j] = (uint32_t)tot[j];
+          }
+        }
+      } else if (h->path == Path::F64 && max_field > kFastFieldMax) {
+        return fail(h, YODA_ERR_RANGE, "a card field leaves the fast path; re-upload the nodes");
+      }
+      bool z = false;
+      const uint64_t alloc = recs->alloc_memory ? recs->alloc_memory[t] : 0;
+      const uint64_t s =
+          static_score(recs->free_memory_sum[t], recs->total_memory_sum[t], alloc, &z);
+      const long double cards = (long double)K * (800.0L + 100.0L * (long double)max_clock);
+      if (!h->generic && (s >= (1ull << 51) || cards + (long double)s >= (long double)kFastScoreMax))
+        return fail(h, YODA_ERR_RANGE, "a score leaves the fast path; re-upload the nodes");
+      stat[ti] = s;
+      // the upper bounds only grow (yoda_score_bound, yoda_small_field_max)
+      new_cards = std::max(new_cards, cards + 300.0L);
+      new_small = std::max(new_small, max_small);
+      if (recs->total_memory_sum[t] != 0)
+        new_actual = std::max(new_actual, recs->free_memory_sum[t] * 100u /
+                                              recs->total_memory_sum[t] * 2u);
+      // old record out, new record in: the G maxima of the present nodes
+      const bool absent = h->h_absent[i] != 0;
+      if (n32 && !absent) {
+        uint64_t m[6];
+        record_maxima(h, h->host_records.data() + (size_t)i * stride, m);
+        for (int f = 0; f < 6; ++f) lost |= m[f] == h->h_gmax[f] ? 1u << f : 0u;
+        const uint64_t* src[6] = {bw, ck, co, fr, pw, tot};  // MaxValue field order
+        for (int f = 0; f < 6; ++f)
+          for (uint32_t j = 0; j < nc; ++j) g[f] = std::max(g[f], src[f][j]);
+      }
+      NodePackIn in;
+      in.cnt = nc;
+      in.card_number = recs->card_number[t];
+      in.stat = s;
+      in.zero_total = z;
+      in.no_uniform = no_uniform;
+      in.absent = absent;
+      in.free_memory = fr;
+      in.total_memory = tot;
+      in.clock = ck;
+      in.bandwidth = bw;
+      in.core = co;
+      in.power = pw;
+      in.healthy = hl;
+      in.fcode = fc;
+      in.tcode = tc;
+      NodePackOut out;
+      packed_row_out(h, ti, row_words, out);
+      new_flags[ti] = pack_node(h->path, K, in, out);
+    }
+    // ---- the list passed: the one-model counts (old flags out, new in), then the rows onto the
+    // mirrors and the device, then the host copies ----
+    constexpr uint32_t kOne = kNodeUniform4 | kNodeUniformTotal;
+    for (uint32_t ti = 0; ti < cnt; ++ti) {
+      NodeHdrG hd;
+      std::memcpy(&hd, h->host_records.data() + (size_t)loc[ti] * stride, sizeof(hd));
+      h->n_one_model -= (hd.flags & kOne) == kOne;
+      h->n_uni4 -= (hd.flags & kNodeUniform4) != 0u;
+      h->n_one_model += (new_flags[ti] & kOne) == kOne;
+      h->n_uni4 += (new_flags[ti] & kNodeUniform4) != 0u;
+    }
+    h->all_one_model = h->n_one_model == h->n_nodes;
+    h->all_uni4 = h->n_uni4 == h->n_nodes;
+    h->draw_stage = 0;
+    h->diag_done = false;
+    h->k3_pending = false;
+    int rc = apply_packed_rows(h, loc, row_words);
+    if (rc) return rc;
+    for (uint32_t ti = 0; ti < cnt; ++ti) {
+      const uint32_t i = loc[ti], t = ent[ti];
+      h->h_total_sum[i] = recs->total_memory_sum[t];
+      h->h_free_sum[i] = recs->free_memory_sum[t];
+      h->h_card_number[i] = recs->card_number[t];
+      h->h_alloc[i] = recs->alloc_memory ? recs->alloc_memory[t] : 0;
+    }
+    h->small_max = new_small;
+    if (new_cards > h->sb_cards || new_actual > h->sb_actual) {
+      h->sb_cards = new_cards;
+      h->sb_actual = new_actual;
+      const long double b = new_cards + (long double)new_actual;
+      h->score_bound =
+          std::max<uint64_t>(h->score_bound, b < 9.0e18L ? (uint64_t)b + 1u : ~(uint64_t)0);
+    }
+    // the candidate tables' zero_total bits per block are read from the records
+    if (h->cand_classes && (rc = cand_rebuild_sums(h, false))) return rc;
+    if (h->nodes_diskio &&
+        (rc = push_node_metrics(h, cnt, loc.data(), ent.data(), recs->cpu, recs->disk_io)))
+      return rc;
+    if (!n32) return YODA_OK;
+    // A field whose holder was replaced is searched over the present nodes' new records, stopping
+    // at the first that still reaches the old maximum (yoda_set_node_present's scan).
+    for (int f = 0; f < 6; ++f) {
+      if (!((lost >> f) & 1u) || g[f] > h->h_gmax[f]) continue;
+      const uint64_t old = h->h_gmax[f];
+      uint64_t m = 1;
+      for (uint32_t n = 0; n < h->n_nodes && m < old; ++n) {
+        if (h->h_absent[n]) continue;
+        const unsigned char* r = h->host_records.data() + (size_t)n * stride;
+        NodeHdrG hd;
+        std::memcpy(&hd, r, sizeof(hd));
+        const uint32_t nc = (uint32_t)__builtin_popcount(hd.real_mask);
+        for (uint32_t j = 0; j < nc; ++j) m = std::max(m, rec_field(h, r, kMaxToCard[f], j));
+      }
+      g[f] = m;  // (m < old: the scan was whole; else a present node still reaches old)
+    }
+    return apply_gmax(h, g);
   } catch (const std::bad_alloc&) {
     h->upd_slot.clear();
     return fail(h, YODA_ERR_INVALID_ARG, "host allocation failed");

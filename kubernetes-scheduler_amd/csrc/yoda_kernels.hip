@@ -5863,6 +5863,35 @@ hipError_t launch_set_cards(unsigned char* nodes, uint32_t stride, const uint32_
   return hipGetLastError();
 }
 
+// Mode B's node inputs (yoda_update_node_metrics, yoda_replace_nodes): the staged NodeRecB
+// records -- V = Cpu / 100, U = DiskIO / 50, divided on the host by the expression the upload
+// uses, so the stored bits are the upload's -- over the Mode B records.  One thread per entry,
+// one 16-byte load and store each.  kDense: entry t is node t (the whole fleet after a scrape:
+// coalesced, no index load); else entry t is node node[t], each node listed once.
+template <bool kDense>
+__global__ __launch_bounds__(kBlock) void k_set_node_metrics(NodeRecB* __restrict__ nodes_b,
+                                                             const uint32_t* __restrict__ node,
+                                                             const NodeRecB* __restrict__ recs,
+                                                             uint32_t count, uint32_t n_nodes) {
+  const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+  if (t >= count) return;
+  const uint32_t n = kDense ? t : node[t];
+  if (n >= n_nodes) return;  // (the host lists local ids below n_nodes only)
+  nodes_b[n] = recs[t];
+}
+
+hipError_t launch_set_node_metrics(NodeRecB* nodes_b, const uint32_t* node, const NodeRecB* recs,
+                                   uint32_t count, uint32_t n_nodes, hipStream_t s) {
+  if (count == 0) return hipSuccess;
+  if (node)
+    hipLaunchKernelGGL(k_set_node_metrics<false>, pod_grid(count), dim3(kBlock), 0, s, nodes_b,
+                       node, recs, count, n_nodes);
+  else
+    hipLaunchKernelGGL(k_set_node_metrics<true>, pod_grid(count), dim3(kBlock), 0, s, nodes_b,
+                       node, recs, count, n_nodes);
+  return hipGetLastError();
+}
+
 // The block summaries (yoda_layout.h BlockSumWord) of one summary order from its DEVICE K1 / K2
 // summaries, K1 tiles and model rows: the one builder, run by yoda_upload_nodes, by
 // yoda_update_node_cards and again by yoda_snapshot_check (stored summaries against a fresh

@@ -143,6 +143,9 @@ hipError_t launch_set_cards(unsigned char* nodes, uint32_t stride, const uint32_
                             const uint32_t* rows, uint32_t row_words, uint32_t count, int K,
                             uint32_t* sum, uint32_t* sum2, uint32_t* mix, uint32_t* x1,
                             const PermCopy& pc, hipStream_t s);
+// Mode B's node records of the listed nodes (node == nullptr: of nodes 0 .. count - 1).
+hipError_t launch_set_node_metrics(NodeRecB* nodes_b, const uint32_t* node, const NodeRecB* recs,
+                                   uint32_t count, uint32_t n_nodes, hipStream_t s);
 hipError_t launch_bsum_build(int K, const uint32_t* sum, const uint32_t* sum2, const uint32_t* x1,
                              const uint32_t* mix, uint32_t n_nodes, uint32_t* bsum,
                              hipStream_t s);

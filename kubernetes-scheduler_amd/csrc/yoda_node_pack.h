@@ -2,7 +2,8 @@
 // its record, its K1 and K2 summary rows, its per-card model row and its K1 mixed tile.  Host
 // code without a HIP runtime call: yoda_upload_nodes packs every node with it,
 // yoda_update_node_cards the nodes whose card metrics changed, yoda_set_node_present the nodes
-// that left or returned, and tools/check_node_pack.cpp
+// that left or returned, yoda_replace_nodes the nodes whose whole record is the caller's, and
+// tools/check_node_pack.cpp
 // runs it under AddressSanitizer.  One packer, so the sparse path cannot drift from the upload;
 // what is derived from these rows (block summaries, G table) has one builder too, on the device
 // (k_bsum_build, k_gtable), which both callers run.

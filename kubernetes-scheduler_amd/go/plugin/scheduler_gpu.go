@@ -87,6 +87,7 @@ type Yoda struct {
 	alloc      []uint64 // allocated scv/memory per node as on the device
 	nodeGen    []int64  // framework.NodeInfo.Generation each alloc[i] was summed at (-1: none)
 	cardNumber []uint64
+	scvs       []*scv.Scv // the records as on the device (Mode A): applyDelta compares with them
 }
 
 // (reasons: nil in Mode B -- PreFilter)
@@ -289,12 +290,31 @@ func (y *Yoda) refresh() error {
 			}
 			cpu[i], disk[i] = ni.Cpu, ni.DiskIO
 		}
-		y.names = names
-		return y.gpu.UploadNodes(names, nil, nil, cpu, disk)
+		// the same nodes as uploaded: only the metrics moved (they do every cycle), and the
+		// handle keeps its absent nodes and candidate words; else a new snapshot
+		if y.loaded && sameNames(names, y.names) {
+			return y.gpu.UpdateNodeMetrics(nil, cpu, disk)
+		}
+		if err := y.gpu.UploadNodes(names, nil, nil, cpu, disk); err != nil {
+			return err
+		}
+		y.loaded, y.names = true, names
+		return nil
 	}
 	names, scvs, gen, err := y.source.SCVs()
 	if err != nil {
 		return err
+	}
+	if y.loaded && gen != y.gen && sameNames(names, y.names) {
+		// The records moved, the node set did not: card-only changes go to UpdateCards, static
+		// ones to ReplaceNodes (INTEGRATION.md §2); YODA_ERR_RANGE from either -- the uploaded
+		// format cannot hold a value, the handle is unchanged -- falls through to the upload.
+		err := y.applyDelta(scvs)
+		if err == nil {
+			y.gen, y.scvs = gen, scvs
+		} else if !yodagpu.IsRange(err) {
+			return err
+		}
 	}
 	if !y.loaded || gen != y.gen {
 		alloc, gens := y.allocated(names, nil, nil)
@@ -302,6 +322,7 @@ func (y *Yoda) refresh() error {
 			return err
 		}
 		y.loaded, y.gen, y.names, y.alloc, y.nodeGen = true, gen, names, alloc, gens
+		y.scvs = scvs
 		y.cardNumber = make([]uint64, len(scvs))
 		for i, s := range scvs {
 			y.cardNumber[i] = uint64(s.Status.CardNumber)
@@ -322,6 +343,98 @@ func (y *Yoda) refresh() error {
 		return err
 	}
 	y.alloc, y.nodeGen = alloc, gens
+	return nil
+}
+
+func sameNames(a, b []string) bool {
+	if len(a) != len(b) {
+		return false
+	}
+	for i := range a {
+		if a[i] != b[i] {
+			return false
+		}
+	}
+	return true
+}
+
+// staticChanged: the record differs from the uploaded one in a field UpdateCards does not carry
+// (the card count, TotalMemory[Sum], clock, bandwidth, core, power, CardNumber).
+func staticChanged(a, b *scv.Scv) bool {
+	if len(a.Status.CardList) != len(b.Status.CardList) ||
+		a.Status.TotalMemorySum != b.Status.TotalMemorySum || a.Status.CardNumber != b.Status.CardNumber {
+		return true
+	}
+	for j := range a.Status.CardList {
+		ca, cb := a.Status.CardList[j], b.Status.CardList[j]
+		if ca.TotalMemory != cb.TotalMemory || ca.Clock != cb.Clock || ca.Bandwidth != cb.Bandwidth ||
+			ca.Core != cb.Core || ca.Power != cb.Power {
+			return true
+		}
+	}
+	return false
+}
+
+func dynamicChanged(a, b *scv.Scv) bool {
+	if a.Status.FreeMemorySum != b.Status.FreeMemorySum {
+		return true
+	}
+	for j := range a.Status.CardList {
+		if a.Status.CardList[j].FreeMemory != b.Status.CardList[j].FreeMemory ||
+			a.Status.CardList[j].Health != b.Status.CardList[j].Health {
+			return true
+		}
+	}
+	return false
+}
+
+// applyDelta brings the device from the uploaded records (y.scvs) to scvs, same node order:
+// the nodes with a static change in one ReplaceNodes (their allocation as on the device), the
+// card-only ones in one UpdateCards.  Both validate before they write, and the replacement goes
+// first, so an error leaves at most accepted replacements behind, which the upload that follows
+// a range error overwrites.
+func (y *Yoda) applyDelta(scvs []*scv.Scv) error {
+	var rep, upd []uint32
+	for i := range scvs {
+		switch {
+		case staticChanged(y.scvs[i], scvs[i]):
+			rep = append(rep, uint32(i))
+		case dynamicChanged(y.scvs[i], scvs[i]):
+			upd = append(upd, uint32(i))
+		}
+	}
+	if len(rep) > 0 {
+		recs, alloc := make([]*scv.Scv, len(rep)), make([]uint64, len(rep))
+		for t, i := range rep {
+			recs[t], alloc[t] = scvs[i], y.alloc[i]
+		}
+		if err := y.gpu.ReplaceNodes(rep, recs, alloc, nil, nil); err != nil {
+			return err
+		}
+		for _, i := range rep {
+			y.cardNumber[i] = uint64(scvs[i].Status.CardNumber)
+		}
+	}
+	if len(upd) > 0 {
+		k := 1
+		for _, i := range upd {
+			if len(scvs[i].Status.CardList) > k {
+				k = len(scvs[i].Status.CardList)
+			}
+		}
+		free, healthy := make([]uint64, len(upd)*k), make([]uint8, len(upd)*k)
+		sum := make([]uint64, len(upd))
+		for t, i := range upd {
+			sum[t] = scvs[i].Status.FreeMemorySum
+			for j, c := range scvs[i].Status.CardList {
+				free[t*k+j] = c.FreeMemory
+				if c.Health == "Healthy" { // filter.go:53,57
+					healthy[t*k+j] = 1
+				}
+			}
+		}
+		return y.gpu.UpdateCards(upd, k, free, healthy, sum)
+	}
 	return nil
 }
 

@@ -118,6 +118,21 @@ type Handle struct {
 	pa        podArrays
 }
 
+// Error is a libyoda error code (include/yoda.h YODA_ERR_*) with the call that returned it.
+type Error struct {
+	Code int
+	msg  string
+}
+
+func (e *Error) Error() string { return e.msg }
+
+// IsRange reports whether err is YODA_ERR_RANGE: the uploaded snapshot's record format cannot
+// hold a new value, the handle is unchanged, and the caller uploads the snapshot again.
+func IsRange(err error) bool {
+	var e *Error
+	return errors.As(err, &e) && e.Code == int(C.YODA_ERR_RANGE)
+}
+
 func check(h *C.yoda_t, rc C.int, what string) error {
 	if rc == C.YODA_OK {
 		return nil
@@ -126,7 +141,7 @@ func check(h *C.yoda_t, rc C.int, what string) error {
 	if h != nil {
 		msg = C.GoString(C.yoda_last_error(h))
 	}
-	return fmt.Errorf("%s: libyoda error %d: %s", what, int(rc), msg)
+	return &Error{Code: int(rc), msg: fmt.Sprintf("%s: libyoda error %d: %s", what, int(rc), msg)}
 }
 
 // New opens a handle on GPU `device`.
@@ -330,6 +345,68 @@ func (g *Handle) UpdateCards(idx []uint32, maxCards int, free []uint64, healthy 
 		C.uint32_t(maxCards), (*C.uint64_t)(unsafe.Pointer(&free[0])),
 		(*C.uint8_t)(unsafe.Pointer(&healthy[0])), (*C.uint64_t)(unsafe.Pointer(&freeSum[0])))
 	return check(g.h, rc, "yoda_update_node_cards")
+}
+
+// ReplaceNodes replaces the WHOLE record of a few nodes on the device -- card count, CardNumber,
+// every card field, the memory sums, the allocation and, when the snapshot holds them, Mode B's
+// cpu / diskIO -- without re-uploading the snapshot (yoda_replace_nodes): a machine whose GPUs
+// were swapped, a changed card count or TotalMemory.  idx are snapshot positions; scvs[t] is the
+// new record of node idx[t]; allocMemory may be nil (0); cpu / diskIO as for UploadNodes.  A node
+// keeps its presence (SetNodePresent) and its candidate word.  New nodes take spare slots:
+// upload placeholder records with an empty CardList, take them out with SetNodePresent, and when
+// a node joins replace one and put it back (the node count itself never changes).  IsRange(err):
+// the record does not fit the format the upload chose; the handle is unchanged -- upload the
+// snapshot again.
+func (g *Handle) ReplaceNodes(idx []uint32, scvs []*scv.Scv, allocMemory []uint64,
+	cpu, diskIO []float64) error {
+	if len(idx) != len(scvs) || (allocMemory != nil && len(allocMemory) != len(idx)) {
+		return errors.New("yodagpu: ReplaceNodes arrays differ in length")
+	}
+	if len(idx) == 0 {
+		return nil
+	}
+	for _, i := range idx {
+		if int(i) >= len(g.nodes) {
+			return errors.New("yodagpu: ReplaceNodes position outside the snapshot")
+		}
+	}
+	soa, zero, err := g.na.pack(scvs, allocMemory, cpu, diskIO)
+	if err != nil {
+		return err
+	}
+	rc := C.yoda_replace_nodes(g.h, C.uint32_t(len(idx)), (*C.uint32_t)(unsafe.Pointer(&idx[0])),
+		&soa)
+	if err := check(g.h, rc, "yoda_replace_nodes"); err != nil {
+		return err
+	}
+	for t, i := range idx { // (a repeated position keeps its last entry, as on the device)
+		g.zeroTotal[i] = zero[t]
+	}
+	return nil
+}
+
+// UpdateNodeMetrics replaces Mode B's node inputs, NodeInfo.Cpu and NodeInfo.DiskIO (live
+// metrics the reference re-reads in every PreScore, scheduler.go:101-114), without re-uploading
+// the snapshot (yoda_update_node_metrics).  idx are snapshot positions with one cpu / diskIO
+// value each; idx == nil is the dense form: one value per node of the snapshot, in its order.
+// Absent nodes, candidate words and pod classes stay, and ModeBFollow's eligibility table is not
+// rebuilt.
+func (g *Handle) UpdateNodeMetrics(idx []uint32, cpu, diskIO []float64) error {
+	if len(cpu) != len(diskIO) || (idx != nil && len(idx) != len(cpu)) ||
+		(idx == nil && len(cpu) != len(g.nodes)) {
+		return errors.New("yodagpu: UpdateNodeMetrics arrays differ in length")
+	}
+	if len(cpu) == 0 {
+		return nil
+	}
+	var ip *C.uint32_t
+	if idx != nil {
+		ip = (*C.uint32_t)(unsafe.Pointer(&idx[0]))
+	}
+	// plain-number Go slices passed directly as arguments: allowed by the cgo rules
+	rc := C.yoda_update_node_metrics(g.h, C.uint32_t(len(cpu)), ip,
+		(*C.double)(unsafe.Pointer(&cpu[0])), (*C.double)(unsafe.Pointer(&diskIO[0])))
+	return check(g.h, rc, "yoda_update_node_metrics")
 }
 
 // SetNodePresent takes a few nodes out of the uploaded snapshot (present[i] == 0) or back in

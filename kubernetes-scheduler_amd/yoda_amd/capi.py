@@ -84,6 +84,8 @@ _SIGS = {
     "yoda_set_node_state": ([_vp, _u32, _vp, _vp, _vp], C.c_int),
     "yoda_update_node_cards": ([_vp, _u32, _vp, _u32, _vp, _vp, _vp], C.c_int),
     "yoda_set_node_present": ([_vp, _u32, _vp, _vp], C.c_int),
+    "yoda_replace_nodes": ([_vp, _u32, _vp, C.POINTER(CNodeSoA)], C.c_int),
+    "yoda_update_node_metrics": ([_vp, _u32, _vp, _vp, _vp], C.c_int),
     "yoda_nodes_absent": ([_vp, C.POINTER(C.c_uint32)], C.c_int),
     "yoda_set_candidates": ([_vp, _u32, _vp], C.c_int),
     "yoda_update_candidates": ([_vp, _u32, _vp, _vp], C.c_int),
@@ -522,6 +524,45 @@ class Yoda:
             raise ValueError("set_node_present: ids and present differ in length")
         self._check(lib().yoda_set_node_present(self._h, n.size, _np_ptr(n), _np_ptr(f)),
                     "yoda_set_node_present")
+
+    def replace_nodes(self, ids, nodes: NodeSoA):
+        """The WHOLE record of the listed GLOBAL node ids (others ignored), no re-upload
+        (yoda_replace_nodes): entry t of `nodes` (n_nodes == len(ids), its own max_cards) is the
+        new record of node ids[t] -- card count, every card field, the sums, the allocation, cpu /
+        disk_io.  The node keeps its presence bit and its candidate word; a repeated id keeps its
+        last entry.  New nodes take spare slots: placeholders with card_count 0 uploaded absent,
+        replaced and put back.  YodaError with code YODA_ERR_RANGE: the record does not fit the
+        format the upload chose -- the handle is unchanged; upload the snapshot again."""
+        n = np.ascontiguousarray(ids, np.uint32).ravel()
+        rec = nodes.normalized()
+        if rec.n_nodes != n.size:
+            raise ValueError("replace_nodes: ids and nodes differ in length")
+        if n.size == 0:
+            return
+        cn = rec.c()
+        self._check(lib().yoda_replace_nodes(self._h, n.size, _np_ptr(n), C.byref(cn)),
+                    "yoda_replace_nodes")
+
+    def update_node_metrics(self, ids, cpu, disk_io):
+        """Mode B's node inputs (NodeInfo.Cpu / DiskIO) without a re-upload
+        (yoda_update_node_metrics).  ids: GLOBAL node ids (others ignored, a repeated id keeps its
+        last entry) with one cpu / disk_io each; ids None: the dense form, entry i is local node i
+        and both arrays hold n_nodes values.  Presence, candidates and pod classes stay, and the
+        eligibility table of mode_b_follow is not rebuilt.  YodaError (YODA_ERR_STATE) when the
+        snapshot was uploaded without cpu / disk_io."""
+        c = np.ascontiguousarray(cpu, np.float64).ravel()
+        d = np.ascontiguousarray(disk_io, np.float64).ravel()
+        if c.size != d.size:
+            raise ValueError("update_node_metrics: cpu and disk_io differ in length")
+        if ids is None:
+            rc = lib().yoda_update_node_metrics(self._h, c.size, None, _np_ptr(c), _np_ptr(d))
+        else:
+            n = np.ascontiguousarray(ids, np.uint32).ravel()
+            if n.size != c.size:
+                raise ValueError("update_node_metrics: ids and metrics differ in length")
+            rc = lib().yoda_update_node_metrics(self._h, n.size, _np_ptr(n), _np_ptr(c),
+                                                _np_ptr(d))
+        self._check(rc, "yoda_update_node_metrics")
 
     @property
     def nodes_absent(self) -> int:

@@ -615,6 +615,16 @@ class HandleShard:
     def set_node_state(self, nodes, alloc, card_number):
         self.h.set_node_state(nodes, alloc, card_number)
 
+    def replace_nodes(self, ids, nodes):
+        """Whole node records by GLOBAL id (yoda_replace_nodes): every shard takes the same list
+        and keeps the ids of its own range."""
+        self.h.replace_nodes(ids, nodes)
+
+    def update_node_metrics(self, ids, cpu, disk_io):
+        """Mode B's cpu / disk_io by GLOBAL id (yoda_update_node_metrics); ids None: this
+        shard's nodes in order."""
+        self.h.update_node_metrics(ids, cpu, disk_io)
+
 
 def merge_topk(ts_list: Sequence[np.ndarray], ti_list: Sequence[np.ndarray], k: int):
     """The first k of the union of the shards' candidate lists ([k, P] each), in the lists'

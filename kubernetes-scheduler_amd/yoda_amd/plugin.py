@@ -112,6 +112,18 @@ class YodaPlugin:
     def name(self) -> str:
         return NAME
 
+    # ---- the live snapshot ---------------------------------------------------------------
+    def replace_nodes(self, ids, nodes: NodeSoA):
+        """Whole new records for the nodes at positions `ids` of node_names (the backend's
+        replace_nodes); Score's TotalMemorySum == 0 check follows the new records."""
+        self.backend.replace_nodes(ids, nodes)
+        self.zero_total[np.asarray(ids, np.int64)] = np.asarray(nodes.total_memory_sum) == 0
+
+    def update_node_metrics(self, ids, cpu, disk_io):
+        """Mode B's NodeInfo.Cpu / DiskIO of the nodes at positions `ids` (None: of every node,
+        in node_names order), as the backend's update_node_metrics takes them."""
+        self.backend.update_node_metrics(ids, cpu, disk_io)
+
     # ---- extension points ---------------------------------------------------------------
     def pre_filter(self, state: CycleState, pod: Mapping) -> Status:
         self.backend.upload_pods(pack_pods([pod]))

@@ -215,6 +215,52 @@ def card_delta(old: NodeSoA, new: NodeSoA):
 
 
 @dataclass
+class NodeDelta:
+    """node_delta's answer: which call carries which changed node."""
+    cards: tuple    # Yoda.update_cards(*cards): (ids, card_free_memory, card_healthy, free_memory_sum)
+    replace: tuple  # Yoda.replace_nodes(*replace): (ids, NodeSoA of those nodes)
+    metrics: tuple  # Yoda.update_node_metrics(*metrics): (ids, cpu, disk_io)
+
+
+def node_delta(old: NodeSoA, new: NodeSoA) -> Optional[NodeDelta]:
+    """What takes a handle uploaded with `old` to `new` without a re-upload, node by node, next
+    to card_delta.  A node with a changed static field (card count, TotalMemory[Sum], clock,
+    bandwidth, core, power) goes to `replace` with its whole new record -- CardNumber, the
+    allocation and cpu / disk_io ride along, so it is in no other list.  Of the others, a node
+    whose dynamic SCV metrics differ (a card's FreeMemory or Health, FreeMemorySum) goes to `cards`
+    and one whose cpu or disk_io differs to `metrics` (it may be in both).  CardNumber and the
+    allocated memory of the nodes that are not replaced are not its business, as for card_delta.
+    max_cards may differ (the unused slots are zeros).  None when n_nodes differs: upload `new`.
+    A replace_nodes that raises YODA_ERR_RANGE also means: upload `new`."""
+    a, b = old.normalized(), new.normalized()
+    if a.n_nodes != b.n_nodes:
+        return None
+    k = max(a.max_cards, b.max_cards)
+
+    def wide(x):
+        return np.pad(x, ((0, 0), (0, k - x.shape[1])))
+
+    static = (a.card_count != b.card_count) | (a.total_memory_sum != b.total_memory_sum)
+    for f in ("card_total_memory", "card_clock", "card_bandwidth", "card_core", "card_power"):
+        static |= (wide(getattr(a, f)) != wide(getattr(b, f))).any(axis=1)
+    moved = ((wide(a.card_free_memory) != wide(b.card_free_memory)).any(axis=1) |
+             (wide(a.card_healthy).astype(bool) != wide(b.card_healthy).astype(bool)).any(axis=1) |
+             (a.free_memory_sum != b.free_memory_sum))
+    # (bit patterns: a NaN metric that stays a NaN is no change)
+    scraped = ((a.cpu.view(np.uint64) != b.cpu.view(np.uint64)) |
+               (a.disk_io.view(np.uint64) != b.disk_io.view(np.uint64)))
+    rep = np.flatnonzero(static).astype(np.uint32)
+    ids = np.flatnonzero(moved & ~static).astype(np.uint32)
+    met = np.flatnonzero(scraped & ~static).astype(np.uint32)
+    return NodeDelta(
+        cards=(ids, np.ascontiguousarray(b.card_free_memory[ids]),
+               np.ascontiguousarray(b.card_healthy[ids]),
+               np.ascontiguousarray(b.free_memory_sum[ids])),
+        replace=(rep, b.take(rep)),
+        metrics=(met, np.ascontiguousarray(b.cpu[met]), np.ascontiguousarray(b.disk_io[met])))
+
+
+@dataclass
 class PodSoA:
     has_number: np.ndarray  # u8 [P]
     number: np.ndarray      # u64 [P]
