@@ -639,6 +639,68 @@ int yoda_candidates_info(const yoda_t* h, uint32_t* out);
 /* Diagnostic: the narrowing pass's time (HIP events, ms) summed over the runs that the
  * yoda_profile_read calls since the last call of this one have read (yoda_profile on). */
 int yoda_candidates_profile(yoda_t* h, double* narrow_ms);
+/* ---- Node sampling: score only the first numFeasibleNodesToFind nodes ----
+ * kube-scheduler v1.22.3 does not hand Score every feasible node (findNodesThatPassFilters /
+ * numFeasibleNodesToFind, generic_scheduler.go): it walks the node list from a rotating start
+ * index, stops Filter once num_to_find nodes have passed, and scores those.  Read at parallelism
+ * 1 (the deterministic stand-in, in the spirit of the lowest-node rule), for a pod p with
+ * F'(p) today's feasible set (present, Yoda's Filter, a candidate of the pod's class) and the
+ * rotated order the GLOBAL ids start[p], start[p] + 1, ..., node_offset + N - 1, node_offset,
+ * ..., start[p] - 1 (absent nodes skipped: they are not in the scheduler's list; start[p] may
+ * itself be absent):
+ *   S(p) = the first min(M, |F'|) nodes of F' in rotated order, M = num_to_find.
+ * The PreScore maxima do not move (CollectMaxValues walks every SCV).  Everything downstream of
+ * Filter follows S exactly as it follows F' without sampling: n_feasible = |S|, the
+ * single-feasible-node rule, UNSCHEDULABLE, DIV_ZERO (a zero-total node of S with |S| >= 2),
+ * NormalizeScore's highest and lowest, n_ties, top_score, the lowest-node pick, the draw of
+ * yoda_set_tie_draw, the feasibility bitmask, the raw and normalized rows (-1 outside S) and the
+ * U64 path's exact normalize.  n_found[p] = |F'(p)|, the count before the cut.  next_start[p]: if
+ * |F'| > M the GLOBAL id of the (M+1)-th node of F' in rotated order (the walk stops at it and
+ * does not count it, so the next cycle begins there), else start[p] as given (the walk went full
+ * circle).  A pod with M >= |F'| has the outputs it has without sampling.
+ *   Honoured by yoda_eval, yoda_run (with and without YODA_RUN_BITMASK), yoda_download,
+ * yoda_download_bitmask, yoda_score_rows and yoda_score_rows_norm in Mode A, with or without
+ * candidate classes, absent nodes and the draw.  While sampling is on, Mode B, yoda_greedy*, every
+ * yoda_shard_* and yoda_comm_* call that starts, advances or reads a step, yoda_reason_rows and
+ * yoda_diagnose with YODA_DIAG_ALL return YODA_ERR_STATE and do nothing else; the default
+ * yoda_diagnose works unchanged (a pod with |S| = 0 has |F'| = 0: every node was visited).  With
+ * sampling off nothing launches differently.
+ *   Out of scope, refused as above: sampling in yoda_greedy, on node shards and communicators and
+ * in Mode B; chaining next_start from pod to pod inside one batch (a sequential dependency: the
+ * caller feeds next_start into the NEXT batch's start); K1 stopping early once a pod's sample is
+ * full (the maxima need the whole sweep).
+ *   Cost: three launches after the Filter kernel and the narrowing pass (k_samp_count,
+ * k_samp_scan, k_samp_cut), no host round trip.  A sampled run reads the upload-order node tables
+ * (a mask position is then a node id), which costs the block-grouped order's speed and nothing
+ * else, and the K2 pruning seeds are off, as under candidates and for the same reason.  Measured
+ * at 100k pods x 100k nodes, config 3, M = 5000 and a uniform random start per pod
+ * (profiles/sampling/timing.txt): the step 0.38 ms with sampling never set (inside the parent's
+ * process-to-process spread), 0.91 ms with sampling on and nothing cut (M = N: the upload-order
+ * tables and the lost seeds), 2.72 ms sampled -- K1 0.37, the pass 1.27, K2 1.00 ms: a wave's 64
+ * pods keep 64 different stretches of the node list, so K2 finds almost no node whole -- and
+ * 3.73 ms with 8 candidate classes as well; yoda_set_node_sampling of 100,000 starts 0.06-0.10
+ * ms.  Sampling is for the deployed scheduler's picks, not a saving.  Unmeasured: starts shared
+ * inside a wave, the F64 / U64 paths, K other than 8. */
+/* Host only, 64-bit arithmetic: n_nodes when n_nodes < 100 or percentage >= 100; else with
+ * a = percentage, or max(5, 50 - n_nodes / 125) for percentage <= 0, max(n_nodes * a / 100, 100).
+ * (100000, 0) -> 5000; (5000, 0) -> 500; (4608, 0) -> 645. */
+uint32_t yoda_num_feasible_to_find(uint32_t n_nodes, int32_t percentage);
+/* num_to_find == 0 turns sampling off; so does yoda_upload_nodes.  start[n_pods]: GLOBAL ids in
+ * the caller's pod order; NULL: every pod starts at node_offset.  The array stays on the handle
+ * across uploads of pods, as the class array does; a run whose start array is neither empty nor
+ * as long as the uploaded batch returns YODA_ERR_STATE and launches nothing.  YODA_ERR_NO_NODES
+ * before an upload; YODA_ERR_RANGE for an id outside [node_offset, node_offset + n_nodes) -- the
+ * call validates before it writes.  Ordered on the handle's stream; invalidates pending run,
+ * phase-1, top-k, draw and diagnosis state. */
+int yoda_set_node_sampling(yoda_t* h, uint32_t num_to_find, uint32_t n_pods, const uint32_t* start);
+/* n_found[n_pods], next_start[n_pods] of the last run, caller order; either may be NULL.  Answers
+ * when yoda_download would, after a sampled run; otherwise YODA_ERR_STATE. */
+int yoda_download_sampling(yoda_t* h, uint32_t* n_found, uint32_t* next_start);
+/* Diagnostic, host only: out[3] = {num_to_find (0 = off), the length of the start array, 1 when
+ * the last run ran the sampling pass}. */
+int yoda_sampling_info(const yoda_t* h, uint32_t* out);
+/* Diagnostic: the sampling pass's time (HIP events, ms), as yoda_candidates_profile. */
+int yoda_sampling_profile(yoda_t* h, double* pass_ms);
 /* ---- yoda_greedy honours the candidate classes (opt-in) ----
  * enable != 0: yoda_greedy on this handle runs while candidates are on, each pod's cycle being
  * the candidate-class cycle above against the CURRENT node state of the batch (the assumes of

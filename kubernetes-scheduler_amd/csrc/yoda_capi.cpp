@@ -248,9 +248,19 @@ struct yoda_handle {
   // small batch (config 4: 10k pods x 20k nodes, K1 88 -> 143 us, the last tasks alone)
   // that tail outweighs the whole-block decisions, which win from 32k pods on (the config-4
   // generator at 100k x 100k: K1 0.52 -> 0.20 ms)
+  // (a sampled run reads the upload-order tables, so that a mask position is a node id)
   bool perm_run() const {
-    return perm_on && count_order && (all_one_model || n_work >= kGroupedMixedMinPods);
+    return perm_on && count_order && samp_m == 0 &&
+           (all_one_model || n_work >= kGroupedMixedMinPods);
   }
+  // yoda_set_node_sampling: samp_m != 0: on (num_to_find).  The pods' start ids (LOCAL, caller
+  // order; empty: every pod starts at node 0 of the shard) stay across pod uploads.  samp_scr:
+  // the pass's scratch; samp_zt: the upload order's zero_total bits per block, rebuilt by every
+  // sampled run; samp_out [2][n_pods]: n_found, next_start of the last sampled run (samp_ran).
+  uint32_t samp_m = 0;
+  std::vector<uint32_t> h_start;
+  DevBuf samp_start, samp_scr, samp_zt, samp_out;
+  bool samp_ran = false;
   static constexpr uint32_t kGroupedMixedMinPods = 32768;
   bool all_uni4 = false;       // every node: one GPU model (kNodeUniform4)
   std::vector<unsigned char> host_records;  // kept for alloc updates (greedy)
@@ -464,6 +474,8 @@ struct yoda_handle {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_k1, ev_k2;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_cand;  // around the narrowing pass
   double cand_ms = 0;  // ... summed by yoda_profile_read, handed out by yoda_candidates_profile
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_samp;  // around the sampling pass
+  double samp_ms = 0;  // ... likewise, handed out by yoda_sampling_profile
   size_t ev_used = 0;
 
   hipEvent_t next_event() {
@@ -913,8 +925,18 @@ int pods_complete(yoda_t* h) {
 // (yoda_set_node_present): while a node is absent its entry points refuse to run.
 // batch: the single-handle batch path (yoda_run, yoda_eval, the row calls, yoda_greedy), which
 // follows both once yoda_mode_b_follow is on; the shard and communicator calls keep refusing.
+// Node sampling cuts the Mode A batch path only (yoda_run, yoda_eval, the row calls): everything
+// else that evaluates refuses while it is on.
+int samp_refuse(yoda_t* h, const char* what) {
+  if (!h->samp_m) return YODA_OK;
+  return fail(h, YODA_ERR_STATE,
+              std::string(what) + " does not honour node sampling (yoda_set_node_sampling): "
+                                  "turn it off (num_to_find 0)");
+}
+
 int mode_b_absent(yoda_t* h, int mode, bool batch = false) {
   if (mode != YODA_MODE_DISKIO) return YODA_OK;
+  if (int rc = samp_refuse(h, "Mode B")) return rc;
   if (batch && h->b_follow) return YODA_OK;
   if (h->cand_classes)
     return fail(h, YODA_ERR_STATE,
@@ -932,6 +954,8 @@ int mode_b_absent(yoda_t* h, int mode, bool batch = false) {
 // on (phase 1 narrows the masks and counts whichever entry point called it; Mode B on shards
 // keeps refusing through mode_b_absent).
 int cand_refuse(yoda_t* h, const char* what, bool step = false) {
+  // (every caller is a greedy, shard or communicator entry point: none of them samples)
+  if (int rc = samp_refuse(h, what)) return rc;
   if (!h->cand_classes || (step && h->shard_cand)) return YODA_OK;
   return fail(h, YODA_ERR_STATE,
               std::string(what) + " does not honour candidate classes (yoda_set_candidates): "
@@ -948,6 +972,13 @@ int cand_ready(yoda_t* h) {
   return YODA_OK;
 }
 
+// A batch run with sampling on: the start array is empty or fits the uploaded batch.
+int samp_ready(yoda_t* h) {
+  if (h->samp_m && !h->h_start.empty() && h->h_start.size() != h->n_pods)
+    return fail(h, YODA_ERR_STATE, "yoda_set_node_sampling: the start array's length is not n_pods");
+  return YODA_OK;
+}
+
 int check_ready(yoda_t* h, int mode, bool batch = false) {
   if (!h) return YODA_ERR_INVALID_ARG;
   if (mode != YODA_MODE_SCV && mode != YODA_MODE_DISKIO)
@@ -958,6 +989,7 @@ int check_ready(yoda_t* h, int mode, bool batch = false) {
     return fail(h, YODA_ERR_INVALID_ARG, "Mode B needs node cpu/disk_io and pod rio/rcpu");
   if (int rc = mode_b_absent(h, mode, batch)) return rc;
   if (int rc = cand_ready(h)) return rc;
+  if (int rc = samp_ready(h)) return rc;
   HIP_TRY(h, hipSetDevice(h->device));
   return h->fast_run ? YODA_OK : pods_complete(h);
 }
@@ -1394,12 +1426,55 @@ int cand_narrow(yoda_t* h, uint32_t* counts, uint32_t P, bool pr) {
   return YODA_OK;
 }
 
+// The sampling pass after a phase 1's reduce and narrowing (sampling on): the masks and counts
+// [2][P] from F' to each pod's sample S, n_found and next_start into samp_out.  The run read the
+// upload-order tables (perm_run() is false), so a mask position is a local node id.
+int samp_pass(yoda_t* h, uint32_t* counts, uint32_t P) {
+  const uint32_t N = h->n_nodes;
+  SampArgs a{};
+  a.start = h->h_start.empty() ? nullptr : h->samp_start.as<uint32_t>();
+  a.perm = h->ordered ? h->perm.as<uint32_t>() : nullptr;
+  a.num_to_find = h->samp_m;
+  a.node_offset = h->node_offset;
+  a.n_nodes = N;
+  a.n_work = P;
+  a.bm = h->bitmask.as<uint64_t>();
+  a.bs = h->bm_sparse ? h->bsum.as<BlockMask>() : nullptr;
+  a.blk = h->bm_sparse ? h->blk.as<uint64_t>() : nullptr;
+  a.bm_stride = bm_row(N);
+  a.bs_stride = bs_row(N);
+  a.blk_stride = blk_row(N);
+  a.counts = counts;
+  HIP_TRY(h, h->samp_scr.ensure(samp_scratch_words(P, N) * 4));
+  HIP_TRY(h, h->samp_zt.ensure(std::max<size_t>((N + 63u) / 64u, 1) * 8));
+  HIP_TRY(h, h->samp_out.ensure(2 * (size_t)std::max<uint32_t>(h->n_pods, 1) * 4));
+  samp_scratch(a, h->samp_scr.as<uint32_t>());
+  a.zt = h->samp_zt.as<uint64_t>();
+  a.n_found = h->samp_out.as<uint32_t>();
+  a.next_start = a.n_found + h->n_pods;
+  hipEvent_t c0 = h->profiling ? h->next_event() : nullptr;
+  hipEvent_t c1 = h->profiling ? h->next_event() : nullptr;
+  if (c0) HIP_TRY(h, hipEventRecord(c0, h->stream));
+  // (the zero_total bits follow yoda_replace_nodes: read from the records by every sampled run)
+  HIP_TRY(h, launch_samp_zt(h->nodes.as<unsigned char>(),
+                            h->path == Path::N32 ? n32_stride(h->K) : node_stride(h->K), N,
+                            h->samp_zt.as<uint64_t>(), h->stream));
+  HIP_TRY(h, launch_samp_pass(a, h->stream));
+  if (c1) {
+    HIP_TRY(h, hipEventRecord(c1, h->stream));
+    h->ev_samp.emplace_back(c0, c1);
+  }
+  h->samp_ran = true;
+  return YODA_OK;
+}
+
 // Phase 1: Filter + PreScore maxima (Mode A), or the all-feasible state (Mode B).
 int phase1(yoda_t* h, int mode, uint64_t* maxima, uint32_t* counts,
            Maxima whose = Maxima::Exchanged) {
   const bool final_maxima = whose == Maxima::OwnFinal;
   h->seeds_valid = false;  // (set again below when this run's block K1 writes them)
   h->rcp_ready = false;
+  h->samp_ran = false;
   const uint32_t P = h->n_work;  // sorted positions of this run
   if (P == 0) return YODA_OK;
   if (mode == YODA_MODE_DISKIO) {
@@ -1417,7 +1492,7 @@ int phase1(yoda_t* h, int mode, uint64_t* maxima, uint32_t* counts,
     HIP_TRY(h, hipMemcpyAsync(maxima, ones.data(), ones.size() * 8, hipMemcpyHostToDevice,
                               h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return YODA_OK;
+    return h->samp_m ? samp_pass(h, counts, P) : YODA_OK;
   }
   Partials part = partials(h);
   hipEvent_t e0 = h->profiling ? h->next_event() : nullptr;
@@ -1426,7 +1501,8 @@ int phase1(yoda_t* h, int mode, uint64_t* maxima, uint32_t* counts,
   h->bm_sparse = h->has_k1sum;  // the block K1 writes the sparse form
   // (candidates on: no seed -- it is a best over every node of an ALL block, and may sit above
   // the best of a pod's candidates)
-  h->seeds_valid = h->has_k1sum && mode == YODA_MODE_SCV && !h->cand_classes;
+  // (sampling on: likewise -- the best of an ALL block may sit above the best of a pod's sample)
+  h->seeds_valid = h->has_k1sum && mode == YODA_MODE_SCV && !h->cand_classes && !h->samp_m;
   h->blk_fresh = h->has_k1sum;  // (the memset below or the order scatter clears it whole)
   if (h->blk_valid && !h->blk_zeroed)  // (the list and the seeds after it)
     HIP_TRY(h, hipMemsetAsync(h->blk.p, 0, blk_words(h, P) * 8, h->stream));
@@ -1486,7 +1562,10 @@ int phase1(yoda_t* h, int mode, uint64_t* maxima, uint32_t* counts,
   h->lpt_sorted = h->lpt_active;  // (the order of this run's pod blocks, for phase 2)
   h->rcp_ready = rcp;
   // the masks and counts from Yoda's Filter to every plugin's
-  if (h->cand_classes) return cand_narrow(h, counts, P, pr);
+  if (h->cand_classes)
+    if (int rc = cand_narrow(h, counts, P, pr)) return rc;
+  // ... and from F' to the sample of each pod's walk
+  if (h->samp_m) return samp_pass(h, counts, P);
   return YODA_OK;
 }
 
@@ -2488,6 +2567,9 @@ int yoda_upload_nodes(yoda_t* h, const yoda_node_soa* nd, uint32_t node_offset, 
     h->n_absent = 0;
     h->cand_classes = 0;  // ... and a candidate of every pod (yoda_set_candidates: off)
     h->h_cand.clear();
+    h->samp_m = 0;  // ... and every feasible node is scored (yoda_set_node_sampling: off)
+    h->h_start.clear();
+    h->samp_ran = false;
     h->b_elig_dirty = true;  // (Mode B's eligibility table is the old snapshot's)
     h->b_elig_builds = 0;
     h->nodes_diskio = diskio;
@@ -3202,6 +3284,9 @@ static DiagArgs diag_args(yoda_t* h) {
 int yoda_diagnose(yoda_t* h, uint32_t flags) {
   if (!h) return YODA_ERR_INVALID_ARG;
   if (flags & ~YODA_DIAG_ALL) return fail(h, YODA_ERR_INVALID_ARG, "yoda_diagnose: unknown flag bits");
+  // (the default selection -- the pods with no feasible node -- had every node visited)
+  if (flags & YODA_DIAG_ALL)
+    if (int rc = samp_refuse(h, "yoda_diagnose with YODA_DIAG_ALL")) return rc;
   if (!h->ran || !h->has_nodes || !h->has_pods)
     return fail(h, YODA_ERR_STATE, "yoda_diagnose: no completed run is pending");
   if (h->k3_pending)
@@ -3255,8 +3340,11 @@ int yoda_download_diagnosis(yoda_t* h, uint32_t* counts, uint64_t n_counts) {
 }
 
 int yoda_reason_rows(yoda_t* h, uint8_t* reasons, uint64_t n_reasons) {
-  int rc = check_ready(h, YODA_MODE_SCV, true);
+  if (!h) return YODA_ERR_INVALID_ARG;
+  // (a node past the cut was never visited: it has no Filter verdict to report)
+  int rc = samp_refuse(h, "yoda_reason_rows");
   if (rc) return rc;
+  if ((rc = check_ready(h, YODA_MODE_SCV, true))) return rc;
   if (!reasons) return fail(h, YODA_ERR_INVALID_ARG, "NULL reasons buffer");
   const uint32_t P = h->n_pods, N = h->n_nodes;
   if (n_reasons != (uint64_t)P * N)
@@ -3689,12 +3777,18 @@ int yoda_profile_read(yoda_t* h, double* k1_ms, double* k2_ms, uint32_t* n_launc
     HIP_TRY(h, hipEventElapsedTime(&ms, pr.first, pr.second));
     h->cand_ms += ms;
   }
+  for (auto& pr : h->ev_samp) {
+    float ms = 0;
+    HIP_TRY(h, hipEventElapsedTime(&ms, pr.first, pr.second));
+    h->samp_ms += ms;
+  }
   if (k1_ms) *k1_ms = t1;
   if (k2_ms) *k2_ms = t2;
   if (n_launches) *n_launches = (uint32_t)h->ev_k2.size();
   h->ev_k1.clear();
   h->ev_k2.clear();
   h->ev_cand.clear();
+  h->ev_samp.clear();
   h->ev_used = 0;
   return YODA_OK;
 }
@@ -3881,6 +3975,7 @@ int yoda_greedy(yoda_t* h, const yoda_pod_soa* pods, int mode, uint32_t flags, i
   if (!h) return YODA_ERR_INVALID_ARG;
   if (!pods || !pick) return fail(h, YODA_ERR_INVALID_ARG, "NULL pods or pick");
   if (!h->has_nodes) return fail(h, YODA_ERR_NO_NODES, "no node snapshot uploaded");
+  if (int rc = samp_refuse(h, "yoda_greedy")) return rc;
   if (!h->greedy_cand)
     if (int rc = cand_refuse(h, "yoda_greedy")) return rc;
   if (int rc = mode_b_absent(h, mode, true)) return rc;
@@ -4966,6 +5061,89 @@ int yoda_candidates_info(const yoda_t* h, uint32_t* out) {
   return YODA_OK;
 }
 
+uint32_t yoda_num_feasible_to_find(uint32_t n_nodes, int32_t percentage) {
+  // numFeasibleNodesToFind (generic_scheduler.go, k8s v1.22.3): minFeasibleNodesToFind = 100,
+  // minFeasibleNodesPercentageToFind = 5, the adaptive default 50 - n / 125
+  const int64_t n = n_nodes;
+  if (n < 100 || percentage >= 100) return n_nodes;
+  int64_t a = percentage;
+  if (a <= 0) a = std::max<int64_t>(5, 50 - n / 125);
+  return (uint32_t)std::max<int64_t>(n * a / 100, 100);
+}
+
+int yoda_set_node_sampling(yoda_t* h, uint32_t num_to_find, uint32_t n_pods,
+                           const uint32_t* start) {
+  if (!h) return YODA_ERR_INVALID_ARG;
+  auto invalidate = [&]() {
+    cand_invalidate(h);
+    h->diag_done = false;
+    h->ran_bitmask = false;
+    h->samp_ran = false;
+  };
+  if (num_to_find == 0) {
+    if (h->samp_m) invalidate();
+    h->samp_m = 0;
+    h->h_start.clear();
+    return YODA_OK;
+  }
+  if (!h->has_nodes) return fail(h, YODA_ERR_NO_NODES, "no node snapshot uploaded");
+  if (!start) n_pods = 0;
+  for (uint32_t p = 0; p < n_pods; ++p)
+    if (start[p] < h->node_offset || start[p] - h->node_offset >= h->n_nodes)
+      return fail(h, YODA_ERR_RANGE, "yoda_set_node_sampling: a start id is outside the shard");
+  try {
+    HIP_TRY(h, hipSetDevice(h->device));
+    std::vector<uint32_t> loc(n_pods);
+    for (uint32_t p = 0; p < n_pods; ++p) loc[p] = start[p] - h->node_offset;
+    if (n_pods) {
+      HIP_TRY(h, h->samp_start.ensure((size_t)n_pods * 4));
+      HIP_TRY(h, hipMemcpyAsync(h->samp_start.p, loc.data(), (size_t)n_pods * 4,
+                                hipMemcpyHostToDevice, h->stream));
+      HIP_TRY(h, hipStreamSynchronize(h->stream));  // (the copy's source is pageable)
+    }
+    invalidate();
+    h->h_start.swap(loc);
+    h->samp_m = num_to_find;
+    return YODA_OK;
+  } catch (const std::bad_alloc&) {
+    return fail(h, YODA_ERR_INVALID_ARG, "host allocation failed");
+  } catch (...) {
+    return fail(h, YODA_ERR_INVALID_ARG, "unexpected exception");
+  }
+}
+
+int yoda_download_sampling(yoda_t* h, uint32_t* n_found, uint32_t* next_start) {
+  if (!h) return YODA_ERR_INVALID_ARG;
+  if (!h->ran || h->k3_pending || !h->samp_m || h->last_mode != YODA_MODE_SCV ||
+      !(h->samp_ran || h->n_pods == 0))
+    return fail(h, YODA_ERR_STATE, "yoda_download_sampling before a sampled yoda_run");
+  const uint32_t P = h->n_pods;
+  if (P == 0) return YODA_OK;
+  HIP_TRY(h, hipSetDevice(h->device));
+  const uint32_t* d = h->samp_out.as<uint32_t>();
+  if (n_found)
+    HIP_TRY(h, hipMemcpyAsync(n_found, d, (size_t)P * 4, hipMemcpyDeviceToHost, h->stream));
+  if (next_start)
+    HIP_TRY(h, hipMemcpyAsync(next_start, d + P, (size_t)P * 4, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return YODA_OK;
+}
+
+int yoda_sampling_info(const yoda_t* h, uint32_t* out) {
+  if (!h || !out) return YODA_ERR_INVALID_ARG;
+  out[0] = h->samp_m;
+  out[1] = (uint32_t)h->h_start.size();
+  out[2] = h->samp_ran ? 1u : 0u;
+  return YODA_OK;
+}
+
+int yoda_sampling_profile(yoda_t* h, double* pass_ms) {
+  if (!h || !pass_ms) return YODA_ERR_INVALID_ARG;
+  *pass_ms = h->samp_ms;
+  h->samp_ms = 0;
+  return YODA_OK;
+}
+
 int yoda_snapshot_check(yoda_t* h, uint64_t* digest, uint32_t* mismatch) {
   if (!h) return YODA_ERR_INVALID_ARG;
   if (!h->has_nodes) return fail(h, YODA_ERR_NO_NODES, "no node snapshot uploaded");
@@ -5854,6 +6032,8 @@ static int comm_step(yoda_t* const* hs, int n, int world, int mode, bool local, 
   for (int i = 0; i < n; ++i) {  // (before any shard's run is prepared)
     // candidates on: only the evaluation step, with yoda_shard_candidates on, in Mode A and with
     // a class array that fits the batch; checked on every shard before any of them launches
+    if (hs[i]->samp_m)
+      return fail(h0, samp_refuse(hs[i], "yoda_comm_run"), hs[i]->last_error);
     if (hs[i]->cand_classes) {
       int rc = cand_refuse(hs[i], "yoda_comm_run", draw);
       if (!rc && mode == YODA_MODE_DISKIO) rc = mode_b_absent(hs[i], mode);
@@ -6233,7 +6413,7 @@ static int comm_greedy(yoda_t* const* hs, int n, int world, bool local, const yo
   for (int i = 0; i < n; ++i)
     if (!hs[i]->has_nodes) return fail(h0, YODA_ERR_NO_NODES, "no node snapshot uploaded");
   for (int i = 0; i < n; ++i) {
-    if (hs[i]->cand_classes)
+    if (hs[i]->cand_classes || hs[i]->samp_m)
       return fail(h0, cand_refuse(hs[i], "yoda_comm_greedy"), hs[i]->last_error);
     if (hs[i]->n_absent && mode == YODA_MODE_DISKIO)
       return fail(h0, mode_b_absent(hs[i], mode), hs[i]->last_error);

@@ -5348,6 +5348,230 @@ __global__ __launch_bounds__(kWave) void k_cand_narrow(const CandArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------
+// Node sampling (yoda_set_node_sampling; DESIGN.md §5 "Node sampling").
+//
+// The sample S(p) is the first min(M, |F'|) nodes of F' in the pod's rotated order: local ids
+// start, start + 1, ..., N - 1, 0, ..., start - 1.  The pass runs after the narrowing pass, on
+// masks in the upload order (position = local id), in three launches: count, scan, cut.  One
+// wave per (pod wave, window of 64 node blocks) in count and cut, lane = node when a block's 64
+// mask words are read or written, lane = pod after wave_transpose64; one thread per pod in scan.
+// Integer only; a pod's outputs depend on its own mask, start and M and on nothing else, so
+// neither the chunking nor the batch's order shows in them.  A padding position of the counting
+// order is a copy of its pod, start included: it writes what the pod writes.
+
+// The zero_total bits of the upload order's blocks (k_cand_build's zt without a word table).
+__global__ __launch_bounds__(kWave) void k_samp_zt(const unsigned char* __restrict__ nodes,
+                                                   uint32_t stride, uint32_t n_nodes,
+                                                   uint64_t* __restrict__ zt) {
+  const uint32_t b = blockIdx.x, n = 64u * b + threadIdx.x;
+  const bool z = n < n_nodes &&
+                 reinterpret_cast<const NodeHdrG*>(nodes + (size_t)n * stride)->zero_total != 0u;
+  const uint64_t zb = ballot(z);
+  if (threadIdx.x == 0) zt[b] = zb;
+}
+
+// The position of the set bit of x with rank r (0-based); r < popcount(x).
+__device__ __forceinline__ uint32_t select64(uint64_t x, uint32_t r) {
+  uint32_t t = 0;
+#pragma unroll
+  for (uint32_t s = 32u; s >= 1u; s >>= 1) {
+    const uint32_t c = (uint32_t)__builtin_popcountll((x >> t) & ((1ull << s) - 1ull));
+    if (r >= c) {
+      r -= c;
+      t += s;
+    }
+  }
+  return t;
+}
+// The k lowest set bits of x (all of them when it has at most k).
+__device__ __forceinline__ uint64_t keep_lowest(uint64_t x, uint32_t k) {
+  if (k >= (uint32_t)__builtin_popcountll(x)) return x;
+  return x & ((1ull << select64(x, k)) - 1ull);
+}
+// Lane = node: the mask word of node 64 b + lane of a LISTED block, dense or sparse form.
+__device__ __forceinline__ uint64_t samp_word(const SampArgs& a, uint32_t w, uint32_t b,
+                                              uint32_t lane, uint64_t live) {
+  const uint32_t n = 64u * b + lane;
+  if (n >= a.n_nodes) return 0ull;
+  const uint64_t* bmw = a.bm + (size_t)w * a.bm_stride;
+  if (a.bs) {
+    const BlockMask bk = a.bs[(size_t)w * a.bs_stride + b];
+    if ((bk.full >> lane) & 1ull) return live;
+    return ((bk.nz >> lane) & 1ull) ? bmw[n] & live : 0ull;
+  }
+  return bmw[n] & live;
+}
+// The listed real blocks of window `win` of wave w (dense form: every real block).
+__device__ __forceinline__ uint64_t samp_listed(const SampArgs& a, uint32_t w, uint32_t win,
+                                                uint32_t NB) {
+  const uint32_t left = NB - 64u * win;  // (> 0: the caller returned for a window past NB)
+  const uint64_t real = left >= 64u ? ~0ull : (1ull << left) - 1ull;
+  if (!a.bs) return real;
+  return uniform_u64(a.blk[(size_t)w * a.blk_stride + win]) & real;
+}
+__device__ __forceinline__ uint32_t samp_start(const SampArgs& a, uint32_t p) {
+  return a.start ? a.start[a.perm ? a.perm[p] : p] : 0u;
+}
+
+// Count.  wc[w][win][lane]: the pod's F' nodes in the window; for the pods whose start lies in
+// the window, tail[p]: those at or after start.  A wave whose pods all have |F'| <= M is skipped
+// here and in the cut (the scan never reads its counts).
+__global__ __launch_bounds__(kWave) void k_samp_count(const SampArgs a) {
+  const Tile tl = tile();
+  const uint32_t w = tl.pb, win = tl.chunk, lane = threadIdx.x;
+  const uint32_t NB = (a.n_nodes + 63u) >> 6;
+  if (64u * win >= NB) return;
+  const uint32_t p = 64u * w + lane;
+  const bool in = p < a.n_work;
+  if (ballot(in && a.counts[p] > a.num_to_find) == 0ull) return;
+  const uint64_t live = wave_live(w, a.n_work);
+  const uint32_t s = in ? samp_start(a, p) : 0u;
+  const bool mine = in && (s >> kSampWindowLog2) == win;
+  const uint32_t sb = s >> 6;
+  uint32_t c = 0, ct = 0;
+  for (uint64_t todo = samp_listed(a, w, win, NB); todo; todo &= todo - 1ull) {
+    const uint32_t b = 64u * win + (uint32_t)__builtin_ctzll(todo);
+    const uint64_t x = wave_transpose64(samp_word(a, w, b, lane, live), lane);
+    c += (uint32_t)__builtin_popcountll(x);
+    if (mine && b >= sb) ct += (uint32_t)__builtin_popcountll(b == sb ? x >> (s & 63u) : x);
+  }
+  a.wc[((size_t)w * gridDim.y + win) * 64u + lane] = c;
+  if (mine) a.tail[p] = ct;
+}
+
+// Scan.  Per pod: n_found, next_start and tot; for a pod above M the walk over its windows in
+// rotated order -- the start window's tail, the windows after it, those before it, the start
+// window's head -- which turns each count into the quota of the sample there, finds the
+// (window, rank) of the (M+1)-th node, and sets counts[0] = M and counts[1] = 0 (the cut
+// recounts it over S).  A pod at or below M in a wave that is cut keeps every node: its quotas
+// are its counts.  n_win: real windows; row: the window stride of wc.
+__global__ __launch_bounds__(kBlock) void k_samp_scan(const SampArgs a, uint32_t n_win,
+                                                      uint32_t row) {
+  const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+  const bool in = p < a.n_work;
+  const uint32_t M = a.num_to_find;
+  const uint32_t cnt = in ? a.counts[p] : 0u;
+  const bool over = cnt > M;
+  const bool wave_over = ballot(over) != 0ull;
+  if (!in) return;
+  const uint32_t q = a.perm ? a.perm[p] : p;
+  const uint32_t s = a.start ? a.start[q] : 0u;
+  a.n_found[q] = cnt;
+  a.tot[p] = cnt;
+  a.nxt[p] = ~0u;
+  if (!over) a.next_start[q] = a.node_offset + s;
+  if (!wave_over) return;
+  const uint32_t sw = s >> kSampWindowLog2;
+  uint32_t* col = a.wc + (size_t)(p >> 6) * row * 64u + (p & 63u);
+  const uint32_t tc = a.tail[p], hc = col[(size_t)sw * 64u] - tc;
+  if (!over) {
+    col[(size_t)sw * 64u] = tc;
+    a.tail[p] = hc;
+    return;
+  }
+  a.counts[p] = M;
+  a.counts[a.n_work + p] = 0u;
+  uint32_t rem = M, seen = 0, nw = ~0u, nr = 0;
+  // one segment of the walk: c nodes of F' in window `win`, the first of rank `base` there
+  auto seg = [&](uint32_t c, uint32_t base, uint32_t win) {
+    const uint32_t take = min(rem, c);
+    if (nw == ~0u && seen + c > M) {
+      nw = win;
+      nr = base + (M - seen);
+    }
+    seen += c;
+    rem -= take;
+    return take;
+  };
+  const uint32_t qt = seg(tc, hc, sw);
+  for (uint32_t k = 1; k < n_win; ++k) {
+    const uint32_t win = sw + k < n_win ? sw + k : sw + k - n_win;
+    col[(size_t)win * 64u] = seg(col[(size_t)win * 64u], 0u, win);
+  }
+  const uint32_t qh = seg(hc, 0u, sw);
+  col[(size_t)sw * 64u] = qt;
+  a.tail[p] = qh;
+  a.nxt[p] = nw;
+  a.nxt[a.n_work + p] = nr;
+}
+
+// Cut.  Per listed block of the window: the pods' node bits, each pod's first `quota` of them
+// kept (in the start's own window the head before start and the tail from it on have a quota
+// each), transposed back; the sparse invariants as k_cand_narrow keeps them.  counts[1] is
+// recounted over S for the pods above M; the window that holds a pod's (M+1)-th node writes its
+// next_start.  A window past every pod's cut clears whole blocks without transposing.
+__global__ __launch_bounds__(kWave) void k_samp_cut(const SampArgs a) {
+  const Tile tl = tile();
+  const uint32_t w = tl.pb, win = tl.chunk, lane = threadIdx.x;
+  const uint32_t NB = (a.n_nodes + 63u) >> 6;
+  if (64u * win >= NB) return;
+  const uint32_t p = 64u * w + lane;
+  const bool in = p < a.n_work;
+  const bool over = in && a.tot[p] > a.num_to_find;
+  if (ballot(over) == 0ull) return;
+  const uint64_t listed = samp_listed(a, w, win, NB);
+  if (listed == 0ull) return;
+  const uint64_t live = wave_live(w, a.n_work);
+  const uint32_t s = in ? samp_start(a, p) : 0u;
+  const bool mine = in && (s >> kSampWindowLog2) == win;
+  const uint32_t split = mine ? s - (win << kSampWindowLog2) : 0u;  // head: positions below it
+  uint32_t qt = in ? a.wc[((size_t)w * gridDim.y + win) * 64u + lane] : 0u;
+  uint32_t qh = mine ? a.tail[p] : 0u;
+  const bool has_next = over && a.nxt[p] == win;
+  const uint32_t nr = has_next ? a.nxt[a.n_work + p] : 0u;
+  uint64_t* bmw = a.bm + (size_t)w * a.bm_stride;
+  unsigned long long* blkw =
+      a.bs ? reinterpret_cast<unsigned long long*>(a.blk) + (size_t)w * a.blk_stride + win
+           : nullptr;
+  if (ballot((qt | qh) != 0u || has_next) == 0ull) {
+    for (uint64_t todo = listed; todo; todo &= todo - 1ull) {
+      const uint32_t b = 64u * win + (uint32_t)__builtin_ctzll(todo), n = 64u * b + lane;
+      if (a.bs) {
+        if (lane == 0) a.bs[(size_t)w * a.bs_stride + b] = BlockMask{0ull, 0ull};
+      } else if (n < a.n_nodes) {
+        bmw[n] = 0ull;
+      }
+    }
+    if (blkw && lane == 0) atomicAnd(blkw, ~(unsigned long long)listed);
+    return;
+  }
+  uint32_t dz = 0, seen = 0;
+  for (uint64_t todo = listed; todo; todo &= todo - 1ull) {
+    const uint32_t j = (uint32_t)__builtin_ctzll(todo);
+    const uint32_t b = 64u * win + j, n = 64u * b + lane;
+    const uint64_t old = samp_word(a, w, b, lane, live);
+    const uint64_t x = wave_transpose64(old, lane);
+    const uint32_t lo = 64u * j;  // the block's first position in the window
+    const uint64_t hm = split <= lo ? 0ull : split - lo >= 64u ? ~0ull : (1ull << (split - lo)) - 1ull;
+    const uint64_t kh = keep_lowest(x & hm, qh), kt = keep_lowest(x & ~hm, qt);
+    qh -= (uint32_t)__builtin_popcountll(kh);
+    qt -= (uint32_t)__builtin_popcountll(kt);
+    const uint64_t keep = kh | kt;
+    if (has_next) {
+      const uint32_t c = (uint32_t)__builtin_popcountll(x);
+      if (nr >= seen && nr - seen < c)
+        a.next_start[a.perm ? a.perm[p] : p] = a.node_offset + 64u * b + select64(x, nr - seen);
+      seen += c;
+    }
+    if (over) dz += (uint32_t)__builtin_popcountll(keep & a.zt[b]);
+    if (ballot(keep != x) == 0ull) continue;
+    const uint64_t kw = wave_transpose64(keep, lane);  // lane = node again
+    const bool lost = (old & ~kw) != 0ull;
+    if (a.bs) {
+      const uint64_t nz = ballot(kw != 0ull), full = ballot(kw == live);
+      if (lost && kw != 0ull && kw != live) bmw[n] = kw;
+      if (lane == 0) {
+        a.bs[(size_t)w * a.bs_stride + b] = BlockMask{nz, full};
+        if (nz == 0ull) atomicAnd(blkw, ~(1ull << j));
+      }
+    } else if (lost) {
+      bmw[n] = kw;
+    }
+  }
+  if (dz) atomicAdd(a.counts + a.n_work + p, dz);
+}
+
+// ---------------------------------------------------------------------------------------
 // Launchers (host side of this translation unit).
 #define YODA_K_SWITCH(K, ...)                       \
   switch (K) {                                      \
@@ -6312,6 +6536,47 @@ hipError_t launch_cand_narrow(const CandArgs& a, hipStream_t s) {
   uint32_t C = blk_row(a.n_nodes);
   if (C >= 8u) C = (C + 7u) / 8u * 8u;
   hipLaunchKernelGGL(k_cand_narrow, dim3(nw, C), dim3(kWave), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_samp_zt(const unsigned char* nodes, uint32_t stride, uint32_t n_nodes,
+                          uint64_t* zt, hipStream_t s) {
+  if (n_nodes == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_samp_zt, dim3((n_nodes + 63u) / 64u), dim3(kWave), 0, s, nodes, stride,
+                     n_nodes, zt);
+  return hipGetLastError();
+}
+
+// The windows of the count and cut grids: as launch_cand_narrow's (a multiple of 8 from 8 on).
+static uint32_t samp_windows(uint32_t n_nodes) {
+  uint32_t C = blk_row(n_nodes);
+  if (C >= 8u) C = (C + 7u) / 8u * 8u;
+  return std::max(C, 1u);
+}
+size_t samp_scratch_words(uint32_t n_work, uint32_t n_nodes) {
+  const size_t nw = (n_work + 63u) / 64u;
+  return nw * samp_windows(n_nodes) * 64u + 4u * nw * 64u;
+}
+void samp_scratch(SampArgs& a, uint32_t* scratch) {
+  const size_t nw = (a.n_work + 63u) / 64u;
+  a.wc = scratch;
+  a.tail = a.wc + nw * samp_windows(a.n_nodes) * 64u;
+  a.tot = a.tail + nw * 64u;
+  a.nxt = a.tot + nw * 64u;  // [2][n_work]
+}
+
+// Three launches on the stream.  Count and cut: grid (pod waves, windows), one wave a workgroup,
+// no LDS, placed by tile().  An empty snapshot runs the scan alone (n_found 0, next_start as
+// given).
+hipError_t launch_samp_pass(const SampArgs& a, hipStream_t s) {
+  if (a.n_work == 0) return hipSuccess;
+  if (a.bs && !a.blk) return hipErrorInvalidValue;  // sparse masks are read through their list
+  const uint32_t nw = (a.n_work + 63u) / 64u, C = samp_windows(a.n_nodes);
+  if (a.n_nodes)
+    hipLaunchKernelGGL(k_samp_count, dim3(nw, C), dim3(kWave), 0, s, a);
+  hipLaunchKernelGGL(k_samp_scan, pod_grid(a.n_work), dim3(kBlock), 0, s, a, blk_row(a.n_nodes), C);
+  if (a.n_nodes)
+    hipLaunchKernelGGL(k_samp_cut, dim3(nw, C), dim3(kWave), 0, s, a);
   return hipGetLastError();
 }
 

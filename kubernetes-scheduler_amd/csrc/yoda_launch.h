@@ -236,6 +236,15 @@ hipError_t launch_cand_update(const uint32_t* node, const uint64_t* value, uint3
                               uint64_t* words, const uint32_t* inv, uint64_t* words_p,
                               hipStream_t s);
 hipError_t launch_cand_narrow(const CandArgs& a, hipStream_t s);
+// Node sampling (yoda_set_node_sampling).  launch_samp_zt: the blocks' zero_total bits of the
+// upload order.  launch_samp_pass: K1's masks and counts from F' to the sample S in place, after
+// launch_reduce1 and launch_cand_narrow (count, scan, cut); n_found / next_start in the caller's
+// pod order.  samp_scratch_words: the u32 words of SampArgs' scratch, carved by samp_scratch.
+hipError_t launch_samp_zt(const unsigned char* nodes, uint32_t stride, uint32_t n_nodes,
+                          uint64_t* zt, hipStream_t s);
+size_t samp_scratch_words(uint32_t n_work, uint32_t n_nodes);
+void samp_scratch(SampArgs& a, uint32_t* scratch);
+hipError_t launch_samp_pass(const SampArgs& a, hipStream_t s);
 // Filter diagnosis (yoda_diagnose / yoda_reason_rows).  launch_diag_select: the pods of a
 // completed run whose n_feasible is 0 (all: every pod) into list / *n_list (zero on entry), and
 // counts [n_pods][4] zeroed for them, all ones for the others.  launch_diagnose: the sweep

@@ -566,6 +566,35 @@ struct CandArgs {
   uint32_t* counts;       // [2][n_work]
 };
 
+// Node sampling (include/yoda.h yoda_set_node_sampling): what the sampling pass reads and cuts.
+// The run reads the upload-order node tables, so a mask position is a local node id.  start is
+// in the caller's pod order (LOCAL ids), reached through perm as the classes are.  A window is
+// 64 node blocks (one word of a wave's block list), kSampWindow nodes.
+constexpr uint32_t kSampWindowLog2 = 12;
+struct SampArgs {
+  const uint32_t* start;  // [caller pods] LOCAL id the pod's walk begins at; nullptr: all 0
+  const uint32_t* perm;
+  const uint64_t* zt;     // [blocks] bit j: node 64 b + j has TotalMemorySum == 0
+  uint32_t num_to_find, node_offset;
+  uint32_t n_nodes, n_work;
+  uint64_t* bm;           // the masks, dense or sparse (bs != nullptr), as MaskSrc
+  BlockMask* bs;
+  uint64_t* blk;
+  uint32_t bm_stride, bs_stride, blk_stride;
+  uint32_t* counts;       // [2][n_work]
+  // scratch, by sorted position.  wc [waves][windows][64]: each pod's F' count of the window
+  // (count pass), then its quota there (scan: of the nodes at or after start in the start's own
+  // window).  tail [n_work]: the start window's count at or after start, then the quota of the
+  // nodes BEFORE start there (the head, visited last).  tot [n_work]: |F'|.  nxt [2][n_work]: the
+  // window (~0u: none) and the rank inside it of the (M+1)-th node of the walk.
+  uint32_t* wc;
+  uint32_t* tail;
+  uint32_t* tot;
+  uint32_t* nxt;
+  uint32_t* n_found;      // [caller pods] |F'|
+  uint32_t* next_start;   // [caller pods] GLOBAL id
+};
+
 // Filter diagnosis (include/yoda.h YODA_REASON_*): the reason codes, and the arguments of the
 // sweep (k1_diagnose).  Everything is in the CALLER's pod order and the UPLOAD order of the nodes.
 constexpr uint32_t kReasonNone = 0u, kReasonNumber = 1u, kReasonMemory = 2u, kReasonClock = 3u,

@@ -480,6 +480,50 @@ func (g *Handle) CandidatesInfo() ([3]uint32, error) {
 	return out, check(g.h, rc, "yoda_candidates_info")
 }
 
+// NumFeasibleToFind is numFeasibleNodesToFind of k8s v1.22.3 for percentageOfNodesToScore pct
+// (yoda_num_feasible_to_find; host only): 5,000 of 100,000 nodes at pct 0.
+func NumFeasibleToFind(nNodes uint32, pct int32) uint32 {
+	return uint32(C.yoda_num_feasible_to_find(C.uint32_t(nNodes), C.int32_t(pct)))
+}
+
+// SetNodeSampling makes the Mode A batch path score only the first numToFind feasible nodes of
+// each pod's walk (yoda_set_node_sampling): pod p's walk begins at the GLOBAL node id start[p]
+// (nil: at the handle's node offset), wraps past the last node and skips absent nodes.  The
+// PreScore maxima do not move; everything downstream of Filter follows the sample.  numToFind 0
+// turns sampling off, as UploadNodes does.  While on, Mode B, greedy, shard and communicator
+// calls, the reason rows and the all-pods diagnosis return an error that wraps YODA_ERR_STATE.
+// Like the rest of this file, not compiled in this repository (no Go toolchain in the image).
+func (g *Handle) SetNodeSampling(numToFind uint32, start []uint32) error {
+	var p *C.uint32_t
+	if len(start) > 0 {
+		p = (*C.uint32_t)(unsafe.Pointer(&start[0]))
+	}
+	rc := C.yoda_set_node_sampling(g.h, C.uint32_t(numToFind), C.uint32_t(len(start)), p)
+	return check(g.h, rc, "yoda_set_node_sampling")
+}
+
+// DownloadSampling fills nFound (|F'| before the cut) and nextStart (the GLOBAL id the pod's next
+// walk begins at) of the last sampled run, one entry per pod of the batch
+// (yoda_download_sampling); either may be nil.
+func (g *Handle) DownloadSampling(nFound, nextStart []uint32) error {
+	var f, x *C.uint32_t
+	if len(nFound) > 0 {
+		f = (*C.uint32_t)(unsafe.Pointer(&nFound[0]))
+	}
+	if len(nextStart) > 0 {
+		x = (*C.uint32_t)(unsafe.Pointer(&nextStart[0]))
+	}
+	return check(g.h, C.yoda_download_sampling(g.h, f, x), "yoda_download_sampling")
+}
+
+// SamplingInfo reports {numToFind (0: off), length of the start array, 1 if the last run ran the
+// sampling pass} (yoda_sampling_info; host only).
+func (g *Handle) SamplingInfo() ([3]uint32, error) {
+	var out [3]uint32
+	rc := C.yoda_sampling_info(g.h, (*C.uint32_t)(unsafe.Pointer(&out[0])))
+	return out, check(g.h, rc, "yoda_sampling_info")
+}
+
 // ModeBFollow makes Mode B's batch path (ScoreRow, Batch, Greedy with absent nodes) follow
 // SetNodePresent and the candidate classes (yoda_mode_b_follow): a pod's cycle runs over the
 // present nodes that are candidates of its class.  Off, the default, Mode B refuses while a node

@@ -92,6 +92,11 @@ _SIGS = {
     "yoda_set_pod_classes": ([_vp, _u32, _vp], C.c_int),
     "yoda_candidates_info": ([_vp, _vp], C.c_int),
     "yoda_candidates_profile": ([_vp, C.POINTER(C.c_double)], C.c_int),
+    "yoda_num_feasible_to_find": ([_u32, C.c_int32], C.c_uint32),
+    "yoda_set_node_sampling": ([_vp, _u32, _u32, _vp], C.c_int),
+    "yoda_download_sampling": ([_vp, _vp, _vp], C.c_int),
+    "yoda_sampling_info": ([_vp, _vp], C.c_int),
+    "yoda_sampling_profile": ([_vp, C.POINTER(C.c_double)], C.c_int),
     "yoda_mode_b_follow": ([_vp, C.c_int], C.c_int),
     "yoda_greedy_candidates": ([_vp, C.c_int], C.c_int),
     "yoda_shard_candidates": ([_vp, C.c_int], C.c_int),
@@ -678,6 +683,51 @@ class Yoda:
         ms = C.c_double(0)
         self._check(lib().yoda_candidates_profile(self._h, C.byref(ms)), "yoda_candidates_profile")
         return ms.value
+
+    def set_node_sampling(self, num_to_find, start=None):
+        """Score only the first `num_to_find` feasible nodes of each pod's walk, as kube-scheduler
+        does with percentageOfNodesToScore (yoda_set_node_sampling): pod p's walk begins at the
+        GLOBAL node id start[p] (caller pod order; None: at node_offset), wraps past the last
+        node, skips absent nodes and stops once num_to_find nodes of F' have passed.  The
+        PreScore maxima do not move; everything downstream of Filter follows the sample.
+        num_to_find 0 turns sampling off, as upload_nodes does.  The start array stays across pod
+        uploads.  While on, Mode B, greedy, the shard and comm calls, reason_rows and
+        diagnose(all=True) raise YODA_ERR_STATE."""
+        s = None if start is None else np.ascontiguousarray(start, np.uint32).ravel()
+        self._check(lib().yoda_set_node_sampling(self._h, int(num_to_find),
+                                                 0 if s is None else s.size,
+                                                 None if s is None else _np_ptr(s)),
+                    "yoda_set_node_sampling")
+
+    def download_sampling(self):
+        """(n_found, next_start) uint32 [P] of the last sampled run (yoda_download_sampling):
+        |F'| before the cut, and the GLOBAL id the pod's next walk begins at -- the (M+1)-th
+        feasible node of this walk, or start[p] when the walk went full circle."""
+        found = np.zeros(self.n_pods, np.uint32)
+        nxt = np.zeros(self.n_pods, np.uint32)
+        self._check(lib().yoda_download_sampling(self._h, _np_ptr(found), _np_ptr(nxt)),
+                    "yoda_download_sampling")
+        return found, nxt
+
+    def sampling_info(self):
+        """(num_to_find or 0 when off, length of the start array, 1 if the last run ran the
+        sampling pass) -- yoda_sampling_info; host only."""
+        out = np.zeros(3, np.uint32)
+        self._check(lib().yoda_sampling_info(self._h, _np_ptr(out)), "yoda_sampling_info")
+        return tuple(int(v) for v in out)
+
+    def sampling_profile(self) -> float:
+        """The sampling pass's HIP-event time (ms) over the runs read by profile_read since the
+        last call (yoda_sampling_profile)."""
+        ms = C.c_double(0)
+        self._check(lib().yoda_sampling_profile(self._h, C.byref(ms)), "yoda_sampling_profile")
+        return ms.value
+
+    @staticmethod
+    def num_feasible_to_find(n_nodes, percentage=0) -> int:
+        """numFeasibleNodesToFind of k8s v1.22.3 for percentageOfNodesToScore `percentage`
+        (yoda_num_feasible_to_find; host only)."""
+        return int(lib().yoda_num_feasible_to_find(int(n_nodes), int(percentage)))
 
     def snapshot_check(self):
         """(digest [8] u64, mismatch [4] u32) of yoda_snapshot_check (diagnostic; synchronizes)."""

@@ -208,15 +208,39 @@ def select_host(scores: Sequence[NodeScore], rng: Optional[random.Random] = None
     return selected
 
 
+def find_nodes_that_pass_filters(plugin: YodaPlugin, state: CycleState, pod: Mapping,
+                                 num_to_find: int = 0, start: int = 0) -> Tuple[list, int]:
+    """k8s v1.22.3 findNodesThatPassFilters at parallelism 1: walk the node list from index
+    `start` (wrapping) and stop once `num_to_find` nodes have passed Filter; num_to_find 0: every
+    node (percentageOfNodesToScore 100).  Returns (the feasible nodes in walk order, the index the
+    next cycle's walk begins at: the node the walk stopped at, or `start` after a full circle) --
+    what yoda_set_node_sampling / yoda_download_sampling compute for a batch."""
+    names = plugin.node_names
+    n = len(names)
+    feasible = []
+    for k in range(n):
+        i = (start + k) % n
+        if plugin.filter(state, pod, names[i]).is_success():
+            if num_to_find and len(feasible) == num_to_find:
+                return feasible, i
+            feasible.append(names[i])
+    return feasible, start
+
+
 def schedule_one(plugin: YodaPlugin, pod: Mapping, rng: Optional[random.Random] = None,
-                 weight: int = 1) -> Tuple[Optional[str], Status]:
-    """One scheduling cycle with yoda as the only Filter/Score plugin
-    (percentageOfNodesToScore 100).  Returns (node name or None, status)."""
+                 weight: int = 1, num_to_find: int = 0,
+                 start: int = 0) -> Tuple[Optional[str], Status]:
+    """One scheduling cycle with yoda as the only Filter/Score plugin.  num_to_find 0:
+    percentageOfNodesToScore 100; else only the first num_to_find feasible nodes of the walk that
+    begins at node index `start` are scored (find_nodes_that_pass_filters).  Returns (node name or
+    None, status)."""
     state = CycleState()
     st = plugin.pre_filter(state, pod)
     if not st.is_success():
         return None, st
-    feasible = [n for n in plugin.node_names if plugin.filter(state, pod, n).is_success()]
+    feasible, _ = find_nodes_that_pass_filters(plugin, state, pod, num_to_find, start)
+    if num_to_find:  # (node-list order again: select_host's deterministic rule is the lowest node)
+        feasible.sort(key=plugin.index.__getitem__)
     if not feasible:
         return None, Status(UNSCHEDULABLE, "0 nodes are available")
     if len(feasible) == 1:
