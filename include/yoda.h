@@ -660,13 +660,14 @@ int yoda_candidates_profile(yoda_t* h, double* narrow_ms);
  * circle).  A pod with M >= |F'| has the outputs it has without sampling.
  *   Honoured by yoda_eval, yoda_run (with and without YODA_RUN_BITMASK), yoda_download,
  * yoda_download_bitmask, yoda_score_rows and yoda_score_rows_norm in Mode A, with or without
- * candidate classes, absent nodes and the draw.  While sampling is on, Mode B, yoda_greedy*, every
- * yoda_shard_* and yoda_comm_* call that starts, advances or reads a step, yoda_reason_rows and
+ * candidate classes, absent nodes and the draw, and by the same calls in Mode B once
+ * yoda_mode_b_sampling (below) is on.  While sampling is on, Mode B without that setting,
+ * yoda_greedy*, every yoda_shard_* and yoda_comm_* call that starts, advances or reads a step, yoda_reason_rows and
  * yoda_diagnose with YODA_DIAG_ALL return YODA_ERR_STATE and do nothing else; the default
  * yoda_diagnose works unchanged (a pod with |S| = 0 has |F'| = 0: every node was visited).  With
  * sampling off nothing launches differently.
- *   Out of scope, refused as above: sampling in yoda_greedy, on node shards and communicators and
- * in Mode B; chaining next_start from pod to pod inside one batch (a sequential dependency: the
+ *   Out of scope, refused as above: sampling in yoda_greedy (either mode) and on node shards and
+ * communicators; chaining next_start from pod to pod inside one batch (a sequential dependency: the
  * caller feeds next_start into the NEXT batch's start); K1 stopping early once a pod's sample is
  * full (the maxima need the whole sweep).
  *   Cost: three launches after the Filter kernel and the narrowing pass (k_samp_count,
@@ -818,8 +819,51 @@ int yoda_shard_candidates(yoda_t* h, int enable);
 int yoda_mode_b_follow(yoda_t* h, int enable);
 /* Diagnostic, host only: out[4] = {enabled, effective classes D' of the last Mode B batch run,
  * 1 if that run took the eligibility kernels (0: the unchanged ones), eligibility-table builds
- * since the upload}. */
+ * since the upload}.  out[1] and out[2] describe the last UNSAMPLED Mode B batch run: a run under
+ * yoda_mode_b_sampling builds no pod classes and leaves them as they were
+ * (yoda_mode_b_sampling_info reports that run). */
 int yoda_mode_b_info(const yoda_t* h, uint32_t* out);
+/* ---- Mode B honours node sampling (opt-in): the deployed scheduler's own cycle ----
+ * The reference ships Mode B scoring together with percentageOfNodesToScore: 0
+ * (deploy/yoda-scheduler.yaml:18), so the cycle the deployed binary runs is a Mode B score over
+ * the first numFeasibleNodesToFind nodes of a rotating walk.  enable != 0: with sampling on
+ * (yoda_set_node_sampling: M = num_to_find, start[p]) Mode B's single-handle batch path scores,
+ * for pod p, S(p) = the first min(M, |E(p)|) nodes of E(p) in the rotated order of Mode A's
+ * sampling (GLOBAL ids, wrap-around, absent nodes skipped, start[p] may be outside E).  E(p) is
+ * yoda_mode_b_follow's set: the whole snapshot while no node is absent and candidates are off or
+ * every pod is YODA_CAND_ANY; an absent node or candidate classes still need yoda_mode_b_follow,
+ * and without it the refusals above stay as they are.
+ *   The cycle is the reference's Mode B cycle on the sub-snapshot of S(p); picks are ids of the
+ * uploaded snapshot.  n_feasible = |S|; |S| = 0 is YODA_STATUS_UNSCHEDULABLE; |S| = 1 is that node
+ * with its raw score and n_ties 1; otherwise top_score is the best level over S, n_ties the nodes
+ * of S at it, and the pick the LOWEST id among them (not the first in walk order: after a wrap it
+ * lies in [node_offset, next_start)), or with yoda_set_tie_draw the tie-set member with the
+ * smallest yoda_tie_hash.  There is no DIV_ZERO.  yoda_download_sampling answers after such a
+ * run: n_found[p] = |E(p)|, next_start[p] the (M+1)-th node of E in rotated order when |E| > M,
+ * else start[p].  In the score rows a node outside S has feasibility bit 0 and raw and normalized
+ * scores of -1, a node of S scores what it scores unsampled, and NormalizeScore's highest and
+ * lowest are taken over S.  A pod with M >= |E| has exactly the outputs it has without sampling.
+ *   Honoured by yoda_run, yoda_eval, yoda_download, yoda_download_sampling, the single-handle
+ * draw, yoda_score_rows and yoda_score_rows_norm (their bitmask_out included).  With sampling on
+ * these keep refusing, setting or not: yoda_greedy in Mode B, every yoda_shard_* and yoda_comm_*
+ * call, and yoda_run(YODA_MODE_DISKIO, YODA_RUN_BITMASK) + yoda_download_bitmask keeps its "run
+ * Mode A" refusal.
+ *   Off (the default): Mode B refuses with YODA_ERR_STATE while sampling is on, exactly as
+ * before.  A setting: it stays across uploads until changed (sampling itself is turned off by
+ * yoda_upload_nodes).  With the setting off or sampling off nothing launches differently.
+ *   Cost: a plan kernel (one thread per pod) and one scoring kernel (one wave per pod over its
+ * walk, the draw inside it), no chunk partials and no reduce.  With eligibility the plan reads
+ * rank tables (65 selectors x ceil(N / 64) blocks: a bit word and a prefix count each, about 1.2
+ * MB at 100k nodes), rebuilt with the eligibility table of yoda_mode_b_follow.  Measured at 100k
+ * pods x 100k nodes, M = 5000, a random start per pod (profiles/modebsampling/timing.txt): with a
+ * distinct request per pod 0.31 ms against 2.31 ms unsampled with every E whole, 0.35 ms against
+ * 4.82 ms with 1,024 absent nodes or 8 classes, and with the draw 0.64-0.75 ms against 13.4-20.4
+ * ms; with one pod spec 0.30-0.44 ms against 0.018-0.025 ms (unsampled that batch is one pod
+ * class; sampled, every pod scores its own walk).  The plan is 0.007-0.010 ms of it. */
+int yoda_mode_b_sampling(yoda_t* h, int enable);
+/* Diagnostic, host only: out[4] = {enabled, 1 if the last Mode B run took the sampled kernels,
+ * rank-table builds since the upload, 1 if that run used the eligibility instances}. */
+int yoda_mode_b_sampling_info(const yoda_t* h, uint32_t* out);
 /* ---- Filter diagnosis: why a node was rejected ----
  * kube-scheduler builds a Pending pod's FitError event ("0/N nodes are available: a ..., b ...")
  * and its PostFilter walk from the per-node Filter statuses.  The reference's Filter is three

@@ -467,6 +467,17 @@ struct yoda_handle {
   bool b_last_elig = false;
   uint32_t b_last_ncls = 0;
   DevBuf b_csel, b_elig, b_ecnt, b_pres;
+  // yoda_mode_b_sampling: Mode B's batch path honours node sampling.  b_rbits / b_rpfx: the rank
+  // tables [65][ceil(n_nodes / 64)] of the walk plan, built with the eligibility table
+  // (b_rank_for: the b_elig_builds they were built at; b_rank_builds: since the upload); b_walk
+  // [n_pods] DiskWalk: the plan's records (b_walk_ok: of this run's phase 1).  b_samp_last_*: the
+  // last Mode B run (yoda_mode_b_sampling_info).  ev_bplan: the plan's profile events.
+  bool b_samp = false;
+  uint32_t b_rank_for = 0xffffffffu;
+  uint32_t b_rank_builds = 0;
+  bool b_walk_ok = false;
+  bool b_samp_last = false, b_samp_last_elig = false;
+  DevBuf b_rbits, b_rpfx, b_walk;
   uint32_t k3_nfl = 0;
   // profiling: event pairs around K1 / K2
   bool profiling = false;
@@ -925,8 +936,8 @@ int pods_complete(yoda_t* h) {
 // (yoda_set_node_present): while a node is absent its entry points refuse to run.
 // batch: the single-handle batch path (yoda_run, yoda_eval, the row calls, yoda_greedy), which
 // follows both once yoda_mode_b_follow is on; the shard and communicator calls keep refusing.
-// Node sampling cuts the Mode A batch path only (yoda_run, yoda_eval, the row calls): everything
-// else that evaluates refuses while it is on.
+// Node sampling cuts the batch path only (yoda_run, yoda_eval, the row calls) -- Mode A's, and
+// Mode B's once yoda_mode_b_sampling is on: everything else that evaluates refuses while it is on.
 int samp_refuse(yoda_t* h, const char* what) {
   if (!h->samp_m) return YODA_OK;
   return fail(h, YODA_ERR_STATE,
@@ -936,7 +947,10 @@ int samp_refuse(yoda_t* h, const char* what) {
 
 int mode_b_absent(yoda_t* h, int mode, bool batch = false) {
   if (mode != YODA_MODE_DISKIO) return YODA_OK;
-  if (int rc = samp_refuse(h, "Mode B")) return rc;
+  // (yoda_mode_b_sampling: yoda_run, yoda_eval and the row calls score each pod's sample;
+  // yoda_greedy refuses sampling before it gets here)
+  if (!(batch && h->b_samp))
+    if (int rc = samp_refuse(h, "Mode B")) return rc;
   if (batch && h->b_follow) return YODA_OK;
   if (h->cand_classes)
     return fail(h, YODA_ERR_STATE,
@@ -1286,6 +1300,45 @@ int ensure_modeb_elig(yoda_t* h) {
   return YODA_OK;
 }
 
+// A Mode B batch run under node sampling (yoda_mode_b_sampling on) takes the sampled kernels.
+bool modeb_sampled(const yoda_t* h) { return h->b_samp && h->samp_m != 0; }
+
+// The rank tables of the sampled walk, rebuilt with the eligibility table (whose build they
+// follow on the handle's stream); only a sampled run with eligibility asks for them.
+int ensure_modeb_rank(yoda_t* h) {
+  if (int rc = ensure_modeb_elig(h)) return rc;
+  if (h->b_rank_for == h->b_elig_builds) return YODA_OK;
+  const size_t nb = std::max<size_t>(((size_t)h->n_nodes + 63) / 64, 1);
+  HIP_TRY(h, h->b_rbits.ensure(kDiskSelCount * nb * 8));
+  HIP_TRY(h, h->b_rpfx.ensure(kDiskSelCount * nb * 4));
+  HIP_TRY(h, launch_modeb_rank_build(h->b_elig.as<DiskElig>(), h->n_nodes,
+                                     h->b_rbits.as<uint64_t>(), h->b_rpfx.as<uint32_t>(),
+                                     h->stream));
+  h->b_rank_for = h->b_elig_builds;
+  ++h->b_rank_builds;
+  return YODA_OK;
+}
+
+// What a sampled Mode B run hands its kernels (after ensure_modeb_rank when eligibility is on).
+static DiskSampArgs modeb_samp_args(yoda_t* h) {
+  DiskSampArgs a{};
+  if (modeb_elig_on(h)) {
+    a.rank = DiskRank{h->b_rbits.as<uint64_t>(), h->b_rpfx.as<uint32_t>(),
+                      std::max<uint32_t>((h->n_nodes + 63u) / 64u, 1u)};
+    a.cls = modeb_cls_bytes(h);
+    a.cnt = h->b_ecnt.as<uint32_t>();
+  }
+  a.start = h->h_start.empty() ? nullptr : h->samp_start.as<uint32_t>();
+  a.m = h->samp_m;
+  a.n_nodes = h->n_nodes;
+  a.n_pods = h->n_pods;
+  a.node_offset = h->node_offset;
+  a.n_found = h->samp_out.as<uint32_t>();
+  a.next_start = a.n_found + h->n_pods;
+  a.walk = h->b_walk.as<DiskWalk>();
+  return a;
+}
+
 // The free levels t_0 = 0 < ... < t_{L-1} = 0xFFFFFFFF of the kbub lv[] bounds (yoda_layout.h):
 // the quantiles of the snapshot's real card frees (K2 summary words: values, or memory ranks),
 // so that a wave's scv/memory range falls between close levels wherever the cards are.
@@ -1475,8 +1528,27 @@ int phase1(yoda_t* h, int mode, uint64_t* maxima, uint32_t* counts,
   h->seeds_valid = false;  // (set again below when this run's block K1 writes them)
   h->rcp_ready = false;
   h->samp_ran = false;
+  h->b_walk_ok = false;
   const uint32_t P = h->n_work;  // sorted positions of this run
   if (P == 0) return YODA_OK;
+  if (mode == YODA_MODE_DISKIO && modeb_sampled(h)) {
+    // the plan: n_feasible = |S(p)|, n_found, next_start and each pod's walk record
+    if (modeb_elig_on(h))
+      if (int rc = ensure_modeb_rank(h)) return rc;
+    HIP_TRY(h, h->samp_out.ensure(2 * (size_t)P * 4));
+    HIP_TRY(h, h->b_walk.ensure((size_t)P * sizeof(DiskWalk)));
+    hipEvent_t c0 = h->profiling ? h->next_event() : nullptr;
+    hipEvent_t c1 = h->profiling ? h->next_event() : nullptr;
+    if (c0) HIP_TRY(h, hipEventRecord(c0, h->stream));
+    HIP_TRY(h, launch_k2b_samp_plan(modeb_samp_args(h), maxima, counts, h->stream));
+    if (c1) {  // (Mode B has no K1: the plan reports in its place, yoda_profile_read)
+      HIP_TRY(h, hipEventRecord(c1, h->stream));
+      h->ev_k1.emplace_back(c0, c1);
+    }
+    h->b_walk_ok = true;
+    h->samp_ran = true;
+    return YODA_OK;
+  }
   if (mode == YODA_MODE_DISKIO) {
     if (modeb_elig_on(h))
       if (int rc = ensure_modeb_elig(h)) return rc;
@@ -1634,8 +1706,10 @@ int phase1_witness(yoda_t* h, uint64_t* maxima, uint32_t* counts, uint32_t* wit,
 // Phase 2: Score over the feasible nodes with the (globally reduced) maxima.
 // counts: the pods' feasible-node counts ([P] prefix of phase 1's [2][P], local or reduced;
 // NULL: unknown): a pod with none takes no part in the block K2's wave bounds.
+// draw: a private run with the selectHost draw on -- a sampled Mode B run draws inside its kernel.
 int phase2(yoda_t* h, int mode, const uint64_t* maxima, const uint32_t* counts, int64_t* best,
-           uint32_t* idx, uint32_t* ties, int64_t* low, int64_t* rows = nullptr) {
+           uint32_t* idx, uint32_t* ties, int64_t* low, int64_t* rows = nullptr,
+           bool draw = false) {
   const uint32_t P = h->n_work;  // sorted positions of this run
   if (P == 0) return YODA_OK;
   const uint64_t* cmask2 = nullptr;
@@ -1656,9 +1730,31 @@ int phase2(yoda_t* h, int mode, const uint64_t* maxima, const uint32_t* counts, 
   if (mode == YODA_MODE_SCV && !h->generic && !h->rcp_ready)
     HIP_TRY(h, launch_prep2(maxima, P, h->rcp.as<double>(),  h->stream));
   h->rcp_ready = false;
+  // (under node sampling this run's phase 1 planned each pod's walk: yoda_mode_b_sampling)
+  const bool sampled = mode == YODA_MODE_DISKIO && h->b_walk_ok && modeb_sampled(h);
+  if (mode == YODA_MODE_DISKIO) {
+    h->b_samp_last = sampled;
+    h->b_samp_last_elig = sampled && modeb_elig_on(h);
+  }
   if (mode == YODA_MODE_DISKIO && !rows) {
     // batch path: over the batch's pod classes, then each pod takes its class's outcome
     // (Mode B runs are never reordered: P == n_pods, caller order)
+    if (sampled) {
+      // under node sampling: one wave per pod over its walk, the outcome straight into the
+      // pod's slot; with the draw on, the pick is drawn inside the same kernel
+      if ((uint64_t)h->n_nodes >> kDiskCountBits)
+        return fail(h, YODA_ERR_INVALID_ARG, "Mode B batch: more than 2^28 nodes");
+      const DiskDrawArgs dr{h->tie_seed, h->tie_pod_base};
+      if (e0) HIP_TRY(h, hipEventRecord(e0, h->stream));
+      HIP_TRY(h, launch_k2b_sampled(h->nodes_b.as<NodeRecB>(), pod_params(h), diskio_levels(),
+                                    modeb_samp_args(h), draw ? &dr : nullptr, best, idx,
+                                    ties, low, h->stream));
+      if (e1) {
+        HIP_TRY(h, hipEventRecord(e1, h->stream));
+        h->ev_k2.emplace_back(e0, e1);
+      }
+      return YODA_OK;
+    }
     int rc = ensure_diskio_classes(h);
     if (rc) return rc;
     if ((uint64_t)h->n_nodes >> kDiskCountBits)
@@ -1696,7 +1792,9 @@ int phase2(yoda_t* h, int mode, const uint64_t* maxima, const uint32_t* counts, 
     HIP_TRY(h, h->p_ties.ensure(cp * 4));
     part = partials(h);
     HIP_TRY(h, launch_k2b_rows(h->nodes_b.as<NodeRecB>(), h->n_nodes, pod_params(h), P, part,
-                               rows, modeb_elig_args(h), h->stream));
+                               rows, modeb_elig_args(h), h->stream,
+                               // (under node sampling: the row covers the pod's walk alone)
+                               sampled ? h->b_walk.as<DiskWalk>() : nullptr));
   } else {
     // the block argmax K2 (N32 with summaries) marks the chunks it wrote (PodParams::cmask2)
     if (h->path == Path::N32 && h->has_k2sum && !rows) cmask2 = pod_params(h).cmask2;
@@ -2572,6 +2670,8 @@ int yoda_upload_nodes(yoda_t* h, const yoda_node_soa* nd, uint32_t node_offset, 
     h->samp_ran = false;
     h->b_elig_dirty = true;  // (Mode B's eligibility table is the old snapshot's)
     h->b_elig_builds = 0;
+    h->b_rank_for = 0xffffffffu;  // (... and so are the rank tables of yoda_mode_b_sampling)
+    h->b_rank_builds = 0;
     h->nodes_diskio = diskio;
     h->upload_flags = flags;
     h->n_one_model = rows.n_one_model;
@@ -3057,7 +3157,8 @@ static int run_private(yoda_t* h, int mode, uint32_t flags, bool draw) {
                      Maxima::OwnFinal)))
       return rc;
     if ((rc = phase2(h, mode, h->maxima.as<uint64_t>(), h->counts.as<uint32_t>(), h->best.as<int64_t>(),
-                     h->idx.as<uint32_t>(), h->ties.as<uint32_t>(), h->lowest.as<int64_t>())))
+                     h->idx.as<uint32_t>(), h->ties.as<uint32_t>(), h->lowest.as<int64_t>(),
+                     nullptr, draw && h->tie_draw)))
       return rc;
     if (diag_env("YODA_SEED_DEBUG", 0) && pod_params(h).seed) seed_report(h);
     if ((rc = finalize(h, mode, h->counts.as<uint32_t>(), h->best.as<int64_t>(),
@@ -3069,7 +3170,9 @@ static int run_private(yoda_t* h, int mode, uint32_t flags, bool draw) {
     h->core_only = false;
     if (defer && h->copy_stream && (rc = pods_complete_async(h))) return rc;
     if (defer && (rc = pods_complete(h))) return rc;
-    if (draw && h->tie_draw && (rc = draw_pass(h, mode))) return rc;
+    // (a sampled Mode B run drew inside its kernel: the list pass would rescan every node)
+    const bool drawn = mode == YODA_MODE_DISKIO && h->b_samp_last;
+    if (draw && h->tie_draw && !drawn && (rc = draw_pass(h, mode))) return rc;
     h->ran = true;
     h->diag_done = false;
     h->ran_bitmask = mode == YODA_MODE_SCV && (flags & YODA_RUN_BITMASK);
@@ -3224,7 +3327,27 @@ int yoda_score_rows_norm(yoda_t* h, int mode, uint32_t* bitmask_out, uint64_t n_
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (bitmask_out && W * P > 0) {
-      if (mode == YODA_MODE_DISKIO && modeb_elig_on(h)) {  // E, from the host mirrors
+      if (mode == YODA_MODE_DISKIO && modeb_sampled(h)) {
+        // S: E from the host mirrors, cut by the plan's walk records
+        const bool el = modeb_elig_on(h), keyed = modeb_keyed(h);
+        std::vector<DiskWalk> wk(P);
+        HIP_TRY(h, hipMemcpyAsync(wk.data(), h->b_walk.p, (size_t)P * sizeof(DiskWalk),
+                                  hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        std::memset(bitmask_out, 0, (size_t)(W * P) * 4);
+        for (uint64_t p = 0; p < P; ++p) {
+          const uint32_t sel = keyed ? disk_sel(h->h_cls[p]) : kDiskSelAny;
+          for (uint32_t n = 0; n < N; ++n) {
+            if (!disk_in_walk(n, wk[p])) continue;
+            if (el) {
+              const DiskElig e =
+                  disk_elig_of(!h->h_absent[n], h->cand_classes ? h->h_cand[n] : ~0ull);
+              if (!disk_eligible(e, sel)) continue;
+            }
+            bitmask_out[p * W + (n >> 5)] |= 1u << (n & 31u);
+          }
+        }
+      } else if (mode == YODA_MODE_DISKIO && modeb_elig_on(h)) {  // E, from the host mirrors
         const bool keyed = modeb_keyed(h);
         std::memset(bitmask_out, 0, (size_t)(W * P) * 4);
         for (uint64_t p = 0; p < P; ++p) {
@@ -5018,6 +5141,26 @@ int yoda_mode_b_follow(yoda_t* h, int enable) {
   return YODA_OK;
 }
 
+int yoda_mode_b_sampling(yoda_t* h, int enable) {
+  if (!h) return YODA_ERR_INVALID_ARG;
+  const bool on = enable != 0;
+  if (on != h->b_samp && h->samp_m) {  // the pending outcomes are the other reading's
+    cand_invalidate(h);
+    h->samp_ran = false;
+  }
+  h->b_samp = on;
+  return YODA_OK;
+}
+
+int yoda_mode_b_sampling_info(const yoda_t* h, uint32_t* out) {
+  if (!h || !out) return YODA_ERR_INVALID_ARG;
+  out[0] = h->b_samp ? 1u : 0u;
+  out[1] = h->b_samp_last ? 1u : 0u;
+  out[2] = h->b_rank_builds;
+  out[3] = h->b_samp_last_elig ? 1u : 0u;
+  return YODA_OK;
+}
+
 int yoda_greedy_candidates(yoda_t* h, int enable) {
   if (!h) return YODA_ERR_INVALID_ARG;
   h->greedy_cand = enable != 0;
@@ -5114,7 +5257,9 @@ int yoda_set_node_sampling(yoda_t* h, uint32_t num_to_find, uint32_t n_pods,
 
 int yoda_download_sampling(yoda_t* h, uint32_t* n_found, uint32_t* next_start) {
   if (!h) return YODA_ERR_INVALID_ARG;
-  if (!h->ran || h->k3_pending || !h->samp_m || h->last_mode != YODA_MODE_SCV ||
+  // (a Mode B run answers when it took the sampled kernels: yoda_mode_b_sampling)
+  if (!h->ran || h->k3_pending || !h->samp_m ||
+      (h->last_mode != YODA_MODE_SCV && !(h->b_samp_last || h->n_pods == 0)) ||
       !(h->samp_ran || h->n_pods == 0))
     return fail(h, YODA_ERR_STATE, "yoda_download_sampling before a sampled yoda_run");
   const uint32_t P = h->n_pods;

@@ -13,6 +13,8 @@
 //                          argmax/ties/min for NormalizeScore + selectHost
 //   K2B k2b_*<ELIG>        algorithm.go:99-119 (Mode B: pod classes in batches, lane = node for
 //                          score rows; ELIG = the run honours absent nodes / candidate classes)
+//       k2b_samp_*, k2b_sampled  the same score over each pod's node sample (Mode B under
+//                          node sampling, yoda_mode_b_sampling): a plan, then one wave per pod
 //   K3  k3_exact_normalize scheduler.go:176-179 with int64 wrap (generic path only)
 //       k_draw_*           k8s selectHost as a seeded draw over each tied pod's tie set (a
 //                          post-pass with LANE = NODE, only with yoda_set_tie_draw enabled)
@@ -4512,8 +4514,9 @@ __device__ __forceinline__ void k2b_rows_merge(bool v, double score, uint32_t c,
 // 256-node chunk per workgroup, the pods of the (small) batch in turn -- every lane busy and
 // the row stores coalesced at P = 1.  Per pod the chunk's (best, lowest node, ties, lowest
 // score) partials, as k_reduce2 merges them.  ELIG: a node outside the pod's E keeps the row's
-// -1 (the caller's fill) and stays out of best, low, idx and ties.
-template <bool ELIG>
+// -1 (the caller's fill) and stays out of best, low, idx and ties.  WALK (a sampled run,
+// yoda_mode_b_sampling): likewise a node outside the pod's walk, so the row covers S alone.
+template <bool ELIG, bool WALK>
 __global__ __launch_bounds__(kBlock) void k2b_rows(const NodeRecB* __restrict__ nodes,
                                                    uint32_t n_nodes,
                                                    const double* __restrict__ alpha_in,
@@ -4522,7 +4525,8 @@ __global__ __launch_bounds__(kBlock) void k2b_rows(const NodeRecB* __restrict__ 
                                                    uint32_t* __restrict__ pidx,
                                                    uint32_t* __restrict__ pties,
                                                    double* __restrict__ plow,
-                                                   int64_t* __restrict__ rows, DiskEligArgs ea) {
+                                                   int64_t* __restrict__ rows, DiskEligArgs ea,
+                                                   const DiskWalk* __restrict__ walk) {
   const uint32_t c = blockIdx.x, n = c * kBlock + threadIdx.x;
   const bool in = n < n_nodes;
   const NodeRecB r = in ? nodes[n] : NodeRecB{0.0, 0.0};
@@ -4533,6 +4537,7 @@ __global__ __launch_bounds__(kBlock) void k2b_rows(const NodeRecB* __restrict__ 
   for (uint32_t p = 0; p < n_pods; ++p) {
     bool v = in;
     if constexpr (ELIG) v = disk_eligible(e, ea.cls ? disk_sel(ea.cls[p]) : kDiskSelAny);
+    if constexpr (WALK) v = v && disk_in_walk(n, walk[p]);
     const double score = disk_score(disk_absdiff(alpha_in[p], r.v, beta_in[p], r.u));
     if (v) rows[(size_t)n * n_pods + p] = (int64_t)score;
     k2b_rows_merge(v, score, c, p, n_pods, pbest, pidx, pties, plow);
@@ -5572,6 +5577,178 @@ __global__ __launch_bounds__(kWave) void k_samp_cut(const SampArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------
+// Mode B under node sampling (yoda_mode_b_sampling): pod p scores S(p), the first
+// min(M, |E|) nodes of E(p) in its walk.  The plan and the walk predicate are yoda_modeb.h's
+// (disk_plan_walk, disk_plan_whole, disk_in_walk), shared with the host check.
+
+// The rank tables' bit rows from the eligibility table: one wave per 64-node block transposes
+// the nodes' candidate words (lane = node -> lane = class) and ballots the presence bits.  A
+// node past the last one contributes zeros, so the tail bits of the last block are clear.
+__global__ __launch_bounds__(kBlock) void k_modeb_rank_build(const DiskElig* __restrict__ elig,
+                                                             uint32_t n_nodes, uint32_t n_blocks,
+                                                             uint64_t* __restrict__ bits) {
+  const uint32_t lane = lane_id();
+  const uint32_t b = blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6);
+  if (b >= n_blocks) return;  // (wave-uniform)
+  const uint32_t n = 64u * b + lane;
+  DiskElig e{0ull, 0ull};
+  if (n < n_nodes) e = elig[n];
+  bits[(size_t)lane * n_blocks + b] = wave_transpose64(e.lo, lane);
+  const uint64_t pres = ballot((e.hi & 1ull) != 0ull);
+  if (lane == 0) bits[(size_t)kDiskSelAny * n_blocks + b] = pres;
+}
+
+// ... and their exclusive prefix counts: one wave per selector scans its row.
+__global__ __launch_bounds__(kWave) void k_modeb_rank_scan(const uint64_t* __restrict__ bits,
+                                                           uint32_t n_blocks,
+                                                           uint32_t* __restrict__ pfx) {
+  const uint32_t sel = blockIdx.x, lane = threadIdx.x;
+  uint32_t carry = 0;
+  for (uint32_t base = 0; base < n_blocks; base += kWave) {
+    const uint32_t b = base + lane;
+    const uint32_t c =
+        b < n_blocks ? (uint32_t)__builtin_popcountll(bits[(size_t)sel * n_blocks + b]) : 0u;
+    uint32_t inc = c;
+#pragma unroll
+    for (int o = 1; o < (int)kWave; o <<= 1) {
+      const uint32_t t = (uint32_t)__shfl_up((int)inc, o, kWave);
+      inc += lane >= (uint32_t)o ? t : 0u;
+    }
+    if (b < n_blocks) pfx[(size_t)sel * n_blocks + b] = carry + inc - c;
+    carry += (uint32_t)__shfl((int)inc, kWave - 1, kWave);
+  }
+}
+
+// The plan, one thread per pod (Mode B runs are never reordered: p is the caller's index):
+// n_feasible = |S|, the maxima as k_fill_diskio_state writes them, n_found and next_start, and
+// the walk record the sampled and the rows kernels read.
+template <bool ELIG>
+__global__ __launch_bounds__(kBlock) void k2b_samp_plan(DiskSampArgs a,
+                                                        uint64_t* __restrict__ maxima,
+                                                        uint32_t* __restrict__ counts) {
+  const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+  if (p >= a.n_pods) return;
+  for (int f = 0; f < 6; ++f) maxima[(size_t)f * a.n_pods + p] = 1;
+  const uint32_t start = a.start ? a.start[p] : 0u;
+  DiskWalkPlan pl;
+  if constexpr (ELIG) {
+    const uint32_t sel = a.cls ? disk_sel(a.cls[p]) : kDiskSelAny;
+    const size_t row = (size_t)sel * a.rank.n_blocks;
+    pl = disk_plan_walk(a.rank.bits + row, a.rank.pfx + row, a.rank.n_blocks, a.cnt[sel], start,
+                        a.m);
+  } else {
+    pl = disk_plan_whole(a.n_nodes, start, a.m);
+  }
+  counts[p] = pl.n_sample;
+  counts[(size_t)a.n_pods + p] = 0;
+  a.n_found[p] = pl.n_found;
+  a.next_start[p] = a.node_offset + pl.next_start;
+  a.walk[p] = pl.walk;
+}
+
+// The nodes of a walk, lane = node, as at most two ascending id segments -- the head [0, stop)
+// before the tail [start, N), so every lane sees increasing ids.  ELIG: the lane's bit of the
+// block's word of the pod's selector row (one wave-uniform load per block; a block with no
+// eligible node is skipped).  f(n) runs for each node of S the lane owns.
+template <bool ELIG, class F>
+__device__ __forceinline__ void walk_sweep(DiskWalk w, uint32_t n_nodes,
+                                           const uint64_t* __restrict__ bits, uint32_t lane,
+                                           F f) {
+  const bool wrap = !w.full && w.stop <= w.start;
+  const uint32_t lo[2] = {(w.full || wrap) ? 0u : w.start, wrap ? w.start : 0u};
+  const uint32_t hi[2] = {w.full ? n_nodes : w.stop, wrap ? n_nodes : 0u};
+#pragma unroll
+  for (int g = 0; g < 2; ++g) {
+    if (lo[g] >= hi[g]) continue;
+    const uint32_t b1 = (hi[g] - 1u) >> 6;
+    for (uint32_t b = lo[g] >> 6; b <= b1; ++b) {
+      const uint32_t n = 64u * b + lane;
+      bool v = n >= lo[g] && n < hi[g];
+      if constexpr (ELIG) {
+        const uint64_t word = bits[b];
+        if (word == 0ull) continue;
+        v = v && ((word >> lane) & 1ull) != 0ull;
+      }
+      if (v) f(n);
+    }
+  }
+}
+
+// The sampled score: one wave per pod, lane = node over the pod's walk; alpha and beta are
+// wave-uniform.  The lanes' (level, count, lowest node) merge through disk_merge_any, and the
+// pod's slot is written directly -- no chunk partials.  DRAW: a pod with >= 2 nodes at its best
+// sweeps its walk again and takes the node of the smallest tie_key among them.
+template <bool ELIG, bool DRAW>
+__global__ __launch_bounds__(kBlock) void k2b_sampled(const NodeRecB* __restrict__ nodes,
+                                                      const double* __restrict__ alpha_in,
+                                                      const double* __restrict__ beta_in,
+                                                      DiskLevels lvs, DiskSampArgs a,
+                                                      DiskDrawArgs dr,
+                                                      int64_t* __restrict__ best_out,
+                                                      uint32_t* __restrict__ idx_out,
+                                                      uint32_t* __restrict__ ties_out,
+                                                      int64_t* __restrict__ low_out) {
+  __shared__ double lv[12];
+  disk_levels_to_lds(lv, lvs);
+  const uint32_t lane = lane_id();
+  const uint32_t p = (uint32_t)__builtin_amdgcn_readfirstlane(
+      (int)(blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6)));
+  if (p >= a.n_pods) return;  // (wave-uniform, after the workgroup's barrier)
+  const double al = alpha_in[p], be = beta_in[p];
+  const DiskWalk w = a.walk[p];
+  const uint64_t* __restrict__ bits = nullptr;
+  if constexpr (ELIG)
+    bits = a.rank.bits + (size_t)(a.cls ? disk_sel(a.cls[p]) : kDiskSelAny) * a.rank.n_blocks;
+  DiskAcc s;
+  DiskSeen sn;
+  disk_init(s, lv);
+  disk_seen_init(sn);
+  walk_sweep<ELIG>(w, a.n_nodes, bits, lane, [&](uint32_t n) {
+    const NodeRecB r = nodes[n];
+    disk_step_elig(s, sn, disk_absdiff(al, r.v, be, r.u), n, lv);
+  });
+  uint32_t mc, mi;
+  disk_settle(s, sn, mc, mi);
+  DiskBest b;
+  disk_best_init(b);
+  disk_merge_any(b, s.lev, mc, mi);
+#pragma unroll
+  for (int o = kWave / 2; o > 0; o >>= 1) {  // (an all-reduce: every lane ends with the pod's)
+    const uint32_t ol = (uint32_t)__shfl_xor((int)(b.cnt ? (uint32_t)b.lev : 0u), o, kWave);
+    const uint32_t oc = (uint32_t)__shfl_xor((int)b.cnt, o, kWave);
+    const uint32_t oi = (uint32_t)__shfl_xor((int)b.idx, o, kWave);
+    disk_merge_any(b, ol, oc, oi);
+  }
+  uint32_t pick = b.idx == 0xffffffffu ? b.idx : b.idx + a.node_offset;
+  if constexpr (DRAW) {
+    if (b.cnt >= 2u) {  // (wave-uniform)
+      const uint32_t L = (uint32_t)b.lev;
+      const double thr = lv[L];  // a node of S is at the best level iff |d| <= t[L]; level 0: all
+      const uint64_t st = tie_pod_state(dr.seed, dr.pod_base + p);
+      uint64_t key = ~0ull;
+      walk_sweep<ELIG>(w, a.n_nodes, bits, lane, [&](uint32_t n) {
+        const NodeRecB r = nodes[n];
+        if (L == 0u || disk_absdiff(al, r.v, be, r.u) <= thr) {
+          const uint64_t k = tie_key(st, a.node_offset + n);
+          key = k < key ? k : key;
+        }
+      });
+#pragma unroll
+      for (int o = kWave / 2; o > 0; o >>= 1) {
+        const uint64_t other = __shfl_xor(key, o, kWave);
+        key = other < key ? other : key;
+      }
+      pick = (uint32_t)key;
+    }
+  }
+  if (lane != 0) return;
+  best_out[p] = b.lev;
+  idx_out[p] = pick;
+  ties_out[p] = b.cnt;
+  low_out[p] = 0;
+}
+
+// ---------------------------------------------------------------------------------------
 // Launchers (host side of this translation unit).
 #define YODA_K_SWITCH(K, ...)                       \
   switch (K) {                                      \
@@ -5684,7 +5861,7 @@ int kernel_capacity(int K, Path path, int which, int mode_diskio) {
   if (mode_diskio) {
     // (Mode B plans its own chunks -- diskio_plan, the rows kernel's 256-node chunks -- so this
     // only sizes the handle's shared partial buffers: the unrestricted rows kernel stands for it)
-    YODA_FN(&k2b_rows<false>);
+    YODA_FN((&k2b_rows<false, false>));
   } else if (which == 1) {
     switch (path) {
       // (the one-model tiles' kernel: the chunk plan of config 3 as measured)
@@ -6386,12 +6563,46 @@ hipError_t launch_reduce2b(const uint32_t* plc, const uint32_t* pidx, uint32_t C
 
 hipError_t launch_k2b_rows(const NodeRecB* nodes, uint32_t n_nodes, const PodParams& pp,
                            uint32_t n_pods, const Partials& part, int64_t* rows,
-                           const DiskEligArgs& ea, hipStream_t s) {
+                           const DiskEligArgs& ea, hipStream_t s, const DiskWalk* walk) {
   if (n_nodes == 0 || n_pods == 0) return hipSuccess;
-  const auto k = ea.elig ? k2b_rows<true> : k2b_rows<false>;
+  auto k = ea.elig ? k2b_rows<true, false> : k2b_rows<false, false>;
+  if (walk) k = ea.elig ? k2b_rows<true, true> : k2b_rows<false, true>;
   hipLaunchKernelGGL(k, dim3((n_nodes + kBlock - 1) / kBlock), dim3(kBlock), 0, s, nodes, n_nodes,
                      pp.alpha, pp.beta, n_pods, part.best_f, part.idx, part.ties, part.low_f, rows,
-                     ea);
+                     ea, walk);
+  return hipGetLastError();
+}
+
+// The rank tables of the sampled walk (yoda_mode_b_sampling) from the eligibility table.
+hipError_t launch_modeb_rank_build(const DiskElig* elig, uint32_t n_nodes, uint64_t* bits,
+                                   uint32_t* pfx, hipStream_t s) {
+  const uint32_t NB = std::max<uint32_t>((n_nodes + 63u) / 64u, 1u);
+  hipLaunchKernelGGL(k_modeb_rank_build, dim3((NB + kBlock / kWave - 1) / (kBlock / kWave)),
+                     dim3(kBlock), 0, s, elig, n_nodes, NB, bits);
+  hipLaunchKernelGGL(k_modeb_rank_scan, dim3(kDiskSelCount), dim3(kWave), 0, s, bits, NB, pfx);
+  return hipGetLastError();
+}
+
+// A sampled Mode B run: the plan (one thread per pod), then the score over each pod's walk (one
+// wave per pod).  a.rank.bits == nullptr: every E whole, the ELIG = false instances.
+hipError_t launch_k2b_samp_plan(const DiskSampArgs& a, uint64_t* maxima, uint32_t* counts,
+                                hipStream_t s) {
+  if (a.n_pods == 0) return hipSuccess;
+  const auto k = a.rank.bits ? k2b_samp_plan<true> : k2b_samp_plan<false>;
+  hipLaunchKernelGGL(k, pod_grid(a.n_pods), dim3(kBlock), 0, s, a, maxima, counts);
+  return hipGetLastError();
+}
+
+hipError_t launch_k2b_sampled(const NodeRecB* nodes, const PodParams& pp, const DiskLevels& lv,
+                              const DiskSampArgs& a, const DiskDrawArgs* draw, int64_t* best,
+                              uint32_t* idx, uint32_t* ties, int64_t* low, hipStream_t s) {
+  if (a.n_pods == 0 || a.n_nodes == 0) return hipSuccess;
+  const bool el = a.rank.bits != nullptr;
+  auto k = el ? k2b_sampled<true, false> : k2b_sampled<false, false>;
+  if (draw) k = el ? k2b_sampled<true, true> : k2b_sampled<false, true>;
+  const uint32_t wpb = kBlock / kWave;
+  hipLaunchKernelGGL(k, dim3((a.n_pods + wpb - 1) / wpb), dim3(kBlock), 0, s, nodes, pp.alpha,
+                     pp.beta, lv, a, draw ? *draw : DiskDrawArgs{}, best, idx, ties, low);
   return hipGetLastError();
 }
 

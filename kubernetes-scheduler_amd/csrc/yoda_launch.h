@@ -52,13 +52,27 @@ hipError_t launch_k2(int K, Path path, const unsigned char* nodes, const unsigne
 // unrestricted run and takes the kernels' ELIG = false instances.  launch_draw takes it too.
 struct DiskElig;
 struct DiskEligArgs;
+struct DiskWalk;
+struct DiskSampArgs;
+struct DiskDrawArgs;
 // The table build: elig [n_nodes], cnt [kDiskSelCount], from the candidate words (nullptr: off)
 // and the presence bitmap.
 hipError_t launch_modeb_elig_build(const uint64_t* words, const uint64_t* pres, uint32_t n_nodes,
                                    DiskElig* elig, uint32_t* cnt, hipStream_t s);
 hipError_t launch_k2b_rows(const NodeRecB* nodes, uint32_t n_nodes, const PodParams& pp,
                            uint32_t n_pods, const Partials& part, int64_t* rows,
-                           const DiskEligArgs& ea, hipStream_t s);
+                           const DiskEligArgs& ea, hipStream_t s, const DiskWalk* walk = nullptr);
+// Mode B under node sampling (yoda_mode_b_sampling): the rank tables bits / pfx
+// [kDiskSelCount][ceil(n_nodes / 64)] from the eligibility table; the plan (counts [2][P], the
+// maxima, a's n_found / next_start / walk); the score over each pod's walk, with the selectHost
+// draw inside it when draw != nullptr.  walk (the rows launch above): the plan's records.
+hipError_t launch_modeb_rank_build(const DiskElig* elig, uint32_t n_nodes, uint64_t* bits,
+                                   uint32_t* pfx, hipStream_t s);
+hipError_t launch_k2b_samp_plan(const DiskSampArgs& a, uint64_t* maxima, uint32_t* counts,
+                                hipStream_t s);
+hipError_t launch_k2b_sampled(const NodeRecB* nodes, const PodParams& pp, const DiskLevels& lv,
+                              const DiskSampArgs& a, const DiskDrawArgs* draw, int64_t* best,
+                              uint32_t* idx, uint32_t* ties, int64_t* low, hipStream_t s);
 DiskPlan diskio_plan(uint32_t n_nodes, uint32_t n_cls);
 hipError_t launch_k2b(const NodeRecB* nodes, uint32_t n_nodes, const double* cab,
                       uint32_t n_cls, const DiskLevels& lv, const DiskPlan& pl, uint32_t* plc,

@@ -1,7 +1,10 @@
 // yoda_modeb.h — the Mode B batch path's per-lane accumulator, its settle and the merges of its
 // partials, shared by the HIP kernels (yoda_kernels.hip k2b_*), the host side of libyoda (the
-// pod-class builder) and a stand-alone host program (tools/check_modeb_elig.cpp).
-// See DESIGN.md §4 (Mode B) and §5 (eligibility: absent nodes and candidate classes).
+// pod-class builder) and a stand-alone host program (tools/check_modeb_elig.cpp); and the walk
+// plan of Mode B under node sampling (the k2b_samp_plan / k2b_sampled / k2b_rows kernels, the
+// rows' host-filled bitmask, tools/check_modeb_sampling.cpp).
+// See DESIGN.md §4 (Mode B) and §5 (eligibility: absent nodes and candidate classes; Mode B under
+// node sampling).
 #pragma once
 #include <stdint.h>
 
@@ -207,6 +210,120 @@ __host__ __device__ __forceinline__ void disk_merge_chunk(DiskBest& b, uint32_t 
     b.cnt += cnt;
   }
 }
+
+// ---------------------------------------------------------------------------------------
+// Node sampling in Mode B (yoda_mode_b_sampling): pod p scores S(p), the first
+// min(M, |E|) nodes of E(p) in the walk order start, start + 1, ..., wrapping at the snapshot's
+// end.  S is E cut to at most two ascending id segments, so a walk is three words: the nodes of
+// [start, stop) (stop > start), or of [start, N) and [0, stop) after a wrap; full: every node of
+// E (|E| <= M, or an empty E).  Local ids throughout.
+struct DiskWalk {
+  uint32_t start, stop, full;
+};
+
+__host__ __device__ __forceinline__ bool disk_in_walk(uint32_t n, DiskWalk w) {
+  if (w.full) return true;
+  const bool ge = n >= w.start, lt = n < w.stop;
+  return w.stop > w.start ? (ge && lt) : (ge || lt);
+}
+
+// The position of the set bit of rank r (0-based, r < popcount(x)): six popcount steps.
+__host__ __device__ __forceinline__ uint32_t disk_select64(uint64_t x, uint32_t r) {
+  uint32_t t = 0;
+#pragma unroll
+  for (uint32_t s = 32u; s >= 1u; s >>= 1) {
+    const uint32_t c = (uint32_t)__builtin_popcountll((x >> t) & ((1ull << s) - 1ull));
+    if (r >= c) {
+      r -= c;
+      t += s;
+    }
+  }
+  return t;
+}
+
+// The rank tables of the walk plan, selector-major over 64-node blocks: bits[sel][b] holds the
+// eligibility of nodes 64 b .. 64 b + 63 under selector sel (tail bits past the last node clear),
+// pfx[sel][b] the eligible nodes below block b.
+struct DiskRank {
+  const uint64_t* bits;  // [kDiskSelCount][n_blocks]
+  const uint32_t* pfx;   // [kDiskSelCount][n_blocks]
+  uint32_t n_blocks;
+};
+
+// A pod's plan: its walk, |E| (n_found), |S| and the node the next walk starts at -- the
+// (M + 1)-th node of E in walk order when |E| > M, else start itself.
+struct DiskWalkPlan {
+  DiskWalk walk;
+  uint32_t n_found, n_sample, next_start;
+};
+
+// Every E whole: E is the id range [0, n_nodes), so the plan is arithmetic.
+__host__ __device__ __forceinline__ DiskWalkPlan disk_plan_whole(uint32_t n_nodes, uint32_t start,
+                                                                 uint32_t m) {
+  DiskWalkPlan pl;
+  pl.n_found = n_nodes;
+  if (n_nodes <= m) {
+    pl.walk = DiskWalk{start, start, 1u};
+    pl.n_sample = n_nodes;
+    pl.next_start = start;
+  } else {
+    const uint32_t stop = (uint32_t)(((uint64_t)start + m) % n_nodes);
+    pl.walk = DiskWalk{start, stop, 0u};
+    pl.n_sample = m;
+    pl.next_start = stop;
+  }
+  return pl;
+}
+
+// One selector's rows (bits, pfx: n_blocks words each) and its total: r0 = the eligible ids below
+// start; the walk's (M + 1)-th node has rank (r0 + M) mod total -- the block by binary search in
+// the prefix row (the last block whose prefix is <= the rank holds it: the next one's is above),
+// the node by the in-word select.
+__host__ __device__ __forceinline__ DiskWalkPlan disk_plan_walk(const uint64_t* bits,
+                                                                const uint32_t* pfx,
+                                                                uint32_t n_blocks, uint32_t total,
+                                                                uint32_t start, uint32_t m) {
+  DiskWalkPlan pl;
+  pl.n_found = total;
+  if (total <= m) {
+    pl.walk = DiskWalk{start, start, 1u};
+    pl.n_sample = total;
+    pl.next_start = start;
+    return pl;
+  }
+  const uint32_t sb = start >> 6;
+  const uint64_t below = bits[sb] & ((1ull << (start & 63u)) - 1ull);
+  const uint32_t r0 = pfx[sb] + (uint32_t)__builtin_popcountll(below);
+  const uint32_t k = (uint32_t)(((uint64_t)r0 + m) % total);
+  uint32_t lo = 0, hi = n_blocks;  // pfx[lo] <= k < pfx[hi] (pfx[n_blocks] = total)
+  while (hi - lo > 1u) {
+    const uint32_t mid = lo + (hi - lo) / 2u;
+    if (pfx[mid] <= k) lo = mid; else hi = mid;
+  }
+  const uint32_t stop = 64u * lo + disk_select64(bits[lo], k - pfx[lo]);
+  pl.walk = DiskWalk{start, stop, 0u};
+  pl.n_sample = m;
+  pl.next_start = stop;
+  return pl;
+}
+
+// What a sampled run hands its kernels, by value.  rank.bits == nullptr: every E whole (the ELIG =
+// false instances, which read no table).
+struct DiskSampArgs {
+  DiskRank rank;
+  const uint8_t* cls;     // the pods' class bytes (nullptr: every pod ANY)
+  const uint32_t* cnt;    // [kDiskSelCount] |E| of each selector
+  const uint32_t* start;  // [n_pods] local start ids (nullptr: every walk starts at node 0)
+  uint32_t m, n_nodes, n_pods, node_offset;
+  uint32_t* n_found;      // [n_pods] |E(p)|
+  uint32_t* next_start;   // [n_pods] global ids
+  DiskWalk* walk;         // [n_pods]
+};
+
+// The selectHost draw inside the sampled kernel (yoda_set_tie_draw).
+struct DiskDrawArgs {
+  uint64_t seed, pod_base;
+};
 
 // ---------------------------------------------------------------------------------------
 // The batch's pod classes (host): pods with bit-identical (alpha, beta) and the same selector

@@ -538,6 +538,31 @@ func (g *Handle) ModeBFollow(enable bool) error {
 	return check(g.h, C.yoda_mode_b_follow(g.h, on), "yoda_mode_b_follow")
 }
 
+// ModeBSampling makes Mode B's batch path (ScoreRow, Batch, the draw) honour SetNodeSampling
+// (yoda_mode_b_sampling): a pod's cycle runs over the first numToFind nodes of its eligible set
+// (ModeBFollow's: the whole snapshot while nothing is absent and candidates are off) in the walk
+// that begins at its start id -- the cycle the deployed scheduler runs with
+// percentageOfNodesToScore: 0.  DownloadSampling answers after such a run.  Off, the default,
+// Mode B refuses while sampling is on.  A setting: it stays across uploads.  Greedy, ShardedBatch
+// and ShardedGreedy keep refusing sampling either way.
+// Like the rest of this file, not compiled in this repository (no Go toolchain in the image).
+func (g *Handle) ModeBSampling(enable bool) error {
+	on := C.int(0)
+	if enable {
+		on = 1
+	}
+	return check(g.h, C.yoda_mode_b_sampling(g.h, on), "yoda_mode_b_sampling")
+}
+
+// ModeBSamplingInfo reports {enabled, 1 if the last Mode B run took the sampled kernels,
+// rank-table builds since the upload, 1 if that run used the eligibility instances}
+// (yoda_mode_b_sampling_info; host only).
+func (g *Handle) ModeBSamplingInfo() ([4]uint32, error) {
+	var out [4]uint32
+	rc := C.yoda_mode_b_sampling_info(g.h, (*C.uint32_t)(unsafe.Pointer(&out[0])))
+	return out, check(g.h, rc, "yoda_mode_b_sampling_info")
+}
+
 // GreedyCandidates makes Greedy on this handle honour the candidate classes
 // (yoda_greedy_candidates): each pod's cycle is the candidate-class cycle against the batch's
 // current node state, its class the SetPodClasses entry at the pod's input index (an array as

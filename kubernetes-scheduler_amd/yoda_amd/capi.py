@@ -101,6 +101,8 @@ _SIGS = {
     "yoda_greedy_candidates": ([_vp, C.c_int], C.c_int),
     "yoda_shard_candidates": ([_vp, C.c_int], C.c_int),
     "yoda_mode_b_info": ([_vp, _vp], C.c_int),
+    "yoda_mode_b_sampling": ([_vp, C.c_int], C.c_int),
+    "yoda_mode_b_sampling_info": ([_vp, _vp], C.c_int),
     "yoda_diagnose": ([_vp, _u32], C.c_int),
     "yoda_download_diagnosis": ([_vp, _vp, C.c_uint64], C.c_int),
     "yoda_reason_rows": ([_vp, _vp, C.c_uint64], C.c_int),
@@ -656,6 +658,26 @@ class Yoda:
         self._check(lib().yoda_mode_b_info(self._h, _np_ptr(out)), "yoda_mode_b_info")
         return tuple(int(v) for v in out)
 
+    def mode_b_sampling(self, enable: bool = True):
+        """Mode B's single-handle batch path (run, eval, download, download_sampling, score_rows,
+        the draw) honours set_node_sampling: pod p's cycle is the reference's Mode B cycle on
+        S(p), the first min(num_to_find, |E(p)|) nodes of E(p) in the walk that begins at start[p]
+        (yoda_mode_b_sampling) -- the cycle the deployed scheduler runs.  E(p) is mode_b_follow's
+        set; an absent node or candidate classes still need mode_b_follow.  Off, the default:
+        Mode B raises YODA_ERR_STATE while sampling is on.  greedy, the shard and the comm calls
+        refuse sampling either way.  A setting: it stays across uploads."""
+        self._check(lib().yoda_mode_b_sampling(self._h, 1 if enable else 0),
+                    "yoda_mode_b_sampling")
+
+    def mode_b_sampling_info(self):
+        """(enabled, 1 if the last Mode B run took the sampled kernels, rank-table builds since
+        the upload, 1 if that run used the eligibility instances) -- yoda_mode_b_sampling_info;
+        host only."""
+        out = np.zeros(4, np.uint32)
+        self._check(lib().yoda_mode_b_sampling_info(self._h, _np_ptr(out)),
+                    "yoda_mode_b_sampling_info")
+        return tuple(int(v) for v in out)
+
     def diagnose(self, all: bool = False) -> np.ndarray:
         """Why Filter rejected nodes, after a completed Mode A run (yoda_diagnose +
         yoda_download_diagnosis): uint32 [P, 4] = (not a candidate, number, memory, clock) nodes
@@ -691,8 +713,8 @@ class Yoda:
         node, skips absent nodes and stops once num_to_find nodes of F' have passed.  The
         PreScore maxima do not move; everything downstream of Filter follows the sample.
         num_to_find 0 turns sampling off, as upload_nodes does.  The start array stays across pod
-        uploads.  While on, Mode B, greedy, the shard and comm calls, reason_rows and
-        diagnose(all=True) raise YODA_ERR_STATE."""
+        uploads.  While on, Mode B (unless mode_b_sampling is on), greedy, the shard and comm
+        calls, reason_rows and diagnose(all=True) raise YODA_ERR_STATE."""
         s = None if start is None else np.ascontiguousarray(start, np.uint32).ravel()
         self._check(lib().yoda_set_node_sampling(self._h, int(num_to_find),
                                                  0 if s is None else s.size,
