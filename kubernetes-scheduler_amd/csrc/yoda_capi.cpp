@@ -363,6 +363,19 @@ struct yoda_handle {
   bool flagged_dirty = true;  // n_flagged may be nonzero (a generic run since the last clear)
   bool maxima_sorted = false;  // h->maxima still in the last run's sorted order (n_work rows)
   bool rcp_ready = false;      // phase 1 wrote the reciprocals of its (final) maxima
+  // a private ordered run off the generic path (defer_merge2, set by run_private around its
+  // phase 2): phase 2 leaves the merge of its K2 partials to finalize, which runs it inside its
+  // own kernel (launch_reduce2_finalize); merge2 is that pending merge
+  bool defer_merge2 = false;
+  struct Merge2 {
+    bool on = false;
+    Partials part{};
+    uint32_t C = 0;
+    bool is_f64 = false;
+    const uint64_t* cmask = nullptr;
+    int64_t *best = nullptr, *low = nullptr;
+    uint32_t *idx = nullptr, *ties = nullptr;
+  } merge2;
   bool count_order = false;    // this run orders by the counting sort (private runs)
   DevBuf bsum;              // [wave][node block] BlockMask: the block K1's sparse masks
   bool bm_sparse = false;   // the last K1 wrote the sparse form (bsum + partial masks only)
@@ -1711,6 +1724,7 @@ int phase2(yoda_t* h, int mode, const uint64_t* maxima, const uint32_t* counts, 
            uint32_t* idx, uint32_t* ties, int64_t* low, int64_t* rows = nullptr,
            bool draw = false) {
   const uint32_t P = h->n_work;  // sorted positions of this run
+  h->merge2.on = false;
   if (P == 0) return YODA_OK;
   const uint64_t* cmask2 = nullptr;
   if (h->n_nodes == 0) {
@@ -1823,6 +1837,10 @@ int phase2(yoda_t* h, int mode, const uint64_t* maxima, const uint32_t* counts, 
   // merge reports each pod's best in their place
   Partials pr = part;
   if (mode == YODA_MODE_SCV && h->path == Path::N32 && h->has_k2sum && !rows) pr.low_f = nullptr;
+  if (h->defer_merge2) {  // (finalize merges them in its own kernel)
+    h->merge2 = {true, pr, C2, is_f64, cmask2, best, low, idx, ties};
+    return YODA_OK;
+  }
   HIP_TRY(h, launch_reduce2(pr, C2, P, is_f64, h->node_offset, best, idx, ties, low,
                             h->stream, cmask2));
   return YODA_OK;
@@ -1833,8 +1851,13 @@ int finalize(yoda_t* h, int mode, const uint32_t* counts, const int64_t* best,
              const uint32_t* idx, const uint32_t* ties, const int64_t* low, bool sharded) {
   const uint32_t P = h->n_work;  // sorted positions of this run
   h->k3_pending = false;
+  const yoda_t::Merge2 m2 = h->merge2;  // phase 2's pending merge (a private ordered run)
+  h->merge2.on = false;
   if (P == 0) return YODA_OK;
   const bool generic = h->generic && mode == YODA_MODE_SCV;
+  if (m2.on && !(h->ordered && !generic))  // (not the fused kernel's case: the merge alone)
+    HIP_TRY(h, launch_reduce2(m2.part, m2.C, P, m2.is_f64, h->node_offset, m2.best, m2.idx,
+                              m2.ties, m2.low, h->stream, m2.cmask));
   // the overflow count is written by the generic path only: clear it for those runs, and
   // once after one (yoda_shard_overflow_count reads it)
   if (generic || h->flagged_dirty) HIP_TRY(h, hipMemsetAsync(h->n_flagged.p, 0, 4, h->stream));
@@ -1851,10 +1874,16 @@ int finalize(yoda_t* h, int mode, const uint32_t* counts, const int64_t* best,
     for (auto& pr : pairs) HIP_TRY(h, pr[1]->ensure(pr[0]->bytes));
     FinalScatter sc{h->perm.as<uint32_t>(), Pc, h->counts_alt.as<uint32_t>(),
                     h->best_alt.as<int64_t>(), nullptr, nullptr};
-    HIP_TRY(h, launch_finalize(counts, best, idx, ties, low, P, false, h->pick_alt.as<int32_t>(),
-                               h->status_alt.as<int32_t>(), h->ties_out_alt.as<uint32_t>(),
-                               h->flagged.as<uint32_t>(), h->n_flagged.as<uint32_t>(), sc,
-                               h->stream));
+    if (m2.on)
+      HIP_TRY(h, launch_reduce2_finalize(m2.part, m2.C, P, m2.is_f64, h->node_offset, m2.cmask,
+                                         counts, m2.best, m2.idx, m2.ties, m2.low,
+                                         h->pick_alt.as<int32_t>(), h->status_alt.as<int32_t>(),
+                                         h->ties_out_alt.as<uint32_t>(), sc, h->stream));
+    else
+      HIP_TRY(h, launch_finalize(counts, best, idx, ties, low, P, false,
+                                 h->pick_alt.as<int32_t>(), h->status_alt.as<int32_t>(),
+                                 h->ties_out_alt.as<uint32_t>(), h->flagged.as<uint32_t>(),
+                                 h->n_flagged.as<uint32_t>(), sc, h->stream));
     for (auto& pr : pairs) pr[0]->swap(*pr[1]);
     h->maxima_sorted = true;
     return YODA_OK;
@@ -3151,16 +3180,21 @@ static int run_private(yoda_t* h, int mode, uint32_t flags, bool draw) {
     struct Clear {
       bool& f;
       ~Clear() { f = false; }
-    } clear{h->core_only};
+    } clear{h->core_only}, clear_defer{h->defer_merge2}, clear_merge{h->merge2.on};
     if ((rc = order_pods(h, mode))) return rc;
     if ((rc = phase1(h, mode, h->maxima.as<uint64_t>(), h->counts.as<uint32_t>(),
                      Maxima::OwnFinal)))
       return rc;
-    if ((rc = phase2(h, mode, h->maxima.as<uint64_t>(), h->counts.as<uint32_t>(), h->best.as<int64_t>(),
-                     h->idx.as<uint32_t>(), h->ties.as<uint32_t>(), h->lowest.as<int64_t>(),
-                     nullptr, draw && h->tie_draw)))
-      return rc;
-    if (diag_env("YODA_SEED_DEBUG", 0) && pod_params(h).seed) seed_report(h);
+    // an ordered run off the generic path merges the K2 partials in finalize's kernel (the seed
+    // report reads the merged best scores before finalize: with it on, the two kernels)
+    const bool seed_dbg = diag_env("YODA_SEED_DEBUG", 0);
+    h->defer_merge2 = mode == YODA_MODE_SCV && h->ordered && !h->generic && !seed_dbg;
+    rc = phase2(h, mode, h->maxima.as<uint64_t>(), h->counts.as<uint32_t>(), h->best.as<int64_t>(),
+                h->idx.as<uint32_t>(), h->ties.as<uint32_t>(), h->lowest.as<int64_t>(), nullptr,
+                draw && h->tie_draw);
+    h->defer_merge2 = false;
+    if (rc) return rc;
+    if (seed_dbg && pod_params(h).seed) seed_report(h);
     if ((rc = finalize(h, mode, h->counts.as<uint32_t>(), h->best.as<int64_t>(),
                        h->idx.as<uint32_t>(), h->ties.as<uint32_t>(), h->lowest.as<int64_t>(),
                        false)))

@@ -1684,9 +1684,9 @@ __device__ __forceinline__ uint64_t mask_at(const MaskSrc& m, uint32_t w, uint32
   return 0ull;
 }
 
-// Per-pod merge of K1 chunk partials -> maxima [6][P] and counts [2][P].  One thread per
-// (pod, field) (grid.y = the 6 maxima + 2 counts), chunk loads unrolled so each thread keeps
-// several in flight.  NARROW: u32 maxima partials (the N32 K1).
+// Per-pod merge of K1 chunk partials -> maxima [6][P] and counts [2][P].  One thread per pod
+// folds every maxima word and both counts, a round of chunks' loads in flight at a time
+// (reduce1_pod).  NARROW: u32 maxima partials (the N32 K1).
 __device__ __forceinline__ double ru_100_over(double M);
 
 // rcp != nullptr (a single-handle run, whose maxima are final here): each maxima thread also
@@ -1866,6 +1866,90 @@ __global__ __launch_bounds__(1024) void k_lpt_order(uint32_t* __restrict__ wts,
   lpt_order_body(wts, n_waves, n_pb, order, w);
 }
 
+// One sorted pod's merge: all NW maxima words (T: u32 words of the N32 K1, u64 else) and both
+// counts.  A round is every word of up to four chunks (the mask's next set bits, or the next of
+// 0..C), all loaded before any is folded: 4 (NW + 2) loads in flight per thread.  A round's
+// missing chunks (the last round) repeat its first one -- a max takes it twice for nothing, a
+// count adds 0.
+template <bool NARROW, uint32_t NW>
+__device__ __forceinline__ void reduce1_pod(const uint64_t* __restrict__ pmax,
+                                            const uint32_t* __restrict__ pcnt, uint32_t C,
+                                            uint32_t n_pods, uint32_t p,
+                                            uint64_t* __restrict__ maxima,
+                                            uint32_t* __restrict__ counts,
+                                            double* __restrict__ rcp, const MemTab& mt,
+                                            const unsigned long long* __restrict__ cmask) {
+  using T = typename std::conditional<NARROW, uint32_t, uint64_t>::type;
+  constexpr uint32_t kRound = 4;
+  const T* src = reinterpret_cast<const T*>(pmax) + p;
+  const uint32_t* csrc = pcnt + p;
+  const size_t fs = (size_t)C * n_pods;  // one field's partials
+  T m[NW];
+#pragma unroll
+  for (uint32_t w = 0; w < NW; ++w) m[w] = NARROW ? (T)narrow_floor((int)w, NW) : (T)1;  // floor 1
+  uint32_t nf = 0, nz = 0;
+  // (cmask: only the chunks that wrote -- the wave's bits, a uniform loop)
+  uint64_t bits = cmask != nullptr ? cmask[p >> 6] : 0ull;
+  const uint32_t CN = cmask != nullptr ? (uint32_t)__builtin_popcountll(bits) : C;
+  for (uint32_t k = 0; k < CN; k += kRound) {
+    size_t o[kRound];
+    bool v[kRound];
+#pragma unroll
+    for (uint32_t j = 0; j < kRound; ++j) {
+      v[j] = k + j < CN;
+      uint32_t c = v[j] ? k + j : k;
+      if (cmask != nullptr) {
+        c = v[j] ? (uint32_t)__builtin_ctzll(bits) : 0u;
+        bits &= bits - 1ull;
+      }
+      o[j] = (size_t)c * n_pods;
+      if (cmask != nullptr && !v[j]) o[j] = o[0];
+    }
+    T q[kRound][NW];
+    uint32_t a[kRound], z[kRound];
+#pragma unroll
+    for (uint32_t j = 0; j < kRound; ++j) {
+#pragma unroll
+      for (uint32_t w = 0; w < NW; ++w) q[j][w] = src[(size_t)w * fs + o[j]];
+      a[j] = csrc[o[j]];
+      z[j] = csrc[fs + o[j]];
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < kRound; ++j) {
+#pragma unroll
+      for (uint32_t w = 0; w < NW; ++w) {
+        if constexpr (NARROW) m[w] = narrow_max(m[w], q[j][w], (int)w, NW);
+        else m[w] = umax64(m[w], q[j][w]);
+      }
+      nf += v[j] ? a[j] : 0u;
+      nz += v[j] ? z[j] : 0u;
+    }
+  }
+#pragma unroll
+  for (uint32_t f = 0; f < NW; ++f) {
+    if constexpr (NARROW) {
+      narrow_store(m[f], (int)f, n_pods, p, maxima, mt, NW);
+      if (rcp && NW != kNarrowWords) {
+        store_rcp((int)f, maxima[(size_t)f * n_pods + p], n_pods, p, rcp);
+      } else if (rcp) {
+        const int fa = f == 0 ? kMaxBw : f == 1 ? kMaxCore : f == 2 ? kMaxFree : kMaxTotal;
+        store_rcp(fa, maxima[(size_t)fa * n_pods + p], n_pods, p, rcp);
+        if (f == 1) store_rcp(kMaxPower, maxima[(size_t)kMaxPower * n_pods + p], n_pods, p, rcp);
+      }
+    } else {
+      uint64_t mx = m[f];
+      if (mt.vf && f == kMaxFree) mx = rank_value(mx, mt.vf);  // memory ranks -> values
+      if (mt.vf && f == kMaxTotal) mx = rank_value(mx, mt.vt);
+      maxima[(size_t)f * n_pods + p] = mx;
+      store_rcp((int)f, mx, n_pods, p, rcp);
+    }
+  }
+  counts[p] = nf;
+  counts[(size_t)n_pods + p] = nz;
+}
+
+// Grid: one 256-pod block of the sorted batch per workgroup, one thread per pod; with lpt_w one
+// more workgroup, the first (so that it never starts last), ranks the K2's pod blocks.
 template <bool NARROW>
 __global__ __launch_bounds__(kBlock) void k_reduce1(const uint64_t* __restrict__ pmax,
                                                     const uint32_t* __restrict__ pcnt, uint32_t C,
@@ -1877,58 +1961,25 @@ __global__ __launch_bounds__(kBlock) void k_reduce1(const uint64_t* __restrict__
                                                     uint32_t* __restrict__ lpt_w = nullptr,
                                                     uint32_t* __restrict__ lpt_order = nullptr,
                                                     const unsigned long long* __restrict__ cmask = nullptr) {
-  if (lpt_w != nullptr && blockIdx.x == gridDim.x - 1) {  // the extra block: the K2's order
-    __shared__ __attribute__((aligned(16))) uint32_t w[kLptMax];
-    if (blockIdx.y == 0)
+  uint32_t pb = blockIdx.x;
+  if (lpt_w != nullptr) {
+    if (pb == 0) {  // the extra block: the K2's order
+      __shared__ __attribute__((aligned(16))) uint32_t w[kLptMax];
       lpt_order_body(lpt_w, (n_pods + kWave - 1) / kWave, (n_pods + kBlock - 1) / kBlock,
                      lpt_order, w);
-    return;
+      return;
+    }
+    --pb;
   }
-  const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
-  const uint32_t f = blockIdx.y;  // NARROW: the nw partial words, then the 2 counts
-  const uint32_t NF = NARROW ? nw : 6u;
+  const uint32_t p = pb * kBlock + threadIdx.x;
   if (p >= n_pods) return;
-  if (f < NF) {
-    if constexpr (NARROW) {
-      const uint32_t* src = reinterpret_cast<const uint32_t*>(pmax) + (size_t)f * C * n_pods + p;
-      uint32_t m32 = narrow_floor((int)f, nw);  // floor 1 (collection.go:31-38)
-      if (cmask != nullptr) {  // only the chunks that wrote (the wave's bits; uniform loop)
-        for (uint64_t bits = cmask[p >> 6]; bits != 0ull; bits &= bits - 1ull)
-          m32 = narrow_max(m32, src[(size_t)__builtin_ctzll(bits) * n_pods], (int)f, nw);
-      } else {
-#pragma unroll 8
-        for (uint32_t c = 0; c < C; ++c)
-          m32 = narrow_max(m32, src[(size_t)c * n_pods], (int)f, nw);
-      }
-      narrow_store(m32, (int)f, n_pods, p, maxima, mt, nw);
-      if (rcp && nw != kNarrowWords) {
-        store_rcp((int)f, maxima[(size_t)f * n_pods + p], n_pods, p, rcp);
-      } else if (rcp) {
-        const int fa = f == 0 ? kMaxBw : f == 1 ? kMaxCore : f == 2 ? kMaxFree : kMaxTotal;
-        store_rcp(fa, maxima[(size_t)fa * n_pods + p], n_pods, p, rcp);
-        if (f == 1) store_rcp(kMaxPower, maxima[(size_t)kMaxPower * n_pods + p], n_pods, p, rcp);
-      }
-    } else {
-      uint64_t mx = 1;
-      const uint64_t* src = pmax + (size_t)f * C * n_pods + p;
-#pragma unroll 8
-      for (uint32_t c = 0; c < C; ++c) mx = umax64(mx, src[(size_t)c * n_pods]);
-      if (mt.vf && f == kMaxFree) mx = rank_value(mx, mt.vf);  // memory ranks -> values
-      if (mt.vf && f == kMaxTotal) mx = rank_value(mx, mt.vt);
-      maxima[(size_t)f * n_pods + p] = mx;
-      store_rcp((int)f, mx, n_pods, p, rcp);
-    }
+  if constexpr (NARROW) {
+    if (nw == kNarrowWords)
+      reduce1_pod<true, kNarrowWords>(pmax, pcnt, C, n_pods, p, maxima, counts, rcp, mt, cmask);
+    else
+      reduce1_pod<true, kWideWords>(pmax, pcnt, C, n_pods, p, maxima, counts, rcp, mt, cmask);
   } else {
-    const uint32_t* src = pcnt + (size_t)(f - NF) * C * n_pods + p;
-    uint32_t s = 0;
-    if (cmask != nullptr) {
-      for (uint64_t bits = cmask[p >> 6]; bits != 0ull; bits &= bits - 1ull)
-        s += src[(size_t)__builtin_ctzll(bits) * n_pods];
-    } else {
-#pragma unroll 8
-      for (uint32_t c = 0; c < C; ++c) s += src[(size_t)c * n_pods];
-    }
-    counts[(size_t)(f - NF) * n_pods + p] = s;
+    reduce1_pod<false, 6>(pmax, pcnt, C, n_pods, p, maxima, counts, rcp, mt, cmask);
   }
 }
 
@@ -4758,21 +4809,16 @@ __global__ __launch_bounds__(kBlock) void k_reduce2b(const uint32_t* __restrict_
 
 // Per-pod merge of K2 chunk partials.  Chunks are in node order, so on equal scores the
 // earlier chunk's index (lower) is kept.
-__global__ __launch_bounds__(kBlock) void k_reduce2(const double* __restrict__ pbest_f,
-                                                    const int64_t* __restrict__ pbest_i,
-                                                    const uint32_t* __restrict__ pidx,
-                                                    const uint32_t* __restrict__ pties,
-                                                    const double* __restrict__ plow_f,
-                                                    const int64_t* __restrict__ plow_i,
-                                                    uint32_t C, uint32_t n_pods, int is_f64,
-                                                    uint32_t node_offset,
-                                                    int64_t* __restrict__ best_out,
-                                                    uint32_t* __restrict__ idx_out,
-                                                    uint32_t* __restrict__ ties_out,
-                                                    int64_t* __restrict__ low_out,
-                                                    const unsigned long long* __restrict__ cmask = nullptr) {
-  const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
-  if (p >= n_pods) return;
+struct Reduce2Out {
+  int64_t best, low;
+  uint32_t idx, ties;  // idx: 0xffffffff (no scored node) or the node + node_offset
+};
+__device__ __forceinline__ Reduce2Out reduce2_pod(
+    const double* __restrict__ pbest_f, const int64_t* __restrict__ pbest_i,
+    const uint32_t* __restrict__ pidx, const uint32_t* __restrict__ pties,
+    const double* __restrict__ plow_f, const int64_t* __restrict__ plow_i, uint32_t C,
+    uint32_t n_pods, int is_f64, uint32_t node_offset, uint32_t p,
+    const unsigned long long* __restrict__ cmask) {
   int64_t best = -1, low = kI64Max;
   uint32_t idx = 0xffffffffu, ties = 0;
   // (cmask: only the chunks whose bit is set wrote this run -- the wave's bits, a uniform loop)
@@ -4805,10 +4851,35 @@ __global__ __launch_bounds__(kBlock) void k_reduce2(const double* __restrict__ p
     best = gt ? b : best;
     low = (v && l < low) ? l : low;
   }
-  best_out[p] = best;
-  idx_out[p] = idx == 0xffffffffu ? idx : idx + node_offset;
-  ties_out[p] = ties;
-  low_out[p] = (is_f64 && !plow_f) ? best : low;  // no lowest scores: the best in its place
+  Reduce2Out r;
+  r.best = best;
+  r.idx = idx == 0xffffffffu ? idx : idx + node_offset;
+  r.ties = ties;
+  r.low = (is_f64 && !plow_f) ? best : low;  // no lowest scores: the best in its place
+  return r;
+}
+
+__global__ __launch_bounds__(kBlock) void k_reduce2(const double* __restrict__ pbest_f,
+                                                    const int64_t* __restrict__ pbest_i,
+                                                    const uint32_t* __restrict__ pidx,
+                                                    const uint32_t* __restrict__ pties,
+                                                    const double* __restrict__ plow_f,
+                                                    const int64_t* __restrict__ plow_i,
+                                                    uint32_t C, uint32_t n_pods, int is_f64,
+                                                    uint32_t node_offset,
+                                                    int64_t* __restrict__ best_out,
+                                                    uint32_t* __restrict__ idx_out,
+                                                    uint32_t* __restrict__ ties_out,
+                                                    int64_t* __restrict__ low_out,
+                                                    const unsigned long long* __restrict__ cmask = nullptr) {
+  const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+  if (p >= n_pods) return;
+  const Reduce2Out r = reduce2_pod(pbest_f, pbest_i, pidx, pties, plow_f, plow_i, C, n_pods,
+                                   is_f64, node_offset, p, cmask);
+  best_out[p] = r.best;
+  idx_out[p] = r.idx;
+  ties_out[p] = r.ties;
+  low_out[p] = r.low;
 }
 
 // Wave-per-pod variant of k_reduce2 (many chunks).  Each lane merges a strided subset of
@@ -4960,6 +5031,58 @@ __global__ __launch_bounds__(kBlock) void k_finalize(const uint32_t* __restrict_
     }
   }
   ties_out[o] = t;
+}
+
+// k_reduce2 and k_finalize of an ordered run off the generic path (a private run's last two
+// launches) in one: the thread of a sorted position merges its K2 chunk partials, keeps the
+// merged best / idx / ties / lowest in registers, writes them in sorted order as k_reduce2 does
+// (the draw pass reads the lowest scores there), and applies k_finalize's outcome rules and
+// scatter to the caller's order.  sc.perm != nullptr, sc.maxima == nullptr.
+__global__ __launch_bounds__(kBlock) void k_reduce2_finalize(
+    const double* __restrict__ pbest_f, const int64_t* __restrict__ pbest_i,
+    const uint32_t* __restrict__ pidx, const uint32_t* __restrict__ pties,
+    const double* __restrict__ plow_f, const int64_t* __restrict__ plow_i, uint32_t C,
+    uint32_t n_pods, int is_f64, uint32_t node_offset,
+    const unsigned long long* __restrict__ cmask, const uint32_t* __restrict__ counts,
+    int64_t* __restrict__ best_out, uint32_t* __restrict__ idx_out,
+    uint32_t* __restrict__ ties_sorted, int64_t* __restrict__ low_out,
+    int32_t* __restrict__ pick, int32_t* __restrict__ status, uint32_t* __restrict__ ties_out,
+    FinalScatter sc) {
+  const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+  if (p >= n_pods) return;
+  const uint32_t q = sc.perm[p];  // where this pod's outputs land
+  const uint32_t nf = counts[p], nz = counts[(size_t)n_pods + p];
+  const Reduce2Out r = reduce2_pod(pbest_f, pbest_i, pidx, pties, plow_f, plow_i, C, n_pods,
+                                   is_f64, node_offset, p, cmask);
+  best_out[p] = r.best;
+  idx_out[p] = r.idx;
+  ties_sorted[p] = r.ties;
+  low_out[p] = r.low;
+  // (a padded order's copies write the same values twice)
+  sc.counts[q] = nf;
+  sc.counts[(size_t)sc.n_out + q] = nz;
+  sc.best[q] = r.best;
+  int32_t pk, st;
+  uint32_t t = r.ties;
+  if (nf == 0) {
+    pk = -1;
+    st = 1;
+    t = 0;
+  } else if (nf == 1) {  // k8s: the only feasible node is returned without scoring
+    pk = (int32_t)r.idx;
+    st = 0;
+    t = 1;
+  } else if (nz > 0) {  // Score would divide by TotalMemorySum == 0: Go panics
+    pk = -2;
+    st = 2;
+    t = 0;
+  } else {  // (off the generic path (highest - lowest) * 100 cannot overflow: k_finalize)
+    pk = (int32_t)r.idx;
+    st = 0;
+  }
+  pick[q] = pk;
+  status[q] = st;
+  ties_out[q] = t;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -5924,7 +6047,7 @@ hipError_t launch_reduce1(const Partials& part, uint32_t C, uint32_t n_pods, uin
     if (rcp) return launch_prep2(maxima, n_pods, rcp, s);
   } else {
     const bool lpt = lpt_w != nullptr && !lpt_apart;
-    const dim3 grid((n_pods + kBlock - 1) / kBlock + (lpt ? 1u : 0u), nw ? nw + 2u : 8u);
+    const dim3 grid((n_pods + kBlock - 1) / kBlock + (lpt ? 1u : 0u));
     if (nw)
       hipLaunchKernelGGL(k_reduce1<true>, grid, dim3(kBlock), 0, s, part.max_u, part.cnt, C,
                          n_pods, maxima, counts, rcp, mt, nw, lpt ? lpt_w : nullptr,
@@ -6678,6 +6801,27 @@ hipError_t launch_finalize(const uint32_t* counts, const int64_t* best, const ui
   hipLaunchKernelGGL(k_finalize, pod_grid(n_pods), dim3(kBlock), 0, s, counts, best, idx, ties_in,
                      lowest, n_pods, generic ? 1 : 0, pick, status, ties_out, flagged, n_flagged,
                      sc);
+  return hipGetLastError();
+}
+
+hipError_t launch_reduce2_finalize(const Partials& part, uint32_t C, uint32_t n_pods,
+                                   bool is_f64, uint32_t node_offset, const uint64_t* cmask,
+                                   const uint32_t* counts, int64_t* best, uint32_t* idx,
+                                   uint32_t* ties, int64_t* low, int32_t* pick, int32_t* status,
+                                   uint32_t* ties_out, const FinalScatter& sc, hipStream_t s) {
+  if (!sc.perm || sc.maxima) return hipErrorInvalidValue;
+  if (C > kWaveReduceChunks) {  // many chunks: the wave-per-pod merge, then k_finalize
+    const hipError_t e = launch_reduce2(part, C, n_pods, is_f64, node_offset, best, idx, ties, low,
+                                        s, cmask);
+    if (e != hipSuccess) return e;
+    return launch_finalize(counts, best, idx, ties, low, n_pods, false, pick, status, ties_out,
+                           nullptr, nullptr, sc, s);
+  }
+  hipLaunchKernelGGL(k_reduce2_finalize, pod_grid(n_pods), dim3(kBlock), 0, s, part.best_f,
+                     part.best_i, part.idx, part.ties, part.low_f, part.low_i, C, n_pods,
+                     is_f64 ? 1 : 0, node_offset,
+                     reinterpret_cast<const unsigned long long*>(cmask), counts, best, idx, ties,
+                     low, pick, status, ties_out, sc);
   return hipGetLastError();
 }
 

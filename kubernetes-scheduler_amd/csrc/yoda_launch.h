@@ -97,6 +97,14 @@ hipError_t launch_finalize(const uint32_t* counts, const int64_t* best, const ui
                            bool generic, int32_t* pick, int32_t* status, uint32_t* ties_out,
                            uint32_t* flagged, uint32_t* n_flagged, const FinalScatter& sc,
                            hipStream_t s);
+// launch_reduce2 and launch_finalize of an ordered run off the generic path in one kernel
+// (C <= 48 chunks; beyond, the two launches): best / idx / ties / low in sorted order as
+// launch_reduce2 leaves them, pick / status / ties_out and sc's arrays in the caller's order.
+hipError_t launch_reduce2_finalize(const Partials& part, uint32_t C, uint32_t n_pods,
+                                   bool is_f64, uint32_t node_offset, const uint64_t* cmask,
+                                   const uint32_t* counts, int64_t* best, uint32_t* idx,
+                                   uint32_t* ties, int64_t* low, int32_t* pick, int32_t* status,
+                                   uint32_t* ties_out, const FinalScatter& sc, hipStream_t s);
 hipError_t launch_k3(int K, const unsigned char* nodes, uint32_t n_nodes, uint32_t chunk_nodes,
                      uint32_t C, const PodParams& pp, const uint64_t* maxima, uint32_t n_pods,
                      const uint64_t* bm, uint32_t bm_stride, const uint32_t* flagged,
