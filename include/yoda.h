@@ -150,7 +150,9 @@ int yoda_synchronize(yoda_t* h);
 /* Upload a node snapshot (or a shard of one).  node_offset is the global index of this
  * shard's first node: picks are reported as node_offset + local index.  Replaces the
  * previous snapshot.  Chooses the narrowest exact record format the value ranges allow
- * (DESIGN.md §Exactness). */
+ * (DESIGN.md §Exactness).  Every copy of the upload is ordered on the handle's stream: a step
+ * already queued there (e.g. a yoda_shard_phase1 behind the caller's own work) still reads the
+ * previous snapshot.  The call returns after a synchronisation of that stream. */
 #define YODA_UPLOAD_FORCE_GENERIC 1u /* always the exact-u64 path                     */
 #define YODA_UPLOAD_FORCE_F64 2u     /* never the narrow path (tests)                 */
 #define YODA_UPLOAD_NO_UNIFORM 4u    /* disable the per-node GPU-model factoring (tests) */

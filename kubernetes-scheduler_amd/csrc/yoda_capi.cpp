@@ -187,6 +187,7 @@ struct yoda_handle {
   // memory ranks (yoda_layout.h MemTab): the N32 memory fields are ranks; value tables
   bool mem_ranks = false;
   DevBuf memtab;
+  std::vector<double> h_memtab;  // the host side of memtab's copy, until the next upload's
   MemTab mt = {};
   std::vector<uint64_t> h_frees;  // the distinct card frees, ascending (pod thresholds)
   std::vector<uint64_t> h_totals;  // ... and the distinct card totals (yoda_replace_nodes)
@@ -2487,11 +2488,16 @@ int upload_gtables(yoda_t* h, const yoda_node_soa* nd, const MemCodes& mc) {
                             h->stream));
   h->mt = MemTab{};
   if (mc.ranks) {  // value tables: v[0] = v[1] = 0, v[2 + i] = the i-th distinct value
-    std::vector<double> vt(4 + mc.frees.size() + mc.totals.size(), 0.0);
+    // (the previous upload ended in a synchronisation: its copy of h_memtab is done)
+    std::vector<double>& vt = h->h_memtab;
+    vt.assign(4 + mc.frees.size() + mc.totals.size(), 0.0);
     for (size_t i = 0; i < mc.frees.size(); ++i) vt[2 + i] = (double)mc.frees[i];
     for (size_t i = 0; i < mc.totals.size(); ++i) vt[4 + mc.frees.size() + i] = (double)mc.totals[i];
     HIP_TRY(h, h->memtab.ensure(vt.size() * 8));
-    HIP_TRY(h, hipMemcpy(h->memtab.p, vt.data(), vt.size() * 8, hipMemcpyHostToDevice));
+    // on the handle's stream, as every table of the upload: a step still queued there reads the
+    // previous snapshot's values (a copy on the null stream does not wait for a non-blocking one)
+    HIP_TRY(h, hipMemcpyAsync(h->memtab.p, vt.data(), vt.size() * 8, hipMemcpyHostToDevice,
+                              h->stream));
     h->mt.vf = h->memtab.as<double>();
     h->mt.vt = h->memtab.as<double>() + 2 + mc.frees.size();
     h->mt.nf = (uint32_t)mc.frees.size();

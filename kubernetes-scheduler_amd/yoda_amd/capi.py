@@ -229,6 +229,9 @@ class Yoda:
     def set_stream(self, stream_ptr: int):
         self._check(lib().yoda_set_stream(self._h, _vp(stream_ptr)), "yoda_set_stream")
 
+    def use_own_stream(self):
+        self._check(lib().yoda_use_own_stream(self._h), "yoda_use_own_stream")
+
     def synchronize(self):
         self._check(lib().yoda_synchronize(self._h), "yoda_synchronize")
 
