@@ -2822,6 +2822,17 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(K <= 8 ?
   // table above, the others after the ids), so the per-pod pass reads a lane's basic score as
   // in a uniform wave instead of computing its card terms per node
   constexpr uint32_t TT = (TOPK && !RK) ? (TKO > 8 ? 3u : 2u) : 1u;
+  // WIDE: a wave of several reciprocal sets keeps four basic scores per set in a node's record,
+  // as a uniform wave does, so a node whose qualifying-card count takes up to four values over
+  // the wave is served by its record.  Sets 0 and 1 in the record's words 8-15, sets 2 and 3 in
+  // the first eight words of the node's prefix-table row (PSW = 10), which only a wave of
+  // uniform maxima (or a top-k list pass, TT > 1) fills.  On for the one instantiation it was
+  // measured on -- argmax, K = 8, one-model snapshot, no memory ranks, f32 small fields: the
+  // headline step's -- and for the traced (STATS) kernel of the same K and Q32, so that the
+  // trace shows the same passes.  It costs registers: every other
+  // instantiation keeps the two-valued records until it is measured there.
+  constexpr bool WIDE = !TOPK && !RK && K == 8 && Q32 && (!MIX || STATS);
+  static_assert(!WIDE || PSW % 2u == 0u, "a table row's word pairs are read as 8-byte words");
   // (RCPS: the sets' reciprocals, then one more slot: the decoupled bound's, below)
   constexpr uint32_t RECS = TAB, RCPS = TAB + kWave * REC, IDW = RCPS + 16 * (kSets + 1),
                      XTAB = IDW + kWave, LDSW = XTAB + (TT - 1) * TAB;
@@ -3002,6 +3013,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(K <= 8 ?
     return (uint64_t)__double_as_longlong(x + 4503599627370496.0) - 0x4330000000000000ull;
   };
   uint32_t npart = 0;  // STATS: per-pod-pass nodes of this (wave, chunk)
+  uint32_t nwork = 0;  // STATS: blocks of this (wave, chunk) that were worked (not pruned / empty)
+  uint32_t nrec = 0;   // STATS: the per-pod nodes among npart that were served by node records
+  uint32_t nwide = 0;  // STATS: of those, nodes of a several-set wave with more than two values
   // TOPK: the lane's list (per-pod nodes) and the wave-uniform list (U nodes), descending
   uint64_t pl[TL], ul[TL];
 #pragma unroll
@@ -3114,6 +3128,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(K <= 8 ?
     }
     if (feas_b == 0) return;  // no pod of the wave can use any node of the block
     worked = true;
+    if (STATS) ++nwork;
     if (STATS && !trace && lane == 0) atomicAdd(stats + 14, 1ull);
     uint64_t fast_b = 0, u_b = 0, rec_b = 0;
     // the clock the per-pod passes compare with the pods' scv/clock (algorithm.go:271): the
@@ -3285,12 +3300,55 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(K <= 8 ?
         }
       } else {
         // several reciprocal sets: no U nodes (scores differ across the wave), a record per
-        // two-valued one-model node with the basic scores of every set (not with memory ranks,
-        // RK: the per-set loop's table gathers would spill the kernel; those nodes take the
-        // per-pod pass)
-        const bool is_rec = !RK && rec_ok && fast && range <= 1u;
+        // two-valued (WIDE: up to four-valued) one-model node with the basic scores of every
+        // set.  Not with memory ranks, RK: the per-set loop's table gathers would spill the
+        // kernel; those nodes take the per-pod pass.
+        const bool is_rec = !RK && rec_ok && fast && range <= (WIDE ? 3u : 1u);
         rec_b = ballot(is_rec);
-        if (!RK && (rec_b != 0ull || (TT > 1u && ballot(fast && !is_rec) != 0ull))) {
+        if constexpr (WIDE) {
+          if (rec_b != 0ull) {
+            if (STATS) nwide += (uint32_t)__builtin_popcountll(ballot(is_rec && range > 1u));
+            if (is_rec) {
+              *reinterpret_cast<uint4*>(rec) = make_uint4(ck, (uint32_t)mask,
+                                                          (uint32_t)(mask >> 32), thr);
+              *reinterpret_cast<uint4*>(rec + 4) = make_uint4((uint32_t)stat_u,
+                                                              (uint32_t)(stat_u >> 32), thr1, thr2);
+            }
+            // the basic score at nq_lo + i (i <= range; repeated past it) under each set, two
+            // values a pass over the sets, the second pass only for a block that has a node with
+            // more than two (four accumulators in one pass spill the kernel: it has no registers
+            // to spare)
+            const uint32_t npass = ballot(is_rec && range > 1u) != 0ull ? 2u : 1u;
+#pragma nounroll
+            for (uint32_t pass = 0; pass < npass; ++pass) {
+              const uint32_t qa = nq_lo + min(range, 2u * pass), qb = nq_lo + min(range, 2u * pass + 1u);
+#pragma nounroll
+              for (uint32_t q = 0; q < nsets; ++q) {
+                const RS* r = reinterpret_cast<const RS*>(lds + RCPS + 16 * q);
+                const double* d = reinterpret_cast<const double*>(lds + RCPS + 16 * q + 8);
+                const double v_free = d[0], v_tot = d[1];
+                const uint32_t shared = card_shared_terms(bw, ck, core, pw, r[0], r[1], r[2]);
+                uint32_t acc = 0, sa = 0, sb = 0;
+#pragma unroll
+                for (int t = 0; t < K; ++t) {
+                  acc += mem_term<false>(fs.v[t], ts.v[t], v_free, v_tot, args.mt);
+                  sa = (uint32_t)(t + 1) == qa ? acc : sa;
+                  sb = (uint32_t)(t + 1) == qb ? acc : sb;
+                }
+                if (is_rec) {
+                  uint32_t* v = q < 2u ? rec + 8 + 4 * q : lds + lane * PSW + 4 * (q - 2u);
+                  const uint2 ab = make_uint2(qa * shared + sa, qb * shared + sb);
+                  if (pass == 0u) {  // (a one-pass block: the second value repeated)
+                    *reinterpret_cast<uint2*>(v) = ab;
+                    *reinterpret_cast<uint2*>(v + 2) = make_uint2(ab.y, ab.y);
+                  } else {
+                    *reinterpret_cast<uint2*>(v + 2) = ab;
+                  }
+                }
+              }
+            }
+          }
+        } else if (!RK && (rec_b != 0ull || (TT > 1u && ballot(fast && !is_rec) != 0ull))) {
           if (is_rec) {
             *reinterpret_cast<uint4*>(rec) = make_uint4(ck, (uint32_t)mask,
                                                         (uint32_t)(mask >> 32), thr);
@@ -3344,6 +3402,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(K <= 8 ?
       if (!uni_max) atomicAdd(stats + 8, (unsigned long long)__builtin_popcountll(part_b));
     }
     if (STATS) npart += (uint32_t)__builtin_popcountll(part_b);
+    if (STATS) nrec += (uint32_t)__builtin_popcountll(rec_b);
     // node order is not kept across the loops: the tie rule keeps the lowest index.
     // Branch-free (selects, no exec-mask branches): f = this pod lane is feasible on nn.
     uint64_t rb = rec_b;
@@ -3380,6 +3439,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(K <= 8 ?
         rs[k] = *reinterpret_cast<const uint4*>(r + 4);
         if (uni_max) {
           rp[k] = *reinterpret_cast<const uint4*>(r + 8);
+        } else if constexpr (WIDE) {  // the lane's set: four values
+          const uint32_t* v = set < 2u ? r + 8 + 4 * set : lds + jj[k] * PSW + 4 * (set - 2u);
+          const uint2 lo = *reinterpret_cast<const uint2*>(v);
+          const uint2 hi = *reinterpret_cast<const uint2*>(v + 2);
+          rp[k] = make_uint4(lo.x, lo.y, hi.x, hi.y);
         } else {
           const uint2 pr = *reinterpret_cast<const uint2*>(r + 8 + 2 * set);
           rp[k] = make_uint4(pr.x, pr.y, pr.y, pr.y);
@@ -3548,8 +3612,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(K <= 8 ?
       };
       if (prune) drop_pruned();
       while (todo != 0ull) {
-        const uint64_t first = (todo & hot_w) != 0ull ? (todo & hot_w) : todo;
-        const uint32_t j = (uint32_t)__builtin_ctzll(first);
+        const uint32_t j = k2_claim_pick(todo, hot_w);
         todo &= ~(1ull << j);
         block((wb + j) << 6);
         if (prune && worked) {
@@ -3569,15 +3632,18 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(K <= 8 ?
   }
   const size_t slot2 = (size_t)(p >> 6) * gridDim.y + chunk;
   if (trace && lane == 0 && slot2 < (size_t)(stats[15] >> 8)) {
-    {  // per-(wave, chunk) trace: start, end (100 MHz clock), per-pod nodes
+    {  // per-(wave, chunk) trace: start, end (100 MHz clock), per-pod nodes | worked blocks << 32
+      // | record-served nodes << 48 (a chunk has fewer than 2^16 blocks and nodes)
       unsigned long long* tr = stats + 16 + 4 * slot2;
       tr[0] = t_start;
       tr[1] = wall_clock64();
-      tr[2] = npart;
+      tr[2] = npart | ((unsigned long long)min(nwork, 0xffffu) << 32) |
+              ((unsigned long long)min(nrec, 0xffffu) << 48);
       // uniform maxima | G's << 1 | decoupled bounds << 2 | reciprocal sets << 4
+      // | several-set record nodes with more than two values << 8 (capped at 255)
       // | set-up end << 16 | block-list walk end << 40 (ticks after the start)
       tr[3] = (uni_max ? 1ull : 0ull) | (use_g ? 2ull : 0ull) | (dec ? 4ull : 0ull) |
-              ((unsigned long long)nsets << 4) |
+              ((unsigned long long)nsets << 4) | ((unsigned long long)min(nwide, 0xffu) << 8) |
               ((unsigned long long)min((unsigned long long)(t_setup - t_start), 0xffffffull) << 16) |
               ((unsigned long long)min((unsigned long long)(t_pass - t_start), 0xffffffull) << 40);
     }
@@ -4844,12 +4910,9 @@ __device__ __forceinline__ Reduce2Out reduce2_pod(
       l = plow_i[o];
     }
     const uint32_t ix = pidx[o], tt = pties[o];
-    const bool v = b >= 0, gt = v && b > best, eq = v && b == best;
     // (equal bests: the lower node -- chunks need not be in node order, block-grouped runs)
-    idx = gt ? ix : (eq ? min(idx, ix) : idx);
-    ties = gt ? tt : (eq ? ties + tt : ties);
-    best = gt ? b : best;
-    low = (v && l < low) ? l : low;
+    argmax_fold(best, idx, ties, b, ix, tt);
+    low = (b >= 0 && l < low) ? l : low;
   }
   Reduce2Out r;
   r.best = best;

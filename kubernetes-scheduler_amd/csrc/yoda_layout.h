@@ -306,6 +306,35 @@ __host__ __device__ inline uint64_t window_bits(const uint64_t* words, uint32_t 
   return bits;
 }
 
+// One pod's argmax over a set of nodes: the best score (below 0: no node), the lowest node index
+// that reaches it and how many nodes do.  Folding the states of two disjoint node sets gives the
+// state of their union: the higher score wins; on an equal score the ties add up and the lower
+// index stays.  Commutative and associative (tools/check_k2_help.cpp), so K2's chunk partials
+// merge in any order (k_reduce2, k_reduce2_finalize).  Selects only: no exec-mask branch on the
+// device.  (ArgmaxState: the three values as one object, for host code.)
+struct ArgmaxState {
+  int64_t best = -1;
+  uint32_t idx = 0xffffffffu, ties = 0u;
+};
+__host__ __device__ inline void argmax_fold(int64_t& best, uint32_t& idx, uint32_t& ties,
+                                            int64_t b, uint32_t ix, uint32_t tt) {
+  const bool v = b >= 0, gt = v && b > best, eq = v && b == best;
+  const uint32_t lo = ix < idx ? ix : idx;
+  idx = gt ? ix : (eq ? lo : idx);
+  ties = gt ? tt : (eq ? ties + tt : ties);
+  best = gt ? b : best;
+}
+__host__ __device__ inline void argmax_fold(ArgmaxState& a, const ArgmaxState& b) {
+  argmax_fold(a.best, a.idx, a.ties, b.best, b.idx, b.ties);
+}
+
+// The block K2 walks a window's listed, unpruned blocks (a 64-bit word, bit j = block wb + j) the
+// hot blocks first, then in list order: the bit it takes next (todo != 0).
+__host__ __device__ inline uint32_t k2_claim_pick(uint64_t todo, uint64_t hot) {
+  const uint64_t first = (todo & hot) != 0ull ? (todo & hot) : todo;
+  return (uint32_t)__builtin_ctzll(first);
+}
+
 // The block K1's wave bounds (k1_block_n32's set-up: the minima / maxima of the wave's pod
 // fields, a pure function of the batch), written once per pod wave by the cost probe that runs
 // before the block K1 of a private run (k1_probe) and read by each of the wave's chunk tasks in

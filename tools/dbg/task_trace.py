@@ -6,7 +6,8 @@ is set (YODA_K1_TRACE=1: the K1 records instead of the K2).  Prints the task cou
 distribution, the kernel's span, the mean concurrency (sum of task durations / span) and the
 durations split by per-pod work (npart = 0: the task's fixed cost plus its lane = block pass),
 the tasks in flight at each tenth of the span and, with --chunks, the co-termination loss of a
-static grid's four-wave workgroups and the 20 last-ending tasks.
+static grid's four-wave workgroups and the 20 last-ending tasks with their worked blocks (K2: also
+the worked-block distribution of the tasks with per-pod nodes).
 
     YODA_K2_TRACE=200000 [YODA_K1_TRACE=1] python tools/dbg/task_trace.py [--pods P] [--nodes N]
 """
@@ -62,6 +63,10 @@ dur = (t[:, 1] - t[:, 0]) / 100.0  # us at 100 MHz
 span = (t[:, 1].max() - t[:, 0].min()) / 100.0
 npart = t[:, 2] & 0xffffffff
 nblk = t[:, 2] >> 32  # K1: blocks classified node by node
+nrec = np.zeros_like(nblk)
+if kern == "k2":  # K2: blocks worked (not pruned / empty), per-pod nodes served by node records
+    nrec = (t[:, 2] >> 48) & 0xffff
+    nblk = nblk & 0xffff
 q = lambda v, x: float(np.percentile(v, x)) if len(v) else None  # noqa: E731
 out = {"kernel": kern, "tasks": int(used.sum()), "span_us": span,
        "mean_concurrency": float(dur.sum() / span) if span > 0 else None,
@@ -83,7 +88,9 @@ if kern == "k1" and len(dur) > 3:
     out["span_share"] = {"base": float(coef[0] * len(dur) / dur.sum()),
                          "node_blocks": float(coef[1] * nblk.sum() / dur.sum()),
                          "part": float(coef[2] * npart.sum() / dur.sum())}
-# phases (the trace's word 3): K1 set-up end | block-pass end << 32; K2 flags | set-up end << 16 |
+# phases (the trace's word 3): K1 set-up end | block-pass end << 32; K2 flags (uniform maxima, G's
+# << 1, decoupled bounds << 2, reciprocal sets << 4) | nwide << 8 (a several-set wave's record
+# nodes with more than two values, capped at 255) | set-up end << 16 |
 # block-list walk end << 40 (ticks after the task's start)
 w3 = tr[used][:, 3].astype(np.uint64)
 if kern == "k1":
@@ -99,6 +106,24 @@ if z.any():
     out["phase_us_mean_npart0"] = {"setup": float(t_set[z].mean()),
                                    "pass": float((t_pass[z] - t_set[z]).mean()),
                                    "epilogue": float((dur[z] - t_pass[z]).mean())}
+w3_all = tr[used][:, 3].astype(np.uint64)
+if kern == "k2" and (npart > 0).any():
+    # worked blocks of the tasks with per-pod nodes: what a split by block could hand to helpers
+    wp = nblk[npart > 0]
+    out["worked_blocks_npart_pos"] = {
+        "mean": float(wp.mean()), "p50": q(wp, 50), "p90": q(wp, 90), "p99": q(wp, 99),
+        "max": int(wp.max()),
+        "hist_1_2_4_8_16_32_64": np.histogram(wp, bins=[0, 1, 2, 4, 8, 16, 32, 64, 1 << 30])[0].tolist()}
+    # per-pod nodes by the pass that serves them: node records (three LDS loads a node), or the
+    # wave-uniform loop over the rest (lane reads of the node's registers, a table or exact score)
+    out["npart_by_pass"] = {"records": int(nrec.sum()), "loop": int((npart - nrec).sum())}
+    ms = (w3_all & np.uint64(1)) == 0  # tasks of waves with several reciprocal sets
+    out["several_sets"] = {"tasks": int(ms.sum()), "dur_sum_us": float(dur[ms].sum()),
+                           "npart": int(npart[ms].sum()), "records": int(nrec[ms].sum()),
+                           "loop_us_per_node": float(np.polyfit((npart - nrec)[ms], dur[ms], 1)[0])
+                           if ms.sum() > 2 and (npart - nrec)[ms].any() else None}
+    out["worked_blocks_all"] = {"mean": float(nblk.mean()), "max": int(nblk.max()),
+                                "sum": int(nblk.sum())}
 if kern == "k2":  # task time by wave kind: G waves, decoupled-bound (non-G) waves, others
     fl = w3 & np.uint64(0xffff)
     for name, sel in (("g", (fl & np.uint64(2)) != 0), ("dec", (fl & np.uint64(4)) != 0),
@@ -135,7 +160,10 @@ if a.chunks:
     last = np.argsort(t[:, 1])[-20:][::-1]
     out["last_ending"] = [{"wave": int(wave[i]), "chunk": int(chunk[i]), "start_us": float(st[i]),
                            "dur_us": float(dur[i]), "npart": int(npart[i]),
-                           "start_rank": int(rank[wave[i]])} for i in last]
+                           "worked_blocks": int(nblk[i]), "nrec": int(nrec[i]),
+                           "pass_us": float(t_pass[i] - t_set[i]),
+                           "flags": int(w3[i] & np.uint64(0xff)),
+                           "nwide": int((w3[i] >> np.uint64(8)) & np.uint64(0xff)), "start_rank": int(rank[wave[i]])} for i in last]
     out["longest_task_share_of_span"] = float(dur.max() / span) if span > 0 else None
 print(json.dumps(out), flush=True)
 # raw records for offline analysis (TASK_TRACE_DUMP=<path.npz>): slot (= wave * chunks + chunk),
